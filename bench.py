@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- headline benchmark of the lens-flare hot path on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4_1gpu|c5_1gpu]
+    python bench.py [--gpus N --steps K --warmup W] [--config c2|c3|c4_1gpu|c5_1gpu] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 (`python bench.py --gpus N` with N > 1 and no torchrun environment starts the N ranks itself, as child
 processes, before it touches the GPU: lens_flare_amd.sharding.self_launch.)
@@ -23,6 +23,11 @@ raytraced_renderer.cpp:706-709).  The paths of one sensor sample share legs, whi
 computes once; counting every path on its own (what a per-path tracer such as the CPU baseline
 does) gives `value_logical`, 3.9x larger on c3 -- an algorithmic saving, reported as such, never as
 throughput.  Inputs are resident in HBM before the timed region starts.
+
+A plain run sets up, warms up, times --steps frames and prints the JSON line; what it reports beside `value` is read
+off those frames.  --full adds what takes runs of its own: the CPU baseline and the reference's CPU flare path (both
+before the first GPU call; --no-cpu leaves them out) and the sampling / culling variants timed after the headline
+frames.  --dump-outputs DIR writes what the last timed frame computed as DIR/<name>.npy (see dump_outputs).
 """
 import argparse
 import hashlib
@@ -57,6 +62,8 @@ FP32_PEAK_TFLOPS = 256 * 4 * 32 * 2 * CLOCK_HZ / 1e12   # 157.3: 32 lanes x FMA 
 FLOP_PER_EVENT = 38.0
 FLOP_PER_FRESNEL = 20.0
 SUN_NS = (0.521445, 0.517156)
+DUMP_BUDGET_BYTES = 64 * 10 ** 6          # --dump-outputs: all arrays together
+DUMP_SEED = 20261016                      # ... and the pixels of a frame too large for its share
 ABLATION_FILE = os.path.join(ROOT, "profiles", "r04_all_weights_ablation.json")
 
 
@@ -372,6 +379,34 @@ def reference_flare_path_gpu(pkg, out):
         return out
 
 
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: every array as out_dir/<name>.npy, together under DUMP_BUDGET_BYTES.  Small arrays as they are
+    (float64); a frame buffer whole in float64 if its share of the budget holds it, else whole in float32, else a fixed
+    sample of its pixels in float64 (sorted flat pixel indices drawn by np.random.default_rng(DUMP_SEED): the same
+    pixels in every run of the same frame size).  -> {name: how it was written}"""
+    os.makedirs(out_dir, exist_ok=True)
+    header = 128                                                # (an .npy header)
+    small = [k for k, a in arrays.items() if a.nbytes <= 1 << 16]
+    big = [k for k in arrays if k not in small]
+    share = (DUMP_BUDGET_BYTES - sum(arrays[k].nbytes + header for k in small)) // max(1, len(big)) - header
+    how = {}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a, np.float64)
+        if name in small or a.nbytes <= share:
+            how[name] = "float64"
+        elif a.nbytes // 2 <= share:
+            a = a.astype(np.float32)
+            how[name] = "float32"
+        else:
+            px = a.reshape(-1, a.shape[-1])
+            k = share // (px.shape[1] * 8)
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(px.shape[0], k, replace=False))
+            a = px[idx]
+            how[name] = f"float64, {k} of {px.shape[0]} pixels (rows of the flattened frame, seed {DUMP_SEED})"
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return how
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -383,9 +418,15 @@ def main():
     ap.add_argument("--spp", type=int, default=0)
     ap.add_argument("--cpu-seconds", type=float, default=24.0)
     ap.add_argument("--ref-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: without the CPU baseline and the reference's CPU runs")
+    ap.add_argument("--full", action="store_true",
+                    help="also the CPU baseline, the reference's CPU flare path and the sampling / culling variants")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed frame computed as DIR/<name>.npy (at most 64 MB)")
     ap.add_argument("--cpu-leg", default=None, help=argparse.SUPPRESS)   # internal: one leg of cpu_baseline, in a child process
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     cfg = dict(CONFIGS[args.config])
     W, H, spp = args.width or cfg["W"], args.height or cfg["H"], args.spp or cfg["spp"]
     if args.cpu_leg:
@@ -413,7 +454,7 @@ def main():
     cpu, ref_path = None, None
     profiled = any(k.startswith("ROCPROFILER_") or k.startswith("ROCPROF_") for k in os.environ) or \
         "rocprof" in os.environ.get("LD_PRELOAD", "")
-    if rank == 0 and world == 1 and not args.no_cpu and not profiled:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu and not profiled:
         cpu = cpu_baseline(args.config, W, H, args.cpu_seconds)
         ref_path = reference_flare_path(pkg, args.ref_seconds, gpu_leg=False)
 
@@ -728,6 +769,21 @@ def main():
     barrier()
     dt = time.perf_counter() - t0
     lf.timing_enable(False)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        # the last timed frame as a caller receives it: the composed frame (every rank holds all of it after the exchange),
+        # with one rank also the march's ghost buffer and the scene term (under a deal the other ranks' parts of those
+        # are undefined), and the flares find_sun_pos found
+        flares = lf.get_flares()
+        arrays = {"sample_buffer": lf.read_buffer(pkg.SAMPLE_BUFFER)}
+        if world == 1:
+            arrays["ghost_buffer"] = lf.read_buffer(pkg.GHOST_BUFFER)
+            if cfg["scene"]:
+                arrays["scene_buffer"] = lf.read_buffer(pkg.SCENE_BUFFER)
+        arrays["flare_origins"] = flares["origins"]
+        arrays["flare_radiance"] = flares["radiance"]
+        dumped = dump_outputs(args.dump_outputs, arrays)
+        del arrays
 
     cnt = lf.counters()
     stats = lf.march_stats()
@@ -739,7 +795,7 @@ def main():
     # apart (tile correlation 7.4; profiles/r04_tile_stride.json).  Rounds 1-3: 4 x 4 sub-cells over 8 x 8
     # adjacent pixels (37.7).  1 x 1 sub-cells = every pixel draws on its own (1.0).
     sampling_variants = None
-    if world == 1 and not cfg["scene"] and not args.no_cpu:   # (--no-cpu = the march alone: profiler passes, A/B runs)
+    if args.full and world == 1 and not cfg["scene"] and not args.no_cpu:   # (--no-cpu = the march alone: profiler passes, A/B runs)
         sampling_variants = {}
 
         def timed_variant():
@@ -917,7 +973,7 @@ def main():
             # the march computes the legs shared by the paths of one sample once
             "value_logical": logical / dt / 1e6,
             "shared_leg_saving": logical / executed if executed else None,
-            "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full,
             "ms_per_step": dt / args.steps * 1e3,
             "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
             "dtype": "f32", "data": "synthetic",
@@ -1022,6 +1078,8 @@ def main():
             "cpu_baseline": cpu,
             "reference_flare_path": ref_path,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         print(json.dumps(out), flush=True)
     lf.close()
     if multi:

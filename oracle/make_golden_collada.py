@@ -7,14 +7,17 @@ reference ships and commits
   tests/golden/collada/<scene>.dae            the input (a data file of the reference, copied)
   tests/golden/collada/<scene>.dump.txt.gz    every triangle / normal / light / camera / material it
                                               ends up with, as hex floats (ref_driver.cpp `collada`)
-  tests/golden/collada/sha256.json            sha256 of that dump for ALL shipped scenes (the big
-                                              ones are checked in this container only)
+  tests/golden/collada/sha256.json            sha256 of that dump for ALL shipped scenes
+  tests/golden/collada/<scene>.dae.xz         the input of the scenes of STORED_XZ, xz-compressed: with
+                                              the .dae files above and lens-flare_amd/data/maxplanck.dae
+                                              every kind of light and material the 21 scenes hold
   tests/golden/c96x72_pyramid_dae.npz         an end-to-end frame: the reference renders the flat
                                               scene of pyramid.dae (its sun makes the flare)
 Only runs in the build container (needs /root/reference)."""
 import gzip
 import hashlib
 import json
+import lzma
 import os
 import shutil
 import subprocess
@@ -29,6 +32,17 @@ REF = mg.REF
 DUMP = mg.DUMP
 OUT = os.path.join(mg.GOLD, "collada")
 SMALL = ["pyramid.dae", "sky/CBspheres_lambertian.dae", "sky/CBempty.dae", "sky/CBgems.dae"]
+# hemisphere light (banana), mirror and glass spheres (CBspheres), microfacet (CBspheres_microfacet_al_ag): small
+# scenes with what the other stored inputs lack; tests/test_collada_loader.py hashes their dumps against sha256.json
+STORED_XZ = ["keenan/banana.dae", "sky/CBspheres.dae", "sky/CBspheres_microfacet_al_ag.dae"]
+
+
+def write_scene_inputs(rels):
+    """tests/golden/collada/<scene>.dae.xz: the scene files `rels` (paths under the reference's dae/), byte for byte"""
+    for rel in rels:
+        data = open(os.path.join(REF, "dae", rel), "rb").read()
+        with open(os.path.join(OUT, os.path.basename(rel) + ".xz"), "wb") as f:
+            f.write(lzma.compress(data, preset=9 | lzma.PRESET_EXTREME))
 
 
 def ref_dump(path, tmp):
@@ -80,6 +94,7 @@ def main():
                         g.write(d)
                 print("scene", rel, len(d), "bytes", flush=True)
     json.dump(sha, open(os.path.join(OUT, "sha256.json"), "w"), indent=1, sort_keys=True)
+    write_scene_inputs(STORED_XZ)
     # end to end: the reference renders what its loader made of pyramid.dae
     spheres, tris, suns, points = parse_dump(ref_dump(os.path.join(REF, "dae", "pyramid.dae"), tmp))
     assert suns and tris

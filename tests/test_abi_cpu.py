@@ -26,8 +26,15 @@ def test_header_symbols_exported():
 
 def test_no_device_fails_loudly():
     """Without a GPU lf_create must return LF_ERR_NO_DEVICE -- never a CPU fallback."""
-    import torch
-    if torch.cuda.is_available():
+    # Asked in a child process: torch carries a HIP runtime of its own, and once that one has started in this process
+    # before the library's, the library's sees no device -- every GPU test after this one in the same session would fail.
+    import subprocess
+    import sys
+    probe = subprocess.run([sys.executable, *(["-s"] if sys.flags.no_user_site else []), "-c",
+                            "import torch; print(int(torch.cuda.is_available()))"],
+                           capture_output=True, text=True, timeout=300)
+    assert probe.returncode == 0, probe.stderr[-2000:]
+    if probe.stdout.split()[-1] == "1":
         import pytest
         pytest.skip("a GPU is present")
     pkg = _pkg()
