@@ -74,7 +74,9 @@ lf_status lf_set_stream(lf_ctx* ctx, void* hip_stream);
 lf_status lf_synchronize(lf_ctx* ctx);
 
 /* ---------------------------------------------------------------- frame ------------------ */
-/* replaces: PathTracer::set_frame_size (pathtracer.cpp:66-69) + clear (:71-79) */
+/* replaces: PathTracer::set_frame_size (pathtracer.cpp:66-69) + clear (:71-79).  Deals the whole frame to this context
+ * again (undoes lf_set_row_interleave / lf_set_block_deal); a cull table share set before (lf_comm_share_cull /
+ * lf_set_cull_share) stays. */
 lf_status lf_set_frame(lf_ctx* ctx, int width, int height);
 /* multi-GPU sharding: this context renders sensor rows [y0, y1) only (default: all rows).
  * Mirrors the tile queue of raytraced_renderer.cpp:314-328, one band of tile rows per GPU. */
@@ -89,7 +91,9 @@ lf_status lf_set_row_interleave(lf_ctx* ctx, int phase, int period);
  * shrink with the number of ranks and the table never crosses a link (where lf_set_row_interleave needs
  * lf_comm_share_cull / lf_set_cull_share and a second collective per frame).  lf_comm_gather / lf_group_gather
  * exchange blocks then.  Pixels, counters summed over the ranks and the gathered frame are the single-GPU frame's.
- * lf_set_row_interleave switches back. */
+ * lf_set_row_interleave (or lf_set_frame) switches back.  A frame dealt by blocks shares no table: refused (LF_ERR_STATE)
+ * while lf_comm_share_cull / lf_set_cull_share(rank, N > 1) is on, and they are refused while it is dealt; its
+ * lf_get_cull_table has zero rows for the blocks of other ranks. */
 lf_status lf_set_block_deal(lf_ctx* ctx, int rank, int nranks);
 /* replaces the public fields PathTracer::ns_aa, flare_radius, flare_intensity
  * (pathtracer.h:93-94,107) */
@@ -529,7 +533,8 @@ typedef enum {
   LF_CULL_APPLIED = 0,              /* the culled march ran */
   LF_CULL_OFF = 1,                  /* lf_set_march_culling(0) */
   LF_CULL_NO_STOP = 2,              /* the prescription has no stop: nothing bounds a pupil cell */
-  LF_CULL_TOO_MANY_PATHS = 3,       /* more than 128 selected paths */
+  LF_CULL_TOO_MANY_PATHS = 3,       /* more than 128 selected paths -- or more than 64 with a table that is not the context's
+                                       alone (shared, lf_comm_share_cull / lf_set_cull_share, or dealt by blocks, lf_set_block_deal) */
   LF_CULL_TOO_MANY_SAMPLES = 4,     /* more than 4096 samples per pixel (64 x 64 strata) */
   LF_CULL_BLOCK_TOO_LARGE = 5,      /* even a block of 16 x 16 pixels is more than 1.8 mm on this sensor */
   LF_CULL_TABLE_TOO_FULL = 6,       /* the table starts more than 0.10 + 1.6 / paths of everything: the path tree is faster */
@@ -583,7 +588,8 @@ lf_status lf_test_knob(lf_ctx* ctx, const char* name, double value);
  *                                  (all zero if this launch does not cull) for an in-place all-gather of slabs in rank
  *                                  order, lf_cull_commit takes the completed table over, and the lf_trace_ghosts that
  *                                  follows (same spp, same inputs) marches with it; a launch without them is refused.
- *                                  (1 rank: off.) */
+ *                                  (1 rank: off.)
+ * Both are refused (LF_ERR_STATE) on a frame dealt by blocks (lf_set_block_deal), which shares nothing. */
 lf_status lf_comm_share_cull(lf_ctx* ctx, int on);
 lf_status lf_set_cull_share(lf_ctx* ctx, int rank, int nranks);
 lf_status lf_cull_prepare(lf_ctx* ctx, int spp);

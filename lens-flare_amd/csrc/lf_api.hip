@@ -306,7 +306,7 @@ lf_status lf_set_frame(lf_ctx* ctx, int width, int height) {
     return lf_fail(ctx, LF_ERR_INVALID, "frame size out of range");
   LF_HIP(ctx, hipSetDevice(ctx->device));
   ctx->W = width; ctx->H = height; ctx->y0 = 0; ctx->y1 = height;
-  ctx->row_period = 1; ctx->row_phase = 0;
+  lf_install_split(ctx, ctx->split.with_deal(LfSplit::kRows, 0, 1));    // the whole frame (a table share set before stays)
   // padded for every interleave period up to 8 (ceil(n/p) p <= n + p - 1); larger periods
   // re-allocate in lf_set_row_interleave
   return alloc_frame_buffers(ctx, ((height + 7) / 8 + 7) * 8);
@@ -332,8 +332,7 @@ lf_status lf_set_row_interleave(lf_ctx* ctx, int phase, int period) {
     lf_status st = alloc_frame_buffers(ctx, padded_rows(ctx->H, period));
     if (st != LF_OK) return st;
   }
-  ctx->row_phase = phase; ctx->row_period = period;
-  if (ctx->deal_by_block) { ctx->deal_by_block = false; ctx->cull_hash = 0; if (ctx->cull_share_how == 3) { ctx->cull_share_how = 0; ctx->cull_share_n = 1; ctx->cull_share_rank = 0; } }
+  lf_install_split(ctx, ctx->split.with_deal(LfSplit::kRows, phase, period));
   return LF_OK;
 }
 
@@ -344,15 +343,10 @@ lf_status lf_set_block_deal(lf_ctx* ctx, int rank, int nranks) {
   if (!ctx) return LF_ERR_INVALID;
   if (nranks < 1 || nranks > 64 || rank < 0 || rank >= nranks) return lf_fail(ctx, LF_ERR_INVALID, "block deal: need 0 <= rank < nranks <= 64");
   if (ctx->W == 0) return lf_fail(ctx, LF_ERR_STATE, "lf_set_block_deal before lf_set_frame");
-  if (ctx->cull_share_how == 1 || ctx->cull_share_how == 2)
+  if (ctx->split.table != LfSplit::kOwn)
     return lf_fail(ctx, LF_ERR_STATE, "lf_set_block_deal: the cull table is shared between ranks (lf_comm_share_cull / lf_set_cull_share): "
                                       "a frame dealt by blocks shares nothing");
-  ctx->row_phase = rank; ctx->row_period = nranks;
-  ctx->deal_by_block = nranks > 1;
-  ctx->cull_share_how = nranks > 1 ? 3 : 0;       // the pre-pass builds the rows of this rank's blocks and nobody else's
-  ctx->cull_share_rank = nranks > 1 ? rank : 0;
-  ctx->cull_share_n = nranks;
-  ctx->cull_hash = 0; ctx->cull_hash_pending = 0; ctx->cull_fresh = false;
+  lf_install_split(ctx, ctx->split.with_deal(nranks > 1 ? LfSplit::kBlocks : LfSplit::kRows, rank, nranks));   // (1: the whole frame)
   return LF_OK;
 }
 
@@ -954,17 +948,16 @@ lf_status lf_set_march_culling(lf_ctx* ctx, int mode) {
 lf_status lf_set_cull_share(lf_ctx* ctx, int rank, int nranks) {
   if (!ctx) return LF_ERR_INVALID;
   if (nranks < 1 || nranks > 64 || rank < 0 || rank >= nranks) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_cull_share: 0 <= rank < nranks <= 64");
-  if (ctx->cull_share_how == 1) return lf_fail(ctx, LF_ERR_STATE, "lf_set_cull_share: the table is shared through the communicator (lf_comm_share_cull)");
-  ctx->cull_share_how = nranks > 1 ? 2 : 0;
-  ctx->cull_share_rank = nranks > 1 ? rank : 0;
-  ctx->cull_share_n = nranks;
-  ctx->cull_hash = 0; ctx->cull_hash_pending = 0; ctx->cull_fresh = false;
+  if (ctx->split.table == LfSplit::kComm) return lf_fail(ctx, LF_ERR_STATE, "lf_set_cull_share: the table is shared through the communicator (lf_comm_share_cull)");
+  if (nranks > 1 && ctx->split.deal == LfSplit::kBlocks)
+    return lf_fail(ctx, LF_ERR_STATE, "lf_set_cull_share: the frame is dealt by blocks (lf_set_block_deal): every rank builds the rows it reads, nothing is shared");
+  lf_install_split(ctx, nranks > 1 ? ctx->split.with_table(LfSplit::kHost, rank, nranks) : ctx->split.with_table(LfSplit::kOwn));
   return LF_OK;
 }
 
 lf_status lf_cull_prepare(lf_ctx* ctx, int spp) {
   if (!ctx) return LF_ERR_INVALID;
-  if (ctx->cull_share_how != 2) return lf_fail(ctx, LF_ERR_STATE, "lf_cull_prepare without lf_set_cull_share(rank, nranks > 1)");
+  if (ctx->split.table != LfSplit::kHost) return lf_fail(ctx, LF_ERR_STATE, "lf_cull_prepare without lf_set_cull_share(rank, nranks > 1)");
   if (!ctx->lens_valid || !ctx->ap[LF_APERTURE_STARBURST].valid || ctx->W == 0)
     return lf_fail(ctx, LF_ERR_STATE, "lf_cull_prepare: frame, prescription and aperture mask come first");
   if (spp < 1) return LF_ERR_INVALID;
@@ -978,15 +971,15 @@ lf_status lf_cull_table_view(lf_ctx* ctx, void** device_ptr, uint64_t* entries, 
   if (ctx->cull_hash_pending == 0) return LF_OK;           // (this launch does not cull: nothing to exchange)
   LF_HIP(ctx, hipSetDevice(ctx->device));
   LF_HIP(ctx, hipStreamSynchronize(ctx->stream));          // the slab is written when the host's exchange reads it
-  *entries_per_rank = (uint64_t)ctx->cull_share_nb * (uint64_t)(ctx->cull_cells + 1);
-  *entries = *entries_per_rank * (uint64_t)ctx->cull_share_n_resident;
+  *entries_per_rank = (uint64_t)ctx->cull_resident.nb * (uint64_t)(ctx->cull_cells + 1);
+  *entries = *entries_per_rank * (uint64_t)ctx->cull_resident.n;
   *device_ptr = ctx->cull_dev;
   return LF_OK;
 }
 
 lf_status lf_cull_commit(lf_ctx* ctx) {
   if (!ctx) return LF_ERR_INVALID;
-  if (ctx->cull_share_how != 2) return lf_fail(ctx, LF_ERR_STATE, "lf_cull_commit without lf_set_cull_share(rank, nranks > 1)");
+  if (ctx->split.table != LfSplit::kHost) return lf_fail(ctx, LF_ERR_STATE, "lf_cull_commit without lf_set_cull_share(rank, nranks > 1)");
   if (ctx->cull_hash_pending == 0) return LF_OK;
   LF_HIP(ctx, hipSetDevice(ctx->device));
   const uint64_t h = ctx->cull_hash_pending;
@@ -1087,13 +1080,14 @@ lf_status lf_get_cull_table(lf_ctx* ctx, uint64_t* out, size_t n_entries) {
   if (n_entries != n) return lf_fail(ctx, LF_ERR_INVALID, "lf_get_cull_table: size must be blocks_x * blocks_y * (cells + 1)");
   LF_HIP(ctx, hipSetDevice(ctx->device));
   LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (ctx->cull_share_nb > 0 && ctx->cull_share_n_resident > 1) {
+  const LfCullSlab& r = ctx->cull_resident;
+  if (r.n > 1) {
     // a shared table lies slab by slab (lf_cull_row_of_block): handed out in block order all the same
-    const size_t re = (size_t)(ctx->cull_cells + 1), rows = (size_t)ctx->cull_share_nb * ctx->cull_share_n_resident;
+    const size_t re = (size_t)(ctx->cull_cells + 1), rows = (size_t)r.nb * r.n;
     std::vector<uint64_t> raw(rows * re);
     LF_HIP(ctx, hipMemcpy(raw.data(), ctx->cull_dev, raw.size() * sizeof(uint64_t), hipMemcpyDeviceToHost));
     for (int b = 0; b < ctx->cull_bx * ctx->cull_by; b++)
-      std::memcpy(out + (size_t)b * re, raw.data() + lf_cull_row_of_block(b, ctx->cull_share_n_resident, ctx->cull_share_nb) * re, re * sizeof(uint64_t));
+      std::memcpy(out + (size_t)b * re, raw.data() + lf_cull_row_of_block(b, r.n, r.nb) * re, re * sizeof(uint64_t));
     return LF_OK;
   }
   LF_HIP(ctx, hipMemcpy(out, ctx->cull_dev, n * sizeof(uint64_t), hipMemcpyDeviceToHost));

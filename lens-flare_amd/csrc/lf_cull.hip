@@ -1579,7 +1579,7 @@ int lf_cull_reason_of(const lf_ctx* ctx, int G) {
   if (!ctx->lens_lambda_monotonic) return LF_CULL_DISPERSION;
   // (a mask has 64 bits; up to 128 paths go in two launches over the halves of the selection: lfk_march -- with a table
   // of this context's own)
-  if (ctx->pairs.n > 2 * kCullMaxPaths || (ctx->pairs.n > kCullMaxPaths && ctx->cull_share_how != 0)) return LF_CULL_TOO_MANY_PATHS;
+  if (ctx->pairs.n > 2 * kCullMaxPaths || (ctx->pairs.n > kCullMaxPaths && lf_cull_table_split(ctx))) return LF_CULL_TOO_MANY_PATHS;
   if (G < 1 || G > 64) return LF_CULL_TOO_MANY_SAMPLES;
   // a block must be SMALL on the sensor for 15 rays to bound it: <= 1.8 mm (the full-enumeration comparison finds no
   // skipped lit ray up to 7.2 mm blocks, profiles/r05_cull_block_size.json) -- frames narrower than 1280 pixels on a
@@ -1599,7 +1599,7 @@ int lf_cull_block_log2(const lf_ctx* ctx, int spp, int n_lambda) {
   int lg = kCullBlockLog2;
   while (lg > 4 && (double)(1 << lg) * mm_per_px > kCullMaxBlockMm) lg--;
   if ((double)(1 << lg) * mm_per_px > kCullMaxBlockMm) return -1;
-  if (lg == kCullBlockLog2 && !ctx->deal_by_block && (double)(2 << lg) * mm_per_px <= kCullBigBlockMm && (long long)spp * n_lambda < 768) {
+  if (lg == kCullBlockLog2 && ctx->split.deal != LfSplit::kBlocks && (double)(2 << lg) * mm_per_px <= kCullBigBlockMm && (long long)spp * n_lambda < 768) {
 #ifdef LF_EXPERIMENTS
     if (std::getenv("LF_CULL_SMALL_BLOCKS")) return lg;
 #endif
@@ -1716,15 +1716,15 @@ __global__ __launch_bounds__(256) void k_cull_audit(const LfLensDev* __restrict_
 lf_status lfk_cull_finish(lf_ctx* ctx, uint64_t hash) {
   if (!ctx->cull_popc_dev) LF_HIP(ctx, hipMalloc((void**)&ctx->cull_popc_dev, 4 * sizeof(unsigned long long)));
   LF_HIP(ctx, hipMemsetAsync(ctx->cull_popc_dev, 0, 4 * sizeof(unsigned long long), ctx->stream));
-  const size_t rows = ctx->cull_share_nb > 0 ? (size_t)ctx->cull_share_nb * (size_t)std::max(1, ctx->cull_share_n_resident)
-                                             : (size_t)ctx->cull_bx * ctx->cull_by;
+  const LfCullSlab& slab = ctx->cull_resident;
+  const size_t rows = slab.nb > 0 ? (size_t)slab.nb * (size_t)slab.n : (size_t)ctx->cull_bx * ctx->cull_by;
   // the blocks this context marches: all of them -- or, the frame dealt by blocks, its own (whose rows lie together: its slab)
   const int n_blk = ctx->cull_bx * ctx->cull_by;
-  const bool own = ctx->cull_own_rows_only;
-  const int own_n = own ? ctx->cull_share_n_resident : 1, own_rank = own ? ctx->cull_share_rank : 0;
+  const bool own = slab.own_rows_only;
+  const int own_n = own ? slab.n : 1, own_rank = own ? slab.rank : 0;
   const int n_own_blk = (n_blk - own_rank + own_n - 1) / own_n;
   const size_t row_entries = (size_t)ctx->cull_cells + 1;
-  if (own) hipLaunchKernelGGL(k_cull_popcount, dim3(1024), dim3(256), 0, ctx->stream, ctx->cull_dev + (size_t)own_rank * ctx->cull_share_nb * row_entries,
+  if (own) hipLaunchKernelGGL(k_cull_popcount, dim3(1024), dim3(256), 0, ctx->stream, ctx->cull_dev + (size_t)own_rank * slab.nb * row_entries,
                               (size_t)n_own_blk, ctx->cull_cells, ctx->cull_popc_dev);
   else hipLaunchKernelGGL(k_cull_popcount, dim3(1024), dim3(256), 0, ctx->stream, ctx->cull_dev, rows, ctx->cull_cells, ctx->cull_popc_dev);
   LF_HIP(ctx, hipGetLastError());
@@ -1735,7 +1735,7 @@ lf_status lfk_cull_finish(lf_ctx* ctx, uint64_t hash) {
     std::memset(&a, 0, sizeof(a));
     a.W = ctx->W; a.H = ctx->H; a.pitch = L.pitch; a.half_w = 0.5f * (float)ctx->W; a.half_h = 0.5f * (float)ctx->H;
     a.blocks_x = ctx->cull_bx; a.blocks_y = ctx->cull_by; a.blk_log2 = ctx->cull_blk_log2;
-    a.share_n = ctx->cull_share_nb > 0 ? ctx->cull_share_n_resident : 1; a.share_nb = ctx->cull_share_nb;
+    a.share_n = slab.n; a.share_nb = slab.nb;
     a.P = ctx->cull_P; a.n_paths = ctx->pairs.n; a.n_lambda = L.n_lambda; a.march_k = ctx->march_k; a.prog_recs = ctx->pairs.prog_recs;
     a.pupil_h = L.pupil_h; a.vz = L.pupil_z - L.z_sensor; a.geom_norm = L.geom_norm; a.inv_stop_h = 1.0f / L.stop_h;
     a.lobe_thr = lf_march_lobe_thr(L);
@@ -1769,6 +1769,23 @@ lf_status lfk_cull_finish(lf_ctx* ctx, uint64_t hash) {
   return LF_OK;
 }
 
+// The slab of table rows this context builds for a table of blocks of 2^blk_log2 pixels (lf_cull_row_of_block).  Dealt by
+// blocks (lf_set_block_deal): the rows of this rank's blocks and nobody else's -- the deal's block is 64 pixels, a frame whose
+// cull blocks are smaller builds the whole table on every rank (small frames: cheap).  A table shared between ranks: the
+// rank's slab, the others come from the all-gather.
+static LfCullSlab lf_cull_slab_of(const lf_ctx* ctx, int blk_log2) {
+  const LfSplit& s = ctx->split;
+  LfCullSlab slab;
+  if (s.deal == LfSplit::kBlocks) {
+    if (blk_log2 == kDealBlockLog2) { slab.rank = s.rank; slab.n = s.n; slab.own_rows_only = true; }
+  } else if (s.table == LfSplit::kComm && ctx->comm_nranks > 1) {
+    slab.rank = ctx->comm_rank; slab.n = ctx->comm_nranks;
+  } else if (s.table == LfSplit::kHost) {
+    slab.rank = s.table_rank; slab.n = s.table_n;
+  }
+  return slab;
+}
+
 lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp) {
   const LfLensDev& L = ctx->lens;
   const lf_ctx::CullRules& R = ctx->cull_rules;
@@ -1780,12 +1797,10 @@ lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp) {
   if (a.blk_log2 < 0) return lf_fail(ctx, LF_ERR_STATE, "cull pre-pass: no block size applies (lf_cull_applies comes first)");
   a.blocks_x = (ctx->W + (1 << a.blk_log2) - 1) >> a.blk_log2;
   a.blocks_y = (ctx->H + (1 << a.blk_log2) - 1) >> a.blk_log2;
-  // a table shared between ranks: this one builds the rows of the blocks b with b % n == rank (lf_cull_row_of_block) -- or
-  // (cull_share_how 3: the frame dealt by blocks, lf_set_block_deal) ONLY those, nobody needs the others.  The deal's block
-  // is 64 pixels: a frame whose cull blocks are smaller builds the whole table on every rank (small frames: cheap)
-  const bool shared = ctx->cull_share_how != 0 && ctx->cull_share_n > 1 && (ctx->cull_share_how != 3 || a.blk_log2 == kDealBlockLog2);
-  a.share_n = shared ? ctx->cull_share_n : 1;
-  a.share_rank = shared ? ctx->cull_share_rank : 0;
+  LfCullSlab slab = lf_cull_slab_of(ctx, a.blk_log2);
+  const bool shared = slab.n > 1;
+  a.share_n = slab.n;
+  a.share_rank = slab.rank;
   a.share_nb = (a.blocks_x * a.blocks_y + a.share_n - 1) / a.share_n;
   const int m = cull_m(ctx, G);
   a.P_final = G * m;
@@ -1828,6 +1843,10 @@ lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp) {
   h = fnv(h, ctx->pairs.ij, sizeof(int) * 2 * (size_t)ctx->pairs.n);
   h = fnv(h, &ctx->mask_generation, sizeof(ctx->mask_generation));
   h = fnv(h, &ctx->cull_rules_custom, sizeof(ctx->cull_rules_custom));
+  if (shared) {   // (same slab, different tables: only this rank's rows, or all of them completed by an all-gather)
+    const int how[2] = {(int)ctx->split.table, slab.own_rows_only ? 1 : 0};
+    h = fnv(h, how, sizeof(how));
+  }
   if (h == 0) h = 1;
   const size_t nblk = (size_t)a.blocks_x * a.blocks_y;
   const size_t rows = (size_t)a.share_nb * (size_t)a.share_n;         // (= nblk unless shared: equal slabs, the last ones padded)
@@ -1842,11 +1861,11 @@ lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp) {
   ctx->cull_bx = a.blocks_x; ctx->cull_by = a.blocks_y; ctx->cull_cells = a.P_final * a.P_final; ctx->cull_G = G;
   ctx->cull_P = a.P_final; ctx->cull_m = m; ctx->cull_blk_log2 = a.blk_log2;
   if (reuse) return LF_OK;
-  if (shared && ctx->cull_share_how == 2 && !ctx->cull_prepare_only)
+  if (ctx->split.table == LfSplit::kHost && !ctx->cull_prepare_only)
     return lf_fail(ctx, LF_ERR_STATE, "the cull table is shared through the host (lf_set_cull_share): lf_cull_prepare, the host's "
                                       "all-gather and lf_cull_commit come before lf_trace_ghosts, with the same inputs");
-  ctx->cull_share_nb = shared ? a.share_nb : 0;
-  ctx->cull_share_n_resident = a.share_n;
+  slab.nb = shared ? a.share_nb : 0;
+  ctx->cull_resident = slab;
   if (entries > ctx->cull_cap) {
     LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
     if (ctx->cull_dev) (void)hipFree(ctx->cull_dev);
@@ -1934,8 +1953,7 @@ lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp) {
     }
   }
   // (comm_force_exchange: tests only -- the collective also with a single rank, as lf_comm_gather does)
-  ctx->cull_own_rows_only = shared && ctx->cull_share_how == 3;
-  if (ctx->cull_share_how == 1 && (shared || ctx->comm_force_exchange)) {
+  if (ctx->split.table == LfSplit::kComm && (shared || ctx->comm_force_exchange)) {
     // every rank has built its slab: one in-place all-gather completes the table everywhere
     const lf_status st = lf_comm_allgather_u64_inplace(ctx, ctx->cull_dev, (size_t)a.share_nb * row_entries);
     if (st != LF_OK) return st;
@@ -1955,7 +1973,7 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
   MarchArgs a = a_in;
   LfCullArgs c;
   c.table = ctx->cull_dev; c.blocks_x = ctx->cull_bx; c.blocks_y = ctx->cull_by; c.cells = ctx->cull_cells;
-  c.share_n = ctx->cull_share_nb > 0 ? ctx->cull_share_n_resident : 1; c.share_nb = ctx->cull_share_nb;
+  c.share_n = ctx->cull_resident.n; c.share_nb = ctx->cull_resident.nb;
   c.blk_log2 = ctx->cull_blk_log2;
   c.multi = ctx->cull_blk_log2 < 3 + a.xs ? 1 : 0;
   // the started paths' common leg is marched once (march_started_set) if a higher path index never leaves it later:

@@ -136,7 +136,7 @@ double* frame_buffer(lf_ctx* ctx, int which) { return which == 0 ? ctx->sample :
 // the exchange's unit: a tile row (8 rows x W x 3) or a block (64 x 64 x 3); `groups` units per rank
 struct Shape { size_t groups, e; };
 Shape shape(const lf_ctx* ctx, int world) {
-  if (ctx->deal_by_block) {
+  if (ctx->split.deal == LfSplit::kBlocks) {
     const size_t nblk = (size_t)((ctx->W + kBlk - 1) / kBlk) * (size_t)((ctx->H + kBlk - 1) / kBlk);
     return Shape{(nblk + world - 1) / world, kBlkE};
   }
@@ -168,7 +168,7 @@ lf_status launch_pack(lf_ctx* ctx, int which, int rank, int world, hipStream_t s
   const size_t n = s.groups * s.e;
   const dim3 grid((unsigned)((n + 255) / 256));
   hipStream_t q = stream ? stream : ctx->stream;
-  if (ctx->deal_by_block) {
+  if (ctx->split.deal == LfSplit::kBlocks) {
     const int bx = (ctx->W + kBlk - 1) / kBlk, nblk = bx * ((ctx->H + kBlk - 1) / kBlk);
     if (ctx->comm_f32)
       hipLaunchKernelGGL(k_pack_blocks<float>, grid, dim3(256), 0, q, frame_buffer(ctx, which), (float*)ctx->comm_stage, rank, world,
@@ -191,7 +191,7 @@ lf_status launch_unpack(lf_ctx* ctx, int which, int rank, int world, hipStream_t
   const size_t n = (size_t)world * s.groups * s.e;
   const dim3 grid((unsigned)((n + 255) / 256));
   hipStream_t q = stream ? stream : ctx->stream;
-  if (ctx->deal_by_block) {
+  if (ctx->split.deal == LfSplit::kBlocks) {
     const int bx = (ctx->W + kBlk - 1) / kBlk, nblk = bx * ((ctx->H + kBlk - 1) / kBlk);
     if (ctx->comm_f32)
       hipLaunchKernelGGL(k_unpack_blocks<float>, grid, dim3(256), 0, q, (const float*)stage_recv(ctx, s.groups * s.e),
@@ -217,10 +217,10 @@ void invalidate_tonemap(lf_ctx* ctx, int which) {
 lf_status check_gather_args(lf_ctx* ctx, int which, int world) {
   if (!ctx || which < 0 || which > 2) return LF_ERR_INVALID;
   if (ctx->W == 0) return lf_fail(ctx, LF_ERR_STATE, "gather before lf_set_frame");
-  if (ctx->row_period != world)
+  if (ctx->split.n != world)
     return lf_fail(ctx, LF_ERR_STATE, "gather: the row interleave does not match the communicator (frame resized?)");
   const Shape s = shape(ctx, world);
-  if (!ctx->deal_by_block && (size_t)ctx->H_alloc * ctx->W * 3 < s.groups * world * s.e)
+  if (ctx->split.deal != LfSplit::kBlocks && (size_t)ctx->H_alloc * ctx->W * 3 < s.groups * world * s.e)
     return lf_fail(ctx, LF_ERR_STATE, "gather: frame buffers are not padded for this world size");
   return LF_OK;
 }
@@ -431,10 +431,12 @@ lf_status lf_comm_gather_async(lf_ctx* ctx, int which) {
 // (the march) when it is done.
 lf_status lf_comm_share_cull(lf_ctx* ctx, int on) {
   if (!ctx) return LF_ERR_INVALID;
-  if (!on) { ctx->cull_share_how = 0; ctx->cull_share_n = 1; ctx->cull_share_rank = 0; return LF_OK; }
+  if (!on) { lf_install_split(ctx, ctx->split.with_table(LfSplit::kOwn)); return LF_OK; }
   LF_COMM_REFUSE_POISONED(ctx);
   if (!ctx->comm) return lf_fail(ctx, LF_ERR_STATE, "lf_comm_share_cull before lf_comm_init_rank");
-  ctx->cull_share_how = 1; ctx->cull_share_n = ctx->comm_nranks; ctx->cull_share_rank = ctx->comm_rank;
+  if (ctx->split.deal == LfSplit::kBlocks)
+    return lf_fail(ctx, LF_ERR_STATE, "lf_comm_share_cull: the frame is dealt by blocks (lf_set_block_deal): every rank builds the rows it reads, nothing is shared");
+  lf_install_split(ctx, ctx->split.with_table(LfSplit::kComm));     // (its slab: comm_rank of comm_nranks)
   return LF_OK;
 }
 
@@ -495,8 +497,9 @@ lf_status lf_comm_abort(lf_ctx* ctx) {
     comm = ctx->comm;
     ctx->comm = nullptr; ctx->comm_nranks = 1; ctx->comm_rank = 0;
     ctx->comm_pending = false;
-    // (a table shared through this communicator: back to every rank building its own)
-    if (ctx->cull_share_how == 1) { ctx->cull_share_how = 0; ctx->cull_share_n = 1; ctx->cull_share_rank = 0; ctx->cull_hash = 0; }
+    // (a table shared through this communicator: back to every rank building its own -- and the resident table, which an
+    // aborted all-gather may have left half complete, is not taken again)
+    if (ctx->split.table == LfSplit::kComm) { lf_install_split(ctx, ctx->split.with_table(LfSplit::kOwn)); ctx->cull_hash = 0; }
   }
   if (!comm) return LF_OK;
   Rccl* r = rccl();
@@ -537,7 +540,7 @@ lf_status lf_comm_destroy(lf_ctx* ctx) {
     Rccl* r = rccl();
     if (r) (void)r->CommDestroy((ncclComm_t)ctx->comm);
     ctx->comm = nullptr; ctx->comm_nranks = 1; ctx->comm_rank = 0;
-    if (ctx->cull_share_how == 1) { ctx->cull_share_how = 0; ctx->cull_share_n = 1; ctx->cull_share_rank = 0; ctx->cull_hash = 0; }
+    if (ctx->split.table == LfSplit::kComm) { lf_install_split(ctx, ctx->split.with_table(LfSplit::kOwn)); ctx->cull_hash = 0; }
   }
   return LF_OK;
 }
@@ -697,7 +700,7 @@ lf_status lf_group_share_cull(lf_group* g, int spp) {
   if (!g || spp < 1) return LF_ERR_INVALID;
   const int n = (int)g->ctx.size();
   if (n == 1) return LF_OK;
-  if (g->ctx[0]->deal_by_block) return LF_OK;       // dealt by blocks: every context builds the rows it reads, nothing to share
+  if (g->ctx[0]->split.deal == LfSplit::kBlocks) return LF_OK;       // dealt by blocks: every context builds the rows it reads, nothing to share
   for (int r = 0; r < n; r++) {
     const lf_status st = lf_set_cull_share(g->ctx[r], r, n);
     if (st != LF_OK) { g->err = lf_last_error(g->ctx[r]); return st; }

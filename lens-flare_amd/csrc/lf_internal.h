@@ -252,6 +252,24 @@ __host__ __device__ inline bool lf_deal_mine(const LfDeal& d, int x, int y) {
   if (d.n <= 1) return true;
   return d.bx > 0 ? ((y >> kDealBlockLog2) * d.bx + (x >> kDealBlockLog2)) % d.n == d.rank : (y >> 3) % d.n == d.rank;
 }
+// What a context was asked to do with other ranks: the deal of its pixels, and who completes its cull table.
+// Invariant: deal == kBlocks => table == kOwn (a rank that owns whole cull blocks builds the rows it reads and nothing else).
+struct LfSplit {
+  // the deal: tile rows t (8 sensor rows) with t % n == rank (lf_set_row_interleave), or 64 x 64-pixel blocks b (row-major)
+  // with b % n == rank (lf_set_block_deal; kBlocks only with n > 1)
+  enum Deal { kRows, kBlocks } deal = kRows;
+  int rank = 0, n = 1;
+  // who completes the cull table: nobody, this context builds all it reads / the library's RCCL communicator, inside
+  // lf_trace_ghosts (lf_comm_share_cull; the slab is comm_rank's of comm_nranks) / the host (lf_set_cull_share: lf_cull_prepare
+  // -> its own all-gather -> lf_cull_commit; the slab is table_rank's of table_n > 1, kHost only)
+  enum Table { kOwn, kComm, kHost } table = kOwn;
+  int table_rank = 0, table_n = 1;
+  LfSplit with_deal(Deal d, int r, int k) const { LfSplit s = *this; s.deal = d; s.rank = r; s.n = k; return s; }
+  LfSplit with_table(Table t, int r = 0, int k = 1) const { LfSplit s = *this; s.table = t; s.table_rank = r; s.table_n = k; return s; }
+};
+// A slab of cull table rows: this context builds the rows of the blocks b with b % n == rank (nb rows, lf_cull_row_of_block)
+// -- and, own_rows_only (the frame dealt by blocks), nobody completes the others.  {0, 1, 0, false}: the whole table.
+struct LfCullSlab { int rank = 0, n = 1, nb = 0; bool own_rows_only = false; };
 
 // ---- lens camera (round 4): the scene imaged through the prescription --------------------------
 // The primary path N-1 .. 0 of a sensor sample (the ray travels -z, against the light), one row per
@@ -312,8 +330,7 @@ struct lf_ctx {
 
   int W = 0, H = 0, y0 = 0, y1 = 0;
   int H_alloc = 0;                     // rows allocated (H rounded up to 64) for in-place gathers
-  int row_period = 1, row_phase = 0;   // tile rows t (8 sensor rows) with t % period == phase -- or, dealt by blocks:
-  bool deal_by_block = false;          // lf_set_block_deal: 64 x 64-pixel blocks b (row-major) with b % period == phase
+  LfSplit split;                       // how the frame is shared with other ranks: written by lf_install_split alone
   int ns_aa = 1;
   double flare_radius = 25.0, flare_intensity = 1.0;
   int flare_arithmetic = 0;   // lf_set_flare_arithmetic: 0 auto (exact pow in MT19937 parity mode), 1 exact, 2 fast
@@ -414,13 +431,7 @@ struct lf_ctx {
   size_t cull_list_cap[2] = {0, 0};
   unsigned* cull_counts = nullptr;             // [levels][kCullMaxPaths] list lengths
   int cull_m = 1;                              // table cells per axis inside one stratum
-  // the pre-pass shared between the ranks of a multi-GPU frame (lf_set_cull_share / lf_comm_share_cull):
-  int cull_share_rank = 0, cull_share_n = 1;   // this context builds the rows of the blocks b with b % n == rank
-  int cull_share_how = 0;                      // 1: the library's RCCL communicator completes the table inside lf_trace_ghosts;
-                                               // 2: the host does (lf_cull_prepare -> its own all-gather -> lf_cull_commit);
-                                               // 3: nobody does -- the frame is dealt by blocks (lf_set_block_deal), a rank needs its own rows only
-  int cull_share_nb = 0, cull_share_n_resident = 1;   // rows per slab and slabs of the RESIDENT table (0 / 1: not shared)
-  bool cull_own_rows_only = false;             // ... of which only this rank's slab is built (the frame dealt by blocks: nobody reads the others)
+  LfCullSlab cull_resident;                    // the layout of the RESIDENT table (written by lfk_cull_prepass alone)
   uint64_t cull_hash_pending = 0;              // of the slab lf_cull_prepare built (the host's exchange is outstanding)
   bool cull_prepare_only = false;              // (lf_cull_prepare is inside lfk_march)
   bool cull_fresh = false;                     // lf_cull_commit just completed the table: the next launch takes it even in mode 2
@@ -518,10 +529,26 @@ inline float lf_march_lobe_thr(const LfLensDev& L) {
   return t;
 }
 
-// the flare layer calls the reference's own pow() (exact) or its cheaper equivalents (fast): DESIGN.md section 3
 inline LfDeal lf_deal_of(const lf_ctx* ctx) {
-  return LfDeal{ctx->row_period, ctx->row_phase, ctx->deal_by_block ? (ctx->W + (1 << kDealBlockLog2) - 1) >> kDealBlockLog2 : 0};
+  const LfSplit& s = ctx->split;
+  return LfDeal{s.n, s.rank, s.deal == LfSplit::kBlocks ? (ctx->W + (1 << kDealBlockLog2) - 1) >> kDealBlockLog2 : 0};
 }
+// The only writer of ctx->split: every setter validates its arguments, then installs the whole record.  A slab prepared for
+// the host's exchange, or a table it completed, belongs to the table share it was built for: a different share drops it.
+// (Whether the resident table is the one a launch needs is the pre-pass's hash to decide: lfk_cull_prepass.)
+inline void lf_install_split(lf_ctx* ctx, const LfSplit& s) {
+  const LfSplit& o = ctx->split;
+  if (s.table != o.table || s.table_rank != o.table_rank || s.table_n != o.table_n) {
+    ctx->cull_hash_pending = 0;
+    ctx->cull_fresh = false;
+  }
+  ctx->split = s;
+}
+// the cull table is not this context's alone: shared between ranks, or built only in part (the frame dealt by blocks)
+inline bool lf_cull_table_split(const lf_ctx* ctx) {
+  return ctx->split.table != LfSplit::kOwn || ctx->split.deal == LfSplit::kBlocks;
+}
+// the flare layer calls the reference's own pow() (exact) or its cheaper equivalents (fast): DESIGN.md section 3
 inline bool lf_flare_exact(const lf_ctx* ctx) {
   return ctx->flare_arithmetic == 1 || (ctx->flare_arithmetic == 0 && ctx->jitter_mode == 0);
 }

@@ -1183,7 +1183,7 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
   if (ctx->y1 <= ctx->y0) {
     // no rows of this context's own -- but a table shared through the communicator is completed by a COLLECTIVE:
     // every rank takes part, whatever it renders
-    if (ctx->cull_share_how == 1 && ctx->cull_share_n > 1 && lf_cull_applies(ctx, march_strata(spp)))
+    if (ctx->split.table == LfSplit::kComm && ctx->comm_nranks > 1 && lf_cull_applies(ctx, march_strata(spp)))
       return lfk_cull_prepass(ctx, march_strata(spp), spp);
     return LF_OK;
   }
@@ -1214,7 +1214,7 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
   } else {
     a.deal.bx = 0;
     const int t_lo = ctx->y0 / 8, t_hi = (ctx->y1 + 7) / 8;  // [t_lo, t_hi)
-    const int period = ctx->row_period, phase = ctx->row_phase;
+    const int period = a.deal.n, phase = a.deal.rank;
     int first = t_lo + ((phase - t_lo) % period + period) % period;
     if (first >= t_hi) return LF_OK;
     const int n_trows = (t_hi - 1 - first) / period + 1;
@@ -1350,7 +1350,7 @@ lf_status lfk_march(lf_ctx* ctx, int spp, uint64_t key) {
   ctx->cull_chunks = 1;
   // more paths than a mask has bits: the culled march in two launches over the halves of the selection (each with its own
   // table), where the cull applies at all and the table is this context's own
-  if (n <= kCullMaxPaths || n > 2 * kCullMaxPaths || ctx->cull_share_how != 0 || ctx->y1 <= ctx->y0 ||
+  if (n <= kCullMaxPaths || n > 2 * kCullMaxPaths || lf_cull_table_split(ctx) || ctx->y1 <= ctx->y0 ||
       lf_cull_reason_of(ctx, march_strata(spp)) != LF_CULL_APPLIED)
     return march_launch(ctx, spp, key, 0, 1, n);
   const LfPairsDev full = ctx->pairs;

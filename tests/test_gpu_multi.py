@@ -686,3 +686,84 @@ def test_block_deal_exchange_through_the_communicator(pkg, force_exchange, cull_
     lf.comm_wait()
     assert np.array_equal(lf.read_buffer(pkg.SAMPLE_BUFFER), want) and want.max() > 0
     lf.close()
+
+
+def _plain_1080p(pkg, lens, mask, spp):
+    """the single-context 1080p frame: sample and ghost buffers, counters, cull table"""
+    one = pkg.LensFlare(0)
+    one.set_frame(1920, 1080)
+    _setup(pkg, one, lens, mask)
+    one.set_march_culling(2)
+    one.reset_counters()
+    _frame(one, spp, 9)
+    assert one.cull_info()["culled"]
+    want = (one.read_buffer(pkg.SAMPLE_BUFFER), one.read_buffer(pkg.GHOST_BUFFER), one.counters(), one.cull_table())
+    one.close()
+    return want
+
+
+def test_set_frame_after_block_deal_renders_the_whole_frame(pkg, cull_forced):
+    """lf_set_frame deals the whole frame again, also after lf_set_block_deal: the next frame, its counters and its cull table
+    are a fresh context's (no block of the old deal left out of the table, none of the frame left unmarched)."""
+    lens = pkg.load_lens_file("dgauss11.lens")
+    mask = load_texels("pentbig500_14.png")
+    want_sample, want_ghost, want_cnt, want_tab = _plain_1080p(pkg, lens, mask, 16)
+    lf = pkg.LensFlare(0)
+    lf.set_frame(1920, 1080)
+    lf.set_block_deal(1, 4)
+    lf.set_frame(1920, 1080)
+    _setup(pkg, lf, lens, mask)
+    lf.set_march_culling(2)
+    lf.reset_counters()
+    _frame(lf, 16, 9)
+    assert lf.cull_info()["culled"]
+    assert np.array_equal(lf.read_buffer(pkg.GHOST_BUFFER), want_ghost) and want_ghost.max() > 0
+    assert np.array_equal(lf.read_buffer(pkg.SAMPLE_BUFFER), want_sample)
+    assert lf.counters() == want_cnt and np.array_equal(lf.cull_table(), want_tab)
+    lf.close()
+
+
+def test_block_deal_refuses_a_shared_table(pkg, cull_forced):
+    """A frame dealt by blocks shares no table: lf_set_cull_share(rank, n > 1) and lf_comm_share_cull(1) are refused with
+    LF_ERR_STATE (as lf_set_block_deal is under a shared table) and the next frame is still the dealt one; switching a
+    share OFF (lf_comm_share_cull(0), lf_set_cull_share(r, 1)) keeps the deal and its pixels."""
+    lens = pkg.load_lens_file("dgauss11.lens")
+    mask = load_texels("pentbig500_14.png")
+    n, rank = 3, 1
+    want_sample, want_ghost, _, want_tab = _plain_1080p(pkg, lens, mask, 16)
+    mine = _block_owner(1920, 1080, n) == rank
+    lf = pkg.LensFlare(0)
+    lf.set_frame(1920, 1080)
+    _setup(pkg, lf, lens, mask)
+    lf.set_march_culling(2)
+    comm = pkg.comm_available()
+    if comm:
+        lf.comm_init_rank(1, 0, pkg.comm_unique_id())    # (before the deal: it deals tile rows itself)
+    lf.set_block_deal(rank, n)
+    with pytest.raises(pkg.LensFlareError) as e:
+        lf.set_cull_share(rank, n)
+    assert e.value.status == 4     # LF_ERR_STATE
+    if comm:
+        with pytest.raises(pkg.LensFlareError) as e:
+            lf.comm_share_cull(True)
+        assert e.value.status == 4
+    _frame(lf, 16, 9)
+    ci = lf.cull_info()
+    assert ci["culled"] and ci["block_px"] == 64
+    got = lf.read_buffer(pkg.GHOST_BUFFER)
+    assert np.array_equal(got[mine], want_ghost[mine]) and want_ghost[mine].max() > 0
+    tab = lf.cull_table().reshape(-1, ci["cells"] + 1)
+    own_blocks = np.arange(tab.shape[0]) % n == rank
+    assert not tab[~own_blocks].any()                    # dealt: nobody else's rows were built
+    assert np.array_equal(tab[own_blocks], want_tab.reshape(-1, ci["cells"] + 1)[own_blocks])
+    sample = lf.read_buffer(pkg.SAMPLE_BUFFER)
+    assert np.array_equal(sample[mine], want_sample[mine])
+    lf.comm_share_cull(False)
+    lf.set_cull_share(0, 1)
+    _frame(lf, 16, 9)
+    assert lf.cull_info()["culled"]
+    assert np.array_equal(lf.read_buffer(pkg.GHOST_BUFFER)[mine], got[mine])
+    assert np.array_equal(lf.read_buffer(pkg.SAMPLE_BUFFER)[mine], sample[mine])
+    if comm:
+        lf.comm_destroy()
+    lf.close()
