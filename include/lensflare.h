@@ -405,6 +405,30 @@ lf_status lf_set_lens(lf_ctx* ctx, int n_surfaces, int stop_index, int n_lambda,
  * the stop).  Replaces the hard-coded table of pathtracer.cpp:541-556 as an INPUT, which is what
  * lets a host that cannot change the reference's header select a lens (LF_LENS_FILE). */
 lf_status lf_load_lens_file(lf_ctx* ctx, const char* path);
+/* Single-layer thin-film (anti-reflection) coatings on the interfaces of the geometric lens (no reference
+ * counterpart).  n_surfaces / n_lambda must be those of the installed lens.
+ *   lambda_nm[l]        vacuum wavelength of index column l of lf_set_lens, nm (> 0, finite)
+ *   thickness_nm[k]     physical film thickness on interface k, nm, in [0, 10000]; 0 = uncoated (the stop: 0)
+ *   index[l*n + k]      film index at wavelength l (ignored where thickness is 0), >= the smaller of the two
+ *                       indices beside interface k at that wavelength
+ * thickness_nm == NULL clears every coating.  A film changes only the Fresnel WEIGHT of the march's rays
+ * (reflection and transmission at that interface, both directions, every path and the lens camera's
+ * primary path), never where they go: the cull table, the counters and the lit pixel set stay those of the
+ * bare lens.  lf_set_lens clears the coatings (they belong to the prescription); lf_focus_lens keeps them.
+ * A lens file may carry them: `coating k thickness_nm m_1 .. m_L` (or one m for all wavelengths) after a
+ * `lambda_nm l_1 .. l_L` line (lf_load_lens_file).  Only the weighted re-march of a lit path pays for a film:
+ * the bench frame (c3) takes 52.2 ms with eight quarter-wave films against 43.8 ms bare (x 1.19,
+ * profiles/coating_cost.json); a lens without films runs the kernels it always ran. */
+lf_status lf_set_lens_coatings(lf_ctx* ctx, int n_surfaces, int n_lambda, const float* lambda_nm,
+                               const float* thickness_nm, const float* index);
+/* what lf_set_lens_coatings installed (any array may be NULL): zeros and n_coated = 0 for a bare lens */
+lf_status lf_get_lens_coatings(lf_ctx* ctx, int n_surfaces, int n_lambda, float* lambda_nm,
+                               float* thickness_nm, float* index, int* n_coated);
+/* host arithmetic, no device (like lf_paraxial_efl): the coated reflectance of ONE interface in the float32
+ * contract of the march -- out = {R_s, R_p, R = (R_s + R_p) / 2} for a ray arriving in n_in at cosine
+ * cos_in (in [0, 1]) of its angle of incidence; thickness 0 gives the bare interface, total reflection 1 */
+lf_status lf_coating_reflectance(float n_in, float n_film, float n_out, float thickness_nm,
+                                 float lambda_nm, float cos_in, float out[3]);
 /* what lf_set_lens / lf_load_lens_file installed (any pointer may be NULL); efl_mm = lf_paraxial_efl at
  * the middle wavelength (0 for an afocal prescription) */
 lf_status lf_get_lens_info(lf_ctx* ctx, int* n_surfaces, int* stop_index, int* n_lambda, float* sensor_width_mm,

@@ -39,7 +39,7 @@ ABI_SYMBOLS = [
     "lf_timing_enable", "lf_timing_reset", "lf_timing_get",
     "lf_clear_ghost_buffer", "lf_draw_ghost", "lf_rasterize_textured_triangle", "lf_fill_textured_pixel",
     "lf_shift_vertex", "lf_compute_phase", "lf_irradiance_falloff", "lf_scene_trace_ray", "lf_scene_shade",
-    "lf_load_lens_file", "lf_get_lens_info",
+    "lf_load_lens_file", "lf_get_lens_info", "lf_set_lens_coatings", "lf_get_lens_coatings", "lf_coating_reflectance",
     "lf_set_pupil_target", "lf_get_pupil_target", "lf_aim_at_exit_pupil", "lf_paraxial_exit_pupil", "lf_set_ghost_accumulate",
     "lf_set_lens_camera", "lf_get_lens_camera", "lf_set_lens_camera_aim", "lf_paraxial_entrance_pupil", "lf_focus_lens", "lf_focus_lens_from_pupil",
     "lf_get_scene_counters", "lf_reset_scene_counters", "lf_set_flare_arithmetic",
@@ -156,7 +156,7 @@ def load_lens_file(path):
     """Parse a .lens prescription (see data/dgauss11.lens) -> dict of float32 arrays."""
     if not os.path.isabs(path) and not os.path.exists(path):
         path = os.path.join(DATA, path)
-    rows, sensor_w, lambda_nm = [], 36.0, None
+    rows, sensor_w, lambda_nm, coats = [], 36.0, None, []
     for line in open(path):
         line = line.split("#")[0].strip()
         if not line:
@@ -167,6 +167,9 @@ def load_lens_file(path):
             continue
         if t[0] == "lambda_nm":      # the wavelengths of the index columns (spectral prescriptions)
             lambda_nm = [float(v) for v in t[1:]]
+            continue
+        if t[0] == "coating":        # coating k thickness_nm m_1 .. m_L | m  (lf_set_lens_coatings)
+            coats.append((int(t[1]), float(t[2]), [float(v) for v in t[3:]]))
             continue
         rows.append([float(v) for v in t])
     rows = np.array(rows, np.float64)
@@ -182,7 +185,35 @@ def load_lens_file(path):
         if len(lambda_nm) != ior.shape[0]:
             raise ValueError(f"{path}: lambda_nm lists {len(lambda_nm)} wavelengths for {ior.shape[0]} index columns")
         lens["lambda_nm"] = np.array(lambda_nm, np.float64)
+    if coats:
+        if lambda_nm is None:
+            raise ValueError(f"{path}: coating lines need a lambda_nm line (the wavelengths of the index columns)")
+        nl = ior.shape[0]
+        thick = np.zeros(n, np.float32)
+        index = np.zeros((nl, n), np.float32)
+        for k, d, m in coats:
+            if not 0 <= k < n or len(m) not in (1, nl) or thick[k] != 0:
+                raise ValueError(f"{path}: bad coating line for interface {k}")
+            thick[k] = d
+            index[:, k] = m if len(m) == nl else m[0]
+        lens["coatings"] = dict(lambda_nm=np.array(lambda_nm, np.float32), thickness_nm=thick, index=index)
     return lens
+
+
+def quarter_wave_thickness(m, lambda_nm):
+    """Physical thickness (nm) of a quarter-wave film of index m at wavelength lambda_nm: lambda / (4 m)."""
+    return float(lambda_nm) / (4.0 * float(m))
+
+
+def coating_reflectance(n_in, n_film, n_out, thickness_nm, lambda_nm, cos_in):
+    """(R_s, R_p, R) of one coated interface in the march's float32 arithmetic (lf_coating_reflectance, host only):
+    a ray arriving in n_in at incidence cosine cos_in; thickness 0 = the bare interface."""
+    out = (C.c_float * 3)()
+    st = load_library().lf_coating_reflectance(C.c_float(n_in), C.c_float(n_film), C.c_float(n_out),
+                                               C.c_float(thickness_nm), C.c_float(lambda_nm), C.c_float(cos_in), out)
+    if st != 0:
+        raise LensFlareError(st, "lf_coating_reflectance")
+    return float(out[0]), float(out[1]), float(out[2])
 
 
 # Fraunhofer lines of the three index columns of the shipped prescriptions (C, d, F)
@@ -595,6 +626,34 @@ class LensFlare:
         self._ck(self.lib.lf_set_lens(self.ctx, int(lens["n"]), int(lens["stop"]), int(i.shape[0]),
                                       _fp(r, C.c_float), _fp(t, C.c_float), _fp(i, C.c_float),
                                       _fp(h, C.c_float), C.c_float(lens["sensor_width_mm"])))
+        if "coatings" in lens:
+            c = lens["coatings"]
+            self.set_lens_coatings(c["lambda_nm"], c["thickness_nm"], c["index"])
+
+    def set_lens_coatings(self, lambda_nm, thickness_nm=None, index=None):
+        """Single-layer films on the installed lens: lambda_nm[l] (the index columns' wavelengths), thickness_nm[k]
+        (0 = bare), index[l, k] (n_lambda x n_surfaces, or one value per interface / one for all).
+        thickness_nm None clears every coating."""
+        if thickness_nm is None:
+            self._ck(self.lib.lf_set_lens_coatings(self.ctx, 0, 0, None, None, None))
+            return
+        lam = np.ascontiguousarray(lambda_nm, np.float32).ravel()
+        d = np.ascontiguousarray(thickness_nm, np.float32).ravel()
+        m = np.ascontiguousarray(np.broadcast_to(np.asarray(index, np.float32), (len(lam), len(d))), np.float32)
+        self._ck(self.lib.lf_set_lens_coatings(self.ctx, len(d), len(lam), _fp(lam, C.c_float), _fp(d, C.c_float),
+                                               _fp(m, C.c_float)))
+
+    def lens_coatings(self):
+        """dict(lambda_nm, thickness_nm, index (n_lambda x n), n_coated) of the installed lens."""
+        info = self.lens_info()
+        n, nl = info["n"], info["n_lambda"]
+        lam = np.zeros(nl, np.float32)
+        d = np.zeros(n, np.float32)
+        m = np.zeros((nl, n), np.float32)
+        nc = C.c_int()
+        self._ck(self.lib.lf_get_lens_coatings(self.ctx, n, nl, _fp(lam, C.c_float), _fp(d, C.c_float),
+                                               _fp(m, C.c_float), C.byref(nc)))
+        return dict(lambda_nm=lam, thickness_nm=d, index=m, n_coated=nc.value)
 
     def set_lambda_rgb(self, weights):
         w = np.ascontiguousarray(weights, np.float32)

@@ -9,6 +9,7 @@
 #include <cstring>
 
 #include "lf_internal.h"
+#include "lf_march_events.h"
 #include "../host/lf_collada.h"
 
 lf_status lf_fail(const lf_ctx* ctx, lf_status st, const std::string& msg) {
@@ -159,6 +160,18 @@ lf_status upload_paraxial(lf_ctx* ctx) {
 }
 
 }  // namespace
+
+// host: the float constants of coated_fraction (lf_march_events.h) for one (interface, direction, wavelength)
+void lf_coat_constants(float n, float m, float np, float thickness_nm, float lambda_nm, LfCoatK* c) {
+  const float m2 = m * m, n2 = n * n, np2 = np * np;
+  c->dm = m2 - n2;
+  c->ph = (2.0f * thickness_nm) / lambda_nm;
+  c->s01 = 1.0f / (n + m);
+  c->s12 = 1.0f / (m + np);
+  const float q1 = std::fmaf(m2, n, n2 * m), q2 = std::fmaf(np2, m, m2 * np);
+  c->p01a = m2 / q1; c->p01b = n2 / q1;
+  c->p12a = np2 / q2; c->p12b = m2 / q2;
+}
 
 extern "C" {
 
@@ -735,8 +748,10 @@ lf_status lf_set_lens(lf_ctx* ctx, int n_surfaces, int stop_index, int n_lambda,
         return lf_fail(ctx, LF_ERR_INVALID, "lens: index of refraction < 1 or not finite");
   }
   // a pupil target belongs to the prescription it was computed for (lf_aim_at_exit_pupil): a new lens
-  // starts from the default disc, the rear element's clear aperture
+  // starts from the default disc, the rear element's clear aperture; so do its coatings: a new lens is bare
   ctx->pupil_target_h = 0.0f; ctx->pupil_target_z = 0.0f;
+  ctx->coat = LfCoatings{};
+  ctx->lenscam_dirty = true;
   lf_derive_lens(ctx, n_surfaces, stop_index, n_lambda, radius, thickness, ior, semi_aperture,
                  sensor_width_mm);
   ctx->raw_n = n_surfaces; ctx->raw_stop = stop_index;
@@ -1339,13 +1354,114 @@ lf_status lf_irradiance_falloff(lf_ctx* ctx, int x, int y, double radius, double
   return lfk_irradiance_falloff(ctx, x, y, radius, rgb);
 }
 
+// ---------------------------------------------------------------- coatings ----------------------
+lf_status lf_set_lens_coatings(lf_ctx* ctx, int n_surfaces, int n_lambda, const float* lambda_nm,
+                               const float* thickness_nm, const float* index) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lens_coatings before lf_set_lens");
+  if (!thickness_nm) {   // every interface bare
+    ctx->coat = LfCoatings{};
+    ctx->events_dirty = true;
+    ctx->lenscam_dirty = true;
+    return LF_OK;
+  }
+  const LfLensDev& L = ctx->lens;
+  if (n_surfaces != ctx->raw_n || n_lambda != L.n_lambda || !lambda_nm || !index)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_coatings: sizes differ from the installed lens (or a NULL array)");
+  for (int l = 0; l < n_lambda; l++)
+    if (!std::isfinite(lambda_nm[l]) || !(lambda_nm[l] > 0.0f))
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_coatings: wavelengths must be finite and > 0 nm");
+  LfCoatings C;
+  for (int k = 0; k < n_surfaces; k++) {
+    const float d = thickness_nm[k];
+    if (!std::isfinite(d) || d < 0.0f || d > kCoatMaxThicknessNm)
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_coatings: a thickness must be finite and in [0, 10000] nm");
+    if (d == 0.0f) continue;
+    if (k == ctx->raw_stop) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_coatings: the stop cannot carry a film");
+    for (int l = 0; l < n_lambda; l++) {
+      const float m = index[(size_t)l * n_surfaces + k];
+      // m >= min(n, n') keeps the film's cosine real wherever the interface does not reflect totally
+      if (!std::isfinite(m) || !(m >= std::min(L.surf[k].n_before[l], L.surf[k].n_after[l])))
+        return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_coatings: a film index must be finite and >= the smaller index beside it");
+    }
+    C.n++;
+  }
+  for (int l = 0; l < n_lambda; l++) C.lambda_nm[l] = lambda_nm[l];
+  for (int k = 0; k < n_surfaces; k++) {
+    C.thickness_nm[k] = thickness_nm[k];
+    for (int l = 0; l < n_lambda; l++)
+      C.index[(size_t)l * n_surfaces + k] = thickness_nm[k] > 0.0f ? index[(size_t)l * n_surfaces + k] : 0.0f;
+  }
+  if (C.n == 0) C = LfCoatings{};
+  ctx->coat = C;
+  ctx->events_dirty = true;
+  ctx->lenscam_dirty = true;
+  return LF_OK;
+}
+
+lf_status lf_get_lens_coatings(lf_ctx* ctx, int n_surfaces, int n_lambda, float* lambda_nm, float* thickness_nm,
+                               float* index, int* n_coated) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_get_lens_coatings before lf_set_lens");
+  if (n_surfaces != ctx->raw_n || n_lambda != ctx->lens.n_lambda)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_get_lens_coatings: sizes differ from the installed lens");
+  const LfCoatings& C = ctx->coat;
+  if (lambda_nm) for (int l = 0; l < n_lambda; l++) lambda_nm[l] = C.lambda_nm[l];
+  if (thickness_nm) for (int k = 0; k < n_surfaces; k++) thickness_nm[k] = C.thickness_nm[k];
+  if (index) for (size_t i = 0; i < (size_t)n_lambda * n_surfaces; i++) index[i] = C.index[i];
+  if (n_coated) *n_coated = C.n;
+  return LF_OK;
+}
+
+lf_status lf_coating_reflectance(float n_in, float n_film, float n_out, float thickness_nm, float lambda_nm,
+                                 float cos_in, float out[3]) {
+  if (!out) return LF_ERR_INVALID;
+  if (!std::isfinite(n_in) || !std::isfinite(n_film) || !std::isfinite(n_out) || !std::isfinite(thickness_nm) ||
+      !std::isfinite(lambda_nm) || !std::isfinite(cos_in))
+    return LF_ERR_INVALID;
+  if (!(n_in >= 1.0f) || !(n_out >= 1.0f) || !(lambda_nm > 0.0f) || !(cos_in >= 0.0f) || !(cos_in <= 1.0f) ||
+      thickness_nm < 0.0f || thickness_nm > kCoatMaxThicknessNm)
+    return LF_ERR_INVALID;
+  if (thickness_nm > 0.0f && !(n_film >= std::min(n_in, n_out))) return LF_ERR_INVALID;
+  // the event's optical cosines: sq = n |cos t|, ct = n' cos t' = sqrt(sq^2 + n'^2 - n^2) (surface_event)
+  const float sq = n_in * cos_in;
+  const float n2 = n_in * n_in, np2 = n_out * n_out;
+  const float k2 = sq * sq + (np2 - n2);
+  if (k2 < 0.0f) { out[0] = out[1] = out[2] = 1.0f; return LF_OK; }   // total reflection
+  const float ct = std::sqrt(k2);
+  if (thickness_nm == 0.0f) {   // the bare fraction of surface_event<true>
+    const float fs = 1.0f / (n_in + n_out), q = std::fmaf(np2, n_in, n2 * n_out), fo = np2 / q, fi = n2 / q;
+    const float a = (sq - ct) * fs, b = (sq + ct) * fs;
+    const float pc = fi * ct;
+    const float A = std::fmaf(fo, sq, -pc), B = std::fmaf(fo, sq, pc);
+    const float u = a * B, v = A * b;
+    const float Rn = 0.5f * std::fmaf(u, u, v * v), bB = b * B;
+    out[0] = (a / b) * (a / b);
+    out[1] = (A / B) * (A / B);
+    out[2] = Rn / (bB * bB);
+    return LF_OK;
+  }
+  LfCoatK k;
+  lf_coat_constants(n_in, n_film, n_out, thickness_nm, lambda_nm, &k);
+  float Rn, Rd, Ns, Ds, Np, Dp;
+  lfm::coated_fraction(sq, ct, k, Rn, Rd, &Ns, &Ds, &Np, &Dp);
+  out[0] = Ns / Ds;
+  out[1] = Np / Dp;
+  out[2] = Rn / Rd;
+  return LF_OK;
+}
+
 // ---------------------------------------------------------------- lens file ---------------------
 lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
   if (!ctx || !path) return LF_ERR_INVALID;
   FILE* f = std::fopen(path, "r");
   if (!f) return lf_fail(ctx, LF_ERR_INVALID, std::string("lf_load_lens_file: cannot open ") + path);
   // rows: radius thickness n_1 ... n_L semi_aperture; '#' starts a comment; radius 0 with index 0 = the stop
-  std::vector<std::vector<double>> rows;
+  // optional: `lambda_nm l_1 .. l_L` (the wavelengths of the index columns) and
+  // `coating k thickness_nm m_1 .. m_L | m` (a film on interface k: lf_set_lens_coatings; needs lambda_nm)
+  std::vector<std::vector<double>> rows, coats;
+  std::vector<double> lambdas;
+  bool lambda_line = false, lambda_bad = false;
   double sensor_w = 36.0;
   char line[1024];
   bool bad = false;
@@ -1353,22 +1469,27 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (char* h = std::strchr(line, '#')) *h = 0;
     std::vector<double> v;
     char* p = line;
-    bool keyword = false, skip_line = false;
+    int keyword = 0;   // 1 sensor_width_mm, 2 lambda_nm, 3 coating
     while (*p) {
       while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') p++;
       if (!*p) break;
-      if (v.empty() && !keyword && std::strncmp(p, "sensor_width_mm", 15) == 0) { keyword = true; p += 15; continue; }
-      // (the wavelengths of the index columns: documentation for the host, the march only needs the indices)
-      if (v.empty() && !keyword && std::strncmp(p, "lambda_nm", 9) == 0) { skip_line = true; break; }
+      if (v.empty() && !keyword && std::strncmp(p, "sensor_width_mm", 15) == 0) { keyword = 1; p += 15; continue; }
+      if (v.empty() && !keyword && std::strncmp(p, "lambda_nm", 9) == 0) { keyword = 2; p += 9; continue; }
+      if (v.empty() && !keyword && std::strncmp(p, "coating", 7) == 0) { keyword = 3; p += 7; continue; }
       char* e = nullptr;
       const double d = std::strtod(p, &e);
-      if (e == p) { bad = true; break; }
+      if (e == p) {
+        // (the wavelengths are only read for a file with coatings: anything on the line is accepted otherwise)
+        if (keyword == 2) { lambda_bad = true; break; }
+        bad = true; break;
+      }
       v.push_back(d);
       p = e;
     }
     if (bad) break;
-    if (skip_line) continue;
-    if (keyword) { if (v.size() != 1) { bad = true; break; } sensor_w = v[0]; continue; }
+    if (keyword == 2) { lambda_line = true; lambdas = v; continue; }
+    if (keyword == 3) { coats.push_back(v); continue; }
+    if (keyword == 1) { if (v.size() != 1) { bad = true; break; } sensor_w = v[0]; continue; }
     if (!v.empty()) rows.push_back(v);
   }
   std::fclose(f);
@@ -1385,7 +1506,28 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (is_stop && stop < 0) stop = k;
     for (int l = 0; l < nl; l++) ior[l * n + k] = (is_stop && stop == k) ? 1.0f : (float)rows[k][2 + l];
   }
-  return lf_set_lens(ctx, n, stop, nl, radius, thick, ior, semi, (float)sensor_w);
+  float lam[LF_MAX_LAMBDA] = {}, cth[LF_MAX_SURFACES] = {}, cidx[LF_MAX_LAMBDA * LF_MAX_SURFACES] = {};
+  if (!coats.empty()) {
+    if (!lambda_line || lambda_bad || (int)lambdas.size() != nl)
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_load_lens_file: coating lines need a lambda_nm line with one wavelength per index column");
+    for (int l = 0; l < nl; l++) lam[l] = (float)lambdas[l];
+    for (const auto& c : coats) {
+      const int k = c.size() >= 3 ? (int)c[0] : -1;
+      if (k < 0 || k >= n || (double)k != c[0] || ((int)c.size() != 3 && (int)c.size() != nl + 2) || cth[k] != 0.0f)
+        return lf_fail(ctx, LF_ERR_INVALID, "lf_load_lens_file: a coating line is `coating k thickness_nm m_1 .. m_L` or `coating k thickness_nm m` (once per interface)");
+      cth[k] = (float)c[1];
+      for (int l = 0; l < nl; l++) cidx[l * n + k] = (float)c[(int)c.size() == 3 ? 2 : 2 + l];
+    }
+  }
+  lf_status st = lf_set_lens(ctx, n, stop, nl, radius, thick, ior, semi, (float)sensor_w);
+  if (st != LF_OK || coats.empty()) return st;
+  st = lf_set_lens_coatings(ctx, n, nl, lam, cth, cidx);
+  if (st != LF_OK) {   // the lens stays, bare
+    const std::string why = ctx->err;
+    (void)lf_set_lens_coatings(ctx, n, nl, nullptr, nullptr, nullptr);
+    return lf_fail(ctx, st, "lf_load_lens_file: " + why);
+  }
+  return LF_OK;
 }
 
 lf_status lf_get_lens_info(lf_ctx* ctx, int* n_surfaces, int* stop_index, int* n_lambda, float* sensor_width_mm,

@@ -782,7 +782,7 @@ struct PathTally {
 // the events of the path's own sequence, K wavelengths together, tallies, the lobe test, the weighted second march
 // (W1 = false) and the fixed-point add into the tile's LDS sums at pixel slot acc_slot.  Shared by the two culled
 // kernels below: lane = pixel (k_march_cull) and lane = one compacted (pixel, sample) item (k_march_items).
-template <int K, bool W1>
+template <int K, bool W1, bool COAT>
 __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                                                    const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
                                                    const LfWeightRow* __restrict__ wrec_table, const float* __restrict__ mask,
@@ -820,7 +820,7 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
       const LfProgRow wr = load_prec(recs, cur & 0xffffu);
       LfWeightRow ww;
       if (W1) ww = load_wrec(wrecs, cur & 0xffffu);
-      else { for (int j = 0; j < 3; j++) { ww.fs[j] = 1.0f; ww.fo[j] = 1.0f; ww.fi[j] = 1.0f; } }
+      else { for (int j = 0; j < 3; j++) { ww.fs[j] = 1.0f; ww.fo[j] = 1.0f; ww.fi[j] = 1.0f; } ww.coat = 0; }
       const unsigned kind = cur >> 16;
       lanemask okv[K], gv[K], died = 0ull;
       if (kind & LF_EV_STOP) {
@@ -845,7 +845,8 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
           for (int j = 0; j < K; j++) {
             if (K > 1 && __builtin_expect(alive[j] == 0ull, 0)) { okv[j] = 0ull; gv[j] = 0ull; continue; }
             okv[j] = surface_event<W1>(r[j], wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, wr.cn22[j], wr.rn2[j],
-                                       wr.delta[j], wr.h2, false, false, wr.sgn, gv[j], ww.fs[j], ww.fo[j], ww.fi[j]);
+                                       wr.delta[j], wr.h2, false, false, wr.sgn, gv[j], ww.fs[j], ww.fo[j], ww.fi[j],
+                                       CoatSel<COAT>{wrec_table, ww.coat, j});
             died |= alive[j] & ~okv[j];
           }
         } else if (kind == (unsigned)LF_EV_REFLECT) {      // a curved mirror: two rows of every pair
@@ -853,7 +854,8 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
           for (int j = 0; j < K; j++) {
             if (K > 1 && __builtin_expect(alive[j] == 0ull, 0)) { okv[j] = 0ull; gv[j] = 0ull; continue; }
             okv[j] = surface_event<W1>(r[j], wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, wr.cn22[j], wr.rn2[j],
-                                       wr.delta[j], wr.h2, true, false, wr.sgn, gv[j], ww.fs[j], ww.fo[j], ww.fi[j]);
+                                       wr.delta[j], wr.h2, true, false, wr.sgn, gv[j], ww.fs[j], ww.fo[j], ww.fi[j],
+                                       CoatSel<COAT>{wrec_table, ww.coat, j});
             died |= alive[j] & ~okv[j];
           }
         } else {
@@ -862,7 +864,8 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
             if (K > 1 && __builtin_expect(alive[j] == 0ull, 0)) { okv[j] = 0ull; gv[j] = 0ull; continue; }
             okv[j] = surface_event<W1>(r[j], wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, wr.cn22[j], wr.rn2[j],
                                        wr.delta[j], wr.h2, (kind & LF_EV_REFLECT) != 0, (kind & LF_EV_FLAT) != 0,
-                                       wr.sgn, gv[j], ww.fs[j], ww.fo[j], ww.fi[j]);
+                                       wr.sgn, gv[j], ww.fs[j], ww.fo[j], ww.fi[j],
+                                       CoatSel<COAT>{wrec_table, ww.coat, j});
             died |= alive[j] & ~okv[j];
           }
         }
@@ -906,26 +909,7 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
         { const float ns = lens->n_start[l]; rw.dx *= ns; rw.dy *= ns; rw.dz *= ns; }
         T.n_rm_lane += (unsigned long long)((unsigned)n_ev * (unsigned)__popcll(lj));
         T.n_rm_rows += (unsigned)n_ev;
-        const int* w = seq;
-        for (int left = n_ev; left > 0; --left, ++w) {
-          const unsigned se2 = (unsigned)*(const int __attribute__((address_space(4)))*)(w);
-          const LfProgRow wr = load_prec(recs, se2 & 0xffffu);
-          const LfWeightRow ww = load_wrec(wrecs, se2 & 0xffffu);
-          const unsigned wfl = se2 >> 16;
-          const float w_cn22 = j == 0 ? wr.cn22[0] : j == 1 ? wr.cn22[1] : wr.cn22[2];
-          const float w_rn2 = j == 0 ? wr.rn2[0] : j == 1 ? wr.rn2[1] : wr.rn2[2];
-          const float w_delta = j == 0 ? wr.delta[0] : j == 1 ? wr.delta[1] : wr.delta[2];
-          const float w_fs = j == 0 ? ww.fs[0] : j == 1 ? ww.fs[1] : ww.fs[2];
-          const float w_fo = j == 0 ? ww.fo[0] : j == 1 ? ww.fo[1] : ww.fo[2];
-          const float w_fi = j == 0 ? ww.fi[0] : j == 1 ? ww.fi[1] : ww.fi[2];
-          if (wfl & LF_EV_STOP) {
-            (void)stop_event<true>(rw, wr.dzv, wr.h2, inv_stop_h, mask, a.mw, a.mh);
-          } else {
-            lanemask geom_ok;
-            (void)surface_event<true>(rw, wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, w_cn22, w_rn2, w_delta, wr.h2,
-                                      (wfl & LF_EV_REFLECT) != 0, (wfl & LF_EV_FLAT) != 0, wr.sgn, geom_ok, w_fs, w_fo, w_fi);
-          }
-        }
+        weighted_remarch<COAT>(rw, seq, n_ev, j, recs, wrecs, wrec_table, mask, inv_stop_h, a.mw, a.mh);
       }
       const float qq = lobe_q(rw.dx, rw.dy, rw.dz, sx, sy, sz, sun_ss, inv_1mc);
       const float om = 1.0f - qq;
@@ -969,7 +953,7 @@ __device__ __forceinline__ lanemask surface_rows(Ray (&r)[K], const lanemask (&a
   return died;
 }
 
-template <int K>
+template <int K, bool COAT>
 __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                                                   const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
                                                   const LfWeightRow* __restrict__ wrec_table, const float* __restrict__ mask,
@@ -1093,26 +1077,7 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
             { const float ns = lens->n_start[l]; rw.dx *= ns; rw.dy *= ns; rw.dz *= ns; }
             T.n_rm_lane += (unsigned long long)((unsigned)n_ev * (unsigned)__popcll(lj));
             T.n_rm_rows += (unsigned)n_ev;
-            const int* w = seq;
-            for (int rem = n_ev; rem > 0; --rem, ++w) {
-              const unsigned se2 = (unsigned)*(const int __attribute__((address_space(4)))*)(w);
-              const LfProgRow wr = load_prec(recs, se2 & 0xffffu);
-              const LfWeightRow ww = load_wrec(wrecs, se2 & 0xffffu);
-              const unsigned wfl = se2 >> 16;
-              const float w_cn22 = j == 0 ? wr.cn22[0] : j == 1 ? wr.cn22[1] : wr.cn22[2];
-              const float w_rn2 = j == 0 ? wr.rn2[0] : j == 1 ? wr.rn2[1] : wr.rn2[2];
-              const float w_delta = j == 0 ? wr.delta[0] : j == 1 ? wr.delta[1] : wr.delta[2];
-              const float w_fs = j == 0 ? ww.fs[0] : j == 1 ? ww.fs[1] : ww.fs[2];
-              const float w_fo = j == 0 ? ww.fo[0] : j == 1 ? ww.fo[1] : ww.fo[2];
-              const float w_fi = j == 0 ? ww.fi[0] : j == 1 ? ww.fi[1] : ww.fi[2];
-              if (wfl & LF_EV_STOP) {
-                (void)stop_event<true>(rw, wr.dzv, wr.h2, inv_stop_h, mask, a.mw, a.mh);
-              } else {
-                lanemask geom_ok;
-                (void)surface_event<true>(rw, wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, w_cn22, w_rn2, w_delta, wr.h2,
-                                          (wfl & LF_EV_REFLECT) != 0, (wfl & LF_EV_FLAT) != 0, wr.sgn, geom_ok, w_fs, w_fo, w_fi);
-              }
-            }
+            weighted_remarch<COAT>(rw, seq, n_ev, j, recs, wrecs, wrec_table, mask, inv_stop_h, a.mw, a.mh);
             const float qq = lobe_q(rw.dx, rw.dy, rw.dz, sx, sy, sz, sun_ss, inv_1mc);
             const float om = 1.0f - qq;
             float contrib = __fdiv_rn(rw.wn, rw.wd) * (om * om);
@@ -1149,7 +1114,8 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
                               // a workgroup holds 2 waves per SIMD, so 5 runs as 4: 47 ms against 38 on the bench frame)
 #endif
 // MODE 0: every started path alone; 1 = SHARED (one table entry per wave and sample, the leg once: march_started_set)
-template <int K, bool W1, int MODE>
+// COAT: the lens has a film somewhere (lf_set_lens_coatings): the weighted march can evaluate one
+template <int K, bool W1, int MODE, bool COAT>
 __global__ __launch_bounds__(64 * kWgWaves, (K == 1 ? 8 : MODE == 1 ? LF_SHARED_WAVES : 6))
 void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                   const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
@@ -1261,7 +1227,7 @@ void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restri
         const unsigned long long todo = crow[entry];
         if (todo == 0ull) continue;
         const StartRay s0 = aim_at_pupil(X, Y, pa0, pb0, pupil_h, vz_u, geom_norm);
-        march_started_set<K>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, todo, active_mask, X, Y, s0, lane, s_acc, s_meta, T);
+        march_started_set<K, COAT>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, todo, active_mask, X, Y, s0, lane, s_acc, s_meta, T);
         continue;
       }
       unsigned long long mine, todo;
@@ -1280,7 +1246,7 @@ void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restri
         const int q = __builtin_ctzll(left_q);
         left_q &= left_q - 1ull;
         const lanemask start_mask = active_mask & __ballot(((mine >> q) & 1ull) != 0ull);   // (all active lanes when the wave shares a cell)
-        march_started_path<K, W1>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, q, start_mask, X, Y, s0, lane, lane, s_acc, T);
+        march_started_path<K, W1, COAT>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, q, start_mask, X, Y, s0, lane, lane, s_acc, T);
       }
     }
     __syncthreads();
@@ -1357,7 +1323,7 @@ constexpr int kItemCap = 16384;      // items of a chunk (2 bytes each)
 constexpr int kItemChunk = 256;      // samples per chunk at most (8 bits of an item; the pixel takes 6)
 constexpr int kItemCellCache = 64;   // chunks of up to this many samples keep each (sample, pixel)'s table cell between the two listing passes
 
-template <int K>
+template <int K, bool COAT>
 __global__ __launch_bounds__(64 * kWgWaves, 6)      // (42 KB of LDS lists: three workgroups per CU)
 void k_march_items(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                    const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
@@ -1512,7 +1478,7 @@ void k_march_items(const LfLensDev* __restrict__ lens, const LfPairsDev* __restr
       const float X = -(((float)x + jx) - half_w) * pitch;
       const float Y = -(((float)y + jy) - half_h) * pitch;
       const StartRay s0 = aim_at_pupil(X, Y, fmaf(2.0f, ua, -1.0f), fmaf(2.0f, ub, -1.0f), pupil_h, vz_u, geom_norm);
-      march_started_path<K, false>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, q, __ballot(have), X, Y, s0, lane, px, s_acc, T);
+      march_started_path<K, false, COAT>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, q, __ballot(have), X, Y, s0, lane, px, s_acc, T);
     }
     __syncthreads();
     c0 += chn;
@@ -1986,14 +1952,16 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
   if (ctx->cull_no_prefix) c.prefix_ok = 0;
   c.P = ctx->cull_P; c.m = ctx->cull_m; c.m_shift = ctx->cull_m == 4 ? 2 : ctx->cull_m == 2 ? 1 : 0;
   hipEvent_t ev = lf_timing_begin(ctx, LFK_MARCH);
-#define LF_LAUNCH_CULL1(KK, WW, SS)                                                                           \
-  hipLaunchKernelGGL((k_march_cull<KK, WW, SS>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
+#define LF_LAUNCH_CULL1(KK, WW, SS)  do { if (coated) LF_LAUNCH_CULL2(KK, WW, SS, true); else LF_LAUNCH_CULL2(KK, WW, SS, false); } while (0)
+#define LF_LAUNCH_CULL2(KK, WW, SS, CC)                                                                       \
+  hipLaunchKernelGGL((k_march_cull<KK, WW, SS, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                         \
                      (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),                                  \
                      (const LfWeightRow*)(ctx->prog_dev + ctx->prog_wrec_off), m.texels, a, c, ctx->ghost,   \
                      ctx->accum, ctx->counters_dev)
-#define LF_LAUNCH_ITEMS(KK)                                                                                  \
-  hipLaunchKernelGGL(k_march_items<KK>, dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
+#define LF_LAUNCH_ITEMS(KK)  do { if (coated) LF_LAUNCH_ITEMS2(KK, true); else LF_LAUNCH_ITEMS2(KK, false); } while (0)
+#define LF_LAUNCH_ITEMS2(KK, CC)                                                                             \
+  hipLaunchKernelGGL((k_march_items<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                         \
                      (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),                                  \
                      (const LfWeightRow*)(ctx->prog_dev + ctx->prog_wrec_off), m.texels, a, c, ctx->ghost,   \
@@ -2001,6 +1969,7 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
 #define LF_LAUNCH_CULL(KK) do { if (items) LF_LAUNCH_ITEMS(KK); else if (weights_first) LF_LAUNCH_CULL1(KK, true, 0); \
                                 else if (shared_leg) LF_LAUNCH_CULL1(KK, false, 1); else LF_LAUNCH_CULL1(KK, false, 0); } while (0)
   const bool weights_first = ctx->cull_weights_first;   // (lf_test_knob: the weight on every executed event)
+  const bool coated = ctx->coat.n > 0;                   // the variant that evaluates films (lf_set_lens_coatings)
   // every pixel its own pupil point (no sub-cells at all): the compacted march.  (2 x 2 sub-cells, where the lanes of a
   // wave still look their cells up one by one, stay with k_march_cull: 48 against 59 ms on the bench frame)
   bool items = ctx->march_sub_bits == 0;
@@ -2063,7 +2032,9 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
   }
 #undef LF_LAUNCH_CULL
 #undef LF_LAUNCH_CULL1
+#undef LF_LAUNCH_CULL2
 #undef LF_LAUNCH_ITEMS
+#undef LF_LAUNCH_ITEMS2
   lf_timing_end(ctx, LFK_MARCH, ev);
   LF_HIP(ctx, hipGetLastError());
 #ifdef LF_EXPERIMENTS

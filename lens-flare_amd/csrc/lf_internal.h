@@ -181,12 +181,31 @@ struct alignas(64) LfProgRow {
 };
 // what only the weight re-march needs of an (interface, direction): the scale factors of the Fresnel
 // fraction (surface_event<true>): fs = 1 / (n + n'), fo = n'^2 / q, fi = n^2 / q, q = n'^2 n + n^2 n'
+// coat: 0 = bare glass; else the byte offset, from the start of the weight records (group 0), of the
+// interface's film constants (3 x LfCoatK: wavelength j of the group at + 32 j; lf_set_lens_coatings)
 struct alignas(64) LfWeightRow {
   float fs[3], pad0;
   float fo[3], pad1;
   float fi[3], pad2;
-  float pad3[4];
+  int coat;
+  float pad3[3];
 };
+// One wavelength of a coated (interface, direction of travel): the constants of coated_fraction
+// (lf_march_events.h), float arithmetic of the prescription and the film (lf_coat_constants):
+// dm = m^2 - n^2, ph = 2 d / lambda, the s amplitudes' scales 1 / (n + m), 1 / (m + n') and the p
+// amplitudes' m^2 / q1, n^2 / q1 (q1 = m^2 n + n^2 m), n'^2 / q2, m^2 / q2 (q2 = n'^2 m + m^2 n').
+struct alignas(32) LfCoatK {
+  float dm, ph, s01, s12, p01a, p01b, p12a, p12b;
+};
+// the film on interface k of the prescription (host): thickness 0 = bare
+struct LfCoatings {
+  int n = 0;                                   // interfaces with a film (0: none)
+  float lambda_nm[LF_MAX_LAMBDA] = {};
+  float thickness_nm[LF_MAX_SURFACES] = {};
+  float index[LF_MAX_LAMBDA * LF_MAX_SURFACES] = {};   // [l * n_surfaces + k]
+};
+constexpr float kCoatMaxThicknessNm = 10000.0f;
+void lf_coat_constants(float n_in, float m, float n_out, float thickness_nm, float lambda_nm, LfCoatK* c);
 // The march does not walk the per-pair sequences one by one: every path of a (sample, wavelength)
 // starts with the same backward leg from the sensor, and all pairs (i, .) share the forward leg that
 // follows the reflection at i.  The per-wavelength *program* is that tree in depth-first order:
@@ -279,9 +298,10 @@ struct LfCullSlab { int rank = 0, n = 1, nb = 0; bool own_rows_only = false; };
 struct LfPrimaryRow {
   float dzv, curv, ch, c2, sc, h2;
   int kind;        // 0 = curved glass, LF_EV_STOP, LF_EV_FLAT
-  int pad;
+  int coated;      // the interface carries a film: coat[] holds its constants
   float cn22[LF_MAX_LAMBDA], rn2[LF_MAX_LAMBDA], delta[LF_MAX_LAMBDA];
   float fs[LF_MAX_LAMBDA], fo[LF_MAX_LAMBDA], fi[LF_MAX_LAMBDA];
+  LfCoatK coat[LF_MAX_LAMBDA];
 };
 struct LfPrimaryDev {
   int n, n_lambda;
@@ -411,6 +431,7 @@ struct lf_ctx {
   float raw_ior[LF_MAX_LAMBDA * LF_MAX_SURFACES] = {};
   float raw_semi_ap[LF_MAX_SURFACES] = {};
   float pupil_target_h = 0.0f, pupil_target_z = 0.0f;   // lf_set_pupil_target; h <= 0: the rear element
+  LfCoatings coat;                                        // lf_set_lens_coatings (cleared by lf_set_lens)
   bool ghost_accumulate = false;                          // lf_set_ghost_accumulate
   LfLensDev* lens_dev = nullptr;
   LfPairsDev pairs{};

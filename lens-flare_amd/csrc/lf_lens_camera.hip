@@ -50,6 +50,12 @@ lf_status lf_upload_primary_table(lf_ctx* ctx) {
       w.fo[l] = n_out2 / q;
       w.fi[l] = n_in2 / q;
     }
+    const LfCoatings& C = ctx->coat;
+    w.coated = C.n > 0 && C.thickness_nm[k] > 0.0f ? 1 : 0;
+    if (w.coated)
+      for (int l = 0; l < L.n_lambda; l++)
+        lf_coat_constants(s.n_after[l], C.index[(size_t)l * L.n_surf + k], s.n_before[l], C.thickness_nm[k], C.lambda_nm[l],
+                          &w.coat[l]);
   }
   if (!ctx->primary_dev) LF_HIP(ctx, hipMalloc((void**)&ctx->primary_dev, sizeof(LfPrimaryDev)));
   // (the context's stream is non-blocking: a kernel that still reads the previous table must finish first)

@@ -96,7 +96,7 @@ __device__ unsigned long long* g_lit_map[8];
 #ifndef LF_SKIP_DEAD_LAMBDA
 #define LF_SKIP_DEAD_LAMBDA 1   // experiments (profiles/r04_march_variants.txt): 0 = no per-wavelength liveness branch
 #endif
-template <int K>
+template <int K, bool COAT>   // COAT: the lens has a film somewhere (lf_set_lens_coatings)
 __global__ __launch_bounds__(64 * kWgWaves, (K == 1 ? 8 : 6))
 void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
              const int* __restrict__ seq_table, const LfProgHdr* __restrict__ hdr_table,
@@ -571,7 +571,7 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
                     lanemask geom_ok;
                     (void)surface_event<true>(rw, wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, w_cn22, w_rn2, w_delta, wr.h2,
                                               (wfl & LF_EV_REFLECT) != 0, (wfl & LF_EV_FLAT) != 0, wr.sgn, geom_ok,
-                                              w_fs, w_fo, w_fi);
+                                              w_fs, w_fo, w_fi, CoatSel<COAT>{wrec_table, ww.coat, j});
                   }
                 }
                 }
@@ -653,6 +653,7 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
 // the prescription (the same event arithmetic as the ghost march); out = {origin xyz on the front
 // element, unit direction xyz towards the scene, transmitted weight, alive flag} in lens space
 // (z along the axis, light travels +z, the scene is at z < 0).
+template <bool COAT>   // COAT: the lens has a film somewhere (lf_set_lens_coatings)
 __global__ __launch_bounds__(256) void k_lens_rays(const LfLensDev* __restrict__ lens,
                                                    const LfPrimaryDev* __restrict__ prim,
                                                    const float* __restrict__ mask, int mw, int mh,
@@ -666,7 +667,7 @@ __global__ __launch_bounds__(256) void k_lens_rays(const LfLensDev* __restrict__
   const float pa = active ? pupil_uv[2 * i] : 0.0f, pb = active ? pupil_uv[2 * i + 1] : 0.0f;
   const StartRay s0 = aim_at_pupil(X, Y, pa, pb, lens->pupil_h, lens->pupil_z - lens->z_sensor, lens->geom_norm);
   Ray r{X, Y, 0.0f, fmaf(X, X, Y * Y), s0.dx, s0.dy, s0.dz, s0.w0, 1.0f};
-  const bool alive = primary_path(prim, lambda, r, mask, mw, mh, lane);
+  const bool alive = primary_path<COAT>(prim, lambda, r, mask, mw, mh, lane);
   if (active) {
     float* o = out + 8 * (size_t)i;
     o[0] = r.px; o[1] = r.py; o[2] = prim->front_zv + r.hz; o[3] = r.dx; o[4] = r.dy; o[5] = r.dz;
@@ -1040,7 +1041,15 @@ static void pack_program(lf_ctx* ctx, const std::vector<LfEventRow>& rows, const
   *wrec_off = *rec_off + (size_t)n_groups * n_recs * sizeof(LfProgRow);
   static_assert(sizeof(LfWeightRow) == sizeof(LfProgRow), "a weight record sits at its record's offset");
   *seq_off = *wrec_off + (size_t)n_groups * n_recs * sizeof(LfWeightRow);
-  out.assign(*seq_off + ((size_t)P.total_events + 1) * sizeof(int), 0);
+  // the film constants of the coated records (lf_set_lens_coatings), after the sequences: 3 x LfCoatK per
+  // (group, coated record), wavelength j of the group at + 32 j
+  const LfCoatings& C = ctx->coat;
+  auto coated = [&](int k) { return C.n > 0 && C.thickness_nm[row_at(0, first_row[(size_t)k]).surf_dir & 0xff] > 0.0f; };
+  int n_coated = 0;
+  for (int k = 0; k < n_recs; k++) n_coated += coated(k) ? 1 : 0;
+  const size_t coat_off = (*seq_off + ((size_t)P.total_events + 1) * sizeof(int) + 63) & ~(size_t)63;
+  out.assign(n_coated ? coat_off + (size_t)n_groups * n_coated * 3 * sizeof(LfCoatK)
+                      : *seq_off + ((size_t)P.total_events + 1) * sizeof(int), 0);
   // the per-pair sequences (read by the weight re-march): one dword per event, record | kind << 16;
   // every (interface, direction) a pair crosses is in the program, so its record exists
   {
@@ -1057,6 +1066,8 @@ static void pack_program(lf_ctx* ctx, const std::vector<LfEventRow>& rows, const
   LfProgHdr* hdrs = reinterpret_cast<LfProgHdr*>(out.data());
   LfProgRow* recs = reinterpret_cast<LfProgRow*>(out.data() + *rec_off);
   LfWeightRow* wrecs = reinterpret_cast<LfWeightRow*>(out.data() + *wrec_off);
+  LfCoatK* coats = reinterpret_cast<LfCoatK*>(out.data() + coat_off);
+  int next_coat = 0;
   for (int g = 0; g < n_groups; g++) {
     for (int i = 0; i < P.prog_rows; i++) {
       LfProgHdr& h = hdrs[(size_t)g * (P.prog_rows + 1) + i];
@@ -1085,6 +1096,18 @@ static void pack_program(lf_ctx* ctx, const std::vector<LfEventRow>& rows, const
         w.fs[j] = 1.0f / (r.n_in + r.n_out);
         w.fo[j] = n_out2 / q;
         w.fi[j] = n_in2 / q;
+      }
+      w.coat = 0;
+      if (coated(k)) {
+        LfCoatK* ck = coats + (size_t)next_coat * 3;
+        w.coat = (int)(coat_off + (size_t)next_coat * 3 * sizeof(LfCoatK) - *wrec_off);
+        next_coat++;
+        const int surf = row_at(0, first_row[k]).surf_dir & 0xff;
+        for (int j = 0; j < 3; j++) {
+          const int l = std::min(g * K + (j < K ? j : K - 1), n_lambda - 1);
+          const LfEventRow& r = row_at(l, first_row[k]);
+          lf_coat_constants(r.n_in, C.index[(size_t)l * ctx->raw_n + surf], r.n_out, C.thickness_nm[surf], C.lambda_nm[l], &ck[j]);
+        }
       }
     }
   }
@@ -1314,8 +1337,9 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
     if (st != LF_OK) return st;
   } else {
   hipEvent_t ev = lf_timing_begin(ctx, LFK_MARCH);
-#define LF_LAUNCH_MARCH(KK)                                                                        \
-  hipLaunchKernelGGL(k_march<KK>, dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
+#define LF_LAUNCH_MARCH(KK)  do { if (ctx->coat.n > 0) LF_LAUNCH_MARCH2(KK, true); else LF_LAUNCH_MARCH2(KK, false); } while (0)
+#define LF_LAUNCH_MARCH2(KK, CC)                                                                   \
+  hipLaunchKernelGGL((k_march<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                \
                      (const LfProgHdr*)ctx->prog_dev,                                               \
                      (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),                         \
@@ -1327,6 +1351,7 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
     default: LF_LAUNCH_MARCH(3); break;
   }
 #undef LF_LAUNCH_MARCH
+#undef LF_LAUNCH_MARCH2
   lf_timing_end(ctx, LFK_MARCH, ev);
   LF_HIP(ctx, hipGetLastError());
   }
@@ -1346,6 +1371,10 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
 }
 
 lf_status lfk_march(lf_ctx* ctx, int spp, uint64_t key) {
+#ifdef LF_MARCH_ALL_WEIGHTS
+  if (ctx->coat.n > 0)
+    return lf_fail(ctx, LF_ERR_INVALID, "LF_MARCH_ALL_WEIGHTS (timing ablation): a coated lens is not supported");
+#endif
   const int n = ctx->pairs.n;
   ctx->cull_chunks = 1;
   // more paths than a mask has bits: the culled march in two launches over the halves of the selection (each with its own
@@ -1400,8 +1429,12 @@ lf_status lfk_lens_rays(lf_ctx* ctx, int lambda, int n, const float* d_xy, const
                              ctx->stream));
   lf_status st = lf_upload_primary_table(ctx);
   if (st != LF_OK) return st;
-  hipLaunchKernelGGL(k_lens_rays, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                     ctx->lens_dev, ctx->primary_dev, m.texels, m.w, m.h, lambda, n, d_xy, d_uv, d_out);
+  if (ctx->coat.n > 0)
+    hipLaunchKernelGGL(k_lens_rays<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       ctx->lens_dev, ctx->primary_dev, m.texels, m.w, m.h, lambda, n, d_xy, d_uv, d_out);
+  else
+    hipLaunchKernelGGL(k_lens_rays<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
+                       ctx->lens_dev, ctx->primary_dev, m.texels, m.w, m.h, lambda, n, d_xy, d_uv, d_out);
   LF_HIP(ctx, hipGetLastError());
   return LF_OK;
 }

@@ -102,7 +102,8 @@ __device__ __forceinline__ LfWeightRow load_wrec(const LfWeightRow* __restrict__
     r.fs[j] = __int_as_float(v[j]); r.fo[j] = __int_as_float(v[4 + j]); r.fi[j] = __int_as_float(v[8 + j]);
   }
   r.pad0 = r.pad1 = r.pad2 = 0.0f;
-  r.pad3[0] = r.pad3[1] = r.pad3[2] = r.pad3[3] = 0.0f;
+  r.coat = v[12];
+  r.pad3[0] = r.pad3[1] = r.pad3[2] = 0.0f;
   return r;
 }
 __device__ __forceinline__ LfProgHdr load_phdr(const LfProgHdr* __restrict__ base, unsigned off) {
@@ -113,5 +114,36 @@ __device__ __forceinline__ LfProgHdr load_phdr(const LfProgHdr* __restrict__ bas
   return h;
 }
 
+// The weighted march of ONE path for wavelength j of group g (recs / wrecs: the group's records; wrec_table: group
+// 0's, where the film offsets count from) along its own sequence (n_ev dwords at w): the same arithmetic on the ray as
+// the geometry-only march, plus the Fresnel / aperture weight -- and, COAT (the kernels launched for a lens with a
+// film), a coated row's film.  The culled kernels' re-march of a lit path (k_march's path tree keeps the same loop
+// inline: folded into this function, its K = 2 instantiation spilled 13 SGPRs more).
+template <bool COAT>
+__device__ __forceinline__ void weighted_remarch(Ray& rw, const int* __restrict__ w, int n_ev, int j, const LfProgRow* __restrict__ recs,
+                                                 const LfWeightRow* __restrict__ wrecs,
+                                                 const LfWeightRow* __restrict__ wrec_table, const float* __restrict__ mask,
+                                                 float inv_stop_h, int mw, int mh) {
+  for (int left = n_ev; left > 0; --left, ++w) {
+    const unsigned se = (unsigned)*(const int __attribute__((address_space(4)))*)(w);
+    const LfProgRow wr = load_prec(recs, se & 0xffffu);
+    const LfWeightRow ww = load_wrec(wrecs, se & 0xffffu);
+    const unsigned wfl = se >> 16;
+    const float w_cn22 = j == 0 ? wr.cn22[0] : j == 1 ? wr.cn22[1] : wr.cn22[2];
+    const float w_rn2 = j == 0 ? wr.rn2[0] : j == 1 ? wr.rn2[1] : wr.rn2[2];
+    const float w_delta = j == 0 ? wr.delta[0] : j == 1 ? wr.delta[1] : wr.delta[2];
+    const float w_fs = j == 0 ? ww.fs[0] : j == 1 ? ww.fs[1] : ww.fs[2];
+    const float w_fo = j == 0 ? ww.fo[0] : j == 1 ? ww.fo[1] : ww.fo[2];
+    const float w_fi = j == 0 ? ww.fi[0] : j == 1 ? ww.fi[1] : ww.fi[2];
+    if (wfl & LF_EV_STOP) {
+      (void)stop_event<true>(rw, wr.dzv, wr.h2, inv_stop_h, mask, mw, mh);
+    } else {
+      lanemask geom_ok;
+      (void)surface_event<true>(rw, wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, w_cn22, w_rn2, w_delta, wr.h2,
+                                (wfl & LF_EV_REFLECT) != 0, (wfl & LF_EV_FLAT) != 0, wr.sgn, geom_ok, w_fs, w_fo, w_fi,
+                                CoatSel<COAT>{wrec_table, ww.coat, j});
+    }
+  }
+}
 
 }  // namespace lfm

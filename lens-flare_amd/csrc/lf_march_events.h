@@ -5,6 +5,8 @@
 // Device code only; nothing here is part of the ABI.
 #pragma once
 
+#include <type_traits>
+
 #include "lf_internal.h"
 
 namespace lfm {
@@ -43,6 +45,60 @@ __device__ __forceinline__ float lf_sqrt(float x) { return __builtin_amdgcn_sqrt
 __device__ __forceinline__ float lf_rcp(float x) { return __builtin_amdgcn_rcpf(x); }
 
 __device__ __forceinline__ float u01(unsigned r) { return (float)(r >> 8) * 5.9604644775390625e-8f; }
+
+// ---- a coated interface ("coatings") -----------------------------------------
+// cos(2 pi x) with a fixed polynomial, never v_cos_f32 (whose argument reduction is the hardware's): the exact
+// reduction y = x - rint(x), |y| folded into [0, 1/4] with a sign (1/2 - |y| is exact there), then an even
+// polynomial in b^2 (max error 1.1e-7 on [0, 1/4] in float).  Host and device: lf_coating_reflectance runs it too.
+__host__ __device__ inline float lf_cos2pi(float x) {
+  const float a = fabsf(x - rintf(x));
+  const bool far = a > 0.25f;
+  const float b = far ? 0.5f - a : a;
+  const float z = b * b;
+  const float c = fmaf(z, fmaf(z, fmaf(z, fmaf(z, fmaf(z, -24.9823456f, 60.1440353f), -85.4535751f), 64.9393463f),
+                               -19.7392082f), 1.0f);
+  return far ? -c : c;
+}
+__host__ __device__ inline float lf_coat_sqrt(float x) {
+#ifdef __HIP_DEVICE_COMPILE__
+  return __builtin_amdgcn_sqrtf(x);
+#else
+  return sqrtf(x);
+#endif
+}
+// The unpolarised reflectance of a single film (index m, thickness d) between the media n and n', as ONE fraction
+// Rn / Rd, from the optical cosines of the event: sq = n |cos t| (incidence), ct = n' cos t' (exit) and the film's
+// cm = sqrt(sq^2 + dm).  Per polarisation the Airy sum r = (r01 + r12 e^{i delta}) / (1 + r01 r12 e^{i delta}) with
+// r01 = a / b, r12 = e / f, C = cos delta = cos 2 pi (ph cm):  |r|^2 = N / D,
+//   N = (a f)^2 + (e b)^2 + 2 (a b)(e f) C,   D = (b f)^2 + (a e)^2 + 2 (a b)(e f) C,
+// amplitudes scaled by the row constants so that b = f = 1 at normal incidence (as fs / fo / fi scale the bare
+// fraction); then Rn = Ns Dp + Np Ds, Rd = 2 Ds Dp.  Nothing is divided.
+__host__ __device__ inline void coated_fraction(float sq, float ct, const LfCoatK& k, float& Rn, float& Rd,
+                                                float* Ns_ = nullptr, float* Ds_ = nullptr, float* Np_ = nullptr,
+                                                float* Dp_ = nullptr) {
+  const float cm = lf_coat_sqrt(fmaxf(fmaf(sq, sq, k.dm), 0.0f));
+  const float C = lf_cos2pi(k.ph * cm);
+  float N[2], D[2];
+#pragma unroll
+  for (int p = 0; p < 2; p++) {
+    float a, b, e, f;
+    if (p == 0) {   // s
+      a = (sq - cm) * k.s01; b = (sq + cm) * k.s01;
+      e = (cm - ct) * k.s12; f = (cm + ct) * k.s12;
+    } else {        // p
+      const float u = k.p01b * cm, v = k.p12b * ct;
+      a = fmaf(k.p01a, sq, -u); b = fmaf(k.p01a, sq, u);
+      e = fmaf(k.p12a, cm, -v); f = fmaf(k.p12a, cm, v);
+    }
+    const float af = a * f, eb = e * b, bf = b * f, ae = a * e;
+    const float x = 2.0f * ((a * b) * (e * f)) * C;
+    N[p] = fmaf(af, af, fmaf(eb, eb, x));
+    D[p] = fmaf(bf, bf, fmaf(ae, ae, x));
+  }
+  Rn = fmaf(N[0], D[1], N[1] * D[0]);
+  Rd = 2.0f * (D[0] * D[1]);
+  if (Ns_) { *Ns_ = N[0]; *Ds_ = D[0]; *Np_ = N[1]; *Dp_ = D[1]; }
+}
 
 // The transmitted weight is carried as a fraction wn / wd: every Fresnel factor is a ratio of
 // two cheap products, so the march multiplies numerators and denominators separately and divides
@@ -85,12 +141,23 @@ typedef unsigned long long lanemask;
 // reflection -- and K' = K + sgn (n' cos t' - n cos t) N: no multiplication of K by an index ratio.
 // Per event that is 27 vector instructions where the unit-direction form of rounds 1-2 had 31.
 // cn22 = 2 c n^2, rn2 = R / n^2, delta = n'^2 - n^2, sc = sgn c come with the row.
-// W = true additionally takes the Fresnel scale factors fs, fo, fi of the row (LfWeightRow).
-template <bool W>
+// W = true additionally takes the Fresnel scale factors fs, fo, fi of the row (LfWeightRow) and where the
+// row's film constants are, if it has any (CT: NoCoat, CoatRec, CoatPrimary below).  A coated row takes
+// coated_fraction instead of the bare fraction behind a wave-uniform branch; a bare row runs the bare
+// fraction as it always has.  NoCoat compiles to the bare event alone: the kernels are instantiated twice,
+// and only a lens with a film launches the variant that can evaluate one (its temporaries, inlined in the
+// re-march, would raise the register pressure of the shared-leg kernel for every frame: DESIGN.md section 4).
+struct NoCoat {
+  NoCoat() = default;
+  __device__ __forceinline__ NoCoat(const void*, int, int) {}
+  __device__ __forceinline__ bool on() const { return false; }
+  __device__ __forceinline__ LfCoatK get() const { return LfCoatK{}; }
+};
+template <bool W, class CT = NoCoat>
 __device__ __forceinline__ lanemask surface_event(Ray& r, float dzv, float c, float ch, float c2, float sc,
                                                   float cn22, float rn2, float delta, float h2, bool reflect,
                                                   bool flat, float sgn, lanemask& geom_ok, float fs = 1.0f,
-                                                  float fo = 1.0f, float fi = 1.0f) {
+                                                  float fo = 1.0f, float fi = 1.0f, const CT& coat = CT()) {
   const float oz = r.hz + dzv;
   const float od = fmaf(r.px, r.dx, fmaf(r.py, r.dy, oz * r.dz));
   const float oo = fmaf(oz, oz, r.r2);
@@ -114,7 +181,11 @@ __device__ __forceinline__ lanemask surface_event(Ray& r, float dzv, float c, fl
     no_tir = k2 >= 0.0f;
     // (a totally reflected ray only survives a mirror event, and only W = true reads ct there)
     ct = lf_sqrt(reflect ? fmaxf(k2, 0.0f) : k2);
-    if (W) {
+    if (W && coat.on()) {   // wave-uniform: a film on this interface
+      coated_fraction(sq, ct, coat.get(), Rn, D);
+      // a refraction transmits Rd - Rn: clamped at 0, a rounding-negative factor must not reach the unsigned sums
+      if (!reflect) Rn = fminf(Rn, D);
+    } else if (W) {
       // unpolarised Fresnel straight from the optical cosines sq = n cos t, ct = n' cos t':
       //   rs = (sq - ct) / (sq + ct),   rp = (n'^2 sq - n^2 ct) / (n'^2 sq + n^2 ct),   R = (rs^2 + rp^2) / 2
       // as ONE fraction R = Rn / D, Rn = ((a B)^2 + (A b)^2) / 2, D = (b B)^2, with the numerators and
@@ -261,11 +332,36 @@ __device__ __forceinline__ StartRay sample_start(const SampleSpec& a, int x, int
   return sample_start_in(a, x, y, s, cx, cy, sxi, syi);
 }
 
+// the film constants of a row of the weight re-march: wavelength j of record `off` (bytes from the weight
+// records' start; 0 = bare glass; the offset is wave-uniform, read with load_wrec's scalar load)
+typedef int lf_i8 __attribute__((ext_vector_type(8)));
+struct CoatRec {
+  const void* base;
+  int off, j;
+  __device__ __forceinline__ bool on() const { return off != 0; }
+  __device__ __forceinline__ LfCoatK get() const {
+    typedef const char __attribute__((address_space(4))) * cptr;
+    const lf_i8 v = *(const lf_i8 __attribute__((address_space(4)))*)((cptr)(base) + (off + 32 * j));
+    return LfCoatK{__int_as_float(v[0]), __int_as_float(v[1]), __int_as_float(v[2]), __int_as_float(v[3]),
+                   __int_as_float(v[4]), __int_as_float(v[5]), __int_as_float(v[6]), __int_as_float(v[7])};
+  }
+};
+// what a kernel instantiated with / without film support (COAT) passes to surface_event
+template <bool COAT> using CoatSel = typename std::conditional<COAT, CoatRec, NoCoat>::type;
+// ... and of a row of the primary table (the wavelength may differ between lanes: a plain load)
+struct CoatPrimary {
+  const LfPrimaryRow* row;
+  int lambda;
+  __device__ __forceinline__ bool on() const { return row->coated != 0; }
+  __device__ __forceinline__ LfCoatK get() const { return row->coat[lambda]; }
+};
+
 // ---- the primary path N-1 .. 0 with its weight (LensCamera::generate_ray) ---------------------------
 // One lane = one ray; the interface table (LfPrimaryDev, built by the host with the float arithmetic
 // of pack_program) is wave-uniform and arrives through the scalar cache.  Returns whether this
 // lane's ray left the front element; r then holds the exit state (hz relative to interface 0's vertex,
 // K = the unit direction in air) and wn / wd the transmitted weight.
+template <bool COAT>
 __device__ __forceinline__ bool primary_path(const LfPrimaryDev* __restrict__ P, int lambda, Ray& r,
                                              const float* __restrict__ mask, int mw, int mh, int lane) {
   { const float ns = P->n_start[lambda]; r.dx *= ns; r.dy *= ns; r.dz *= ns; }   // K = n d
@@ -277,9 +373,14 @@ __device__ __forceinline__ bool primary_path(const LfPrimaryDev* __restrict__ P,
     if (w.kind & LF_EV_STOP) {
       ok = stop_event<true>(r, w.dzv, w.h2, P->inv_stop_h, mask, mw, mh);
     } else {
-      ok = surface_event<true>(r, w.dzv, w.curv, w.ch, w.c2, w.sc, w.cn22[lambda], w.rn2[lambda],
-                               w.delta[lambda], w.h2, false, (w.kind & LF_EV_FLAT) != 0, -1.0f, geom_ok,
-                               w.fs[lambda], w.fo[lambda], w.fi[lambda]);
+      if (COAT)
+        ok = surface_event<true>(r, w.dzv, w.curv, w.ch, w.c2, w.sc, w.cn22[lambda], w.rn2[lambda],
+                                 w.delta[lambda], w.h2, false, (w.kind & LF_EV_FLAT) != 0, -1.0f, geom_ok,
+                                 w.fs[lambda], w.fo[lambda], w.fi[lambda], CoatPrimary{&w, lambda});
+      else
+        ok = surface_event<true>(r, w.dzv, w.curv, w.ch, w.c2, w.sc, w.cn22[lambda], w.rn2[lambda],
+                                 w.delta[lambda], w.h2, false, (w.kind & LF_EV_FLAT) != 0, -1.0f, geom_ok,
+                                 w.fs[lambda], w.fo[lambda], w.fi[lambda]);
     }
     alive = alive && ((ok >> lane) & 1ull) != 0ull;
     if (__ballot(alive) == 0ull) break;   // every lane of the wave is blocked (a closed part of the pupil): nothing left to march

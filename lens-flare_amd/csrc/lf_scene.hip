@@ -478,7 +478,7 @@ __device__ __forceinline__ void scene_pixel(const LfSceneDev& sc, const LfEnvDev
       for (int li = 0; li < n_rays; li++) {
         const int l = lc.mode == 2 ? li : lc.lambda_ref;
         lfm::Ray r{st.X, st.Y, 0.0f, fmaf(st.X, st.X, st.Y * st.Y), st.dx, st.dy, st.dz, st.w0, 1.0f};
-        const bool left = lfm::primary_path(prim, l, r, mask, lc.mw, lc.mh, lane);
+        const bool left = lfm::primary_path<true>(prim, l, r, mask, lc.mw, lc.mh, lane);
         lens_started++;
         if (!left) continue;
         lens_left++;
@@ -740,7 +740,7 @@ __global__ __launch_bounds__(256, LF_SCENE_LENS_WAVES) void k_scene_lens(LfScene
       bool left = false;
       lfm::Ray r{st.X, st.Y, 0.0f, fmaf(st.X, st.X, st.Y * st.Y), st.dx, st.dy, st.dz, st.w0, 1.0f};
       if (active) {
-        left = lfm::primary_path(prim, l, r, mask, lc.mw, lc.mh, lane);
+        left = lfm::primary_path<true>(prim, l, r, mask, lc.mw, lc.mh, lane);
         lens_started++;
         if (left) lens_left++;
       }
