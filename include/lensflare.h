@@ -106,6 +106,33 @@ lf_status lf_set_params(lf_ctx* ctx, int ns_aa, double flare_radius, double flar
 lf_status lf_set_aperture(lf_ctx* ctx, lf_aperture_slot slot, const float* texels, int width,
                           int height);
 lf_status lf_get_aperture_stats(lf_ctx* ctx, lf_aperture_slot slot, lf_aperture_stats* out);
+/* How the geometric march and the lens camera read the stop mask (the LF_APERTURE_STARBURST slot; no reference
+ * counterpart).  LF_MASK_NEAREST, the default: the texel the ray hits, alive iff it is > 0 -- every texel a hard
+ * edge in every ghost.  LF_MASK_BILINEAR: the float32 contract below.  With the stop hit (hx, hy) and the stop's
+ * semi-aperture stop_h,
+ *   fu = fmaf(hx, 1 / stop_h, 1) * (0.5f * w),  fv likewise with h      (texel i has its centre at i + 0.5)
+ *   gx = fu - 0.5f,  i0 = floor(gx),  fx = gx - i0                      (and gy, j0, fy)
+ *   t00 t10 t01 t11 = max(texel, 0) at (i0, j0) (i0 + 1, j0) (i0, j0 + 1) (i0 + 1, j0 + 1), indices clamped to the texture
+ *   a0 = fmaf(fx, t10 - t00, t00),  a1 = fmaf(fx, t11 - t01, t01),  value = fmaf(fy, a1 - a0, a0)
+ *   the ray is ALIVE iff max(t00, t10, t01, t11) > 0 -- any of the four texels open, not value > 0: a ray with
+ *   fx == 0 beside an open texel is alive with weight 0.
+ * The lit set therefore grows by half a texel around the open region (it contains the nearest filter's); the cull
+ * pre-pass, the audit and lf_aim_at_exit_pupil's open radius follow it.  A setting of the context: it survives
+ * lf_set_aperture, lf_set_lens and lf_set_frame.  It does NOT affect the starburst DFT, the LF_APERTURE_GHOST slot
+ * or lf_get_aperture_stats, which keep reading the texels as they are.  The CPU oracles (oracle/) do not follow
+ * filtered frames, as they do not follow coated ones.  Only the weighted re-march of a lit path and the lens
+ * camera's primary path pay for the four loads: the bench frame (c3) takes 44.6 ms under LF_MASK_BILINEAR against
+ * 43.6 ms (x 1.023, profiles/mask_filter_cost.json); a context under LF_MASK_NEAREST runs the kernels it always ran.
+ * Other values of filter: LF_ERR_INVALID. */
+typedef enum { LF_MASK_NEAREST = 0, LF_MASK_BILINEAR = 1 } lf_mask_filter;
+lf_status lf_set_mask_filter(lf_ctx* ctx, int filter);
+lf_status lf_get_mask_filter(lf_ctx* ctx, int* filter);
+/* host arithmetic, no device (like lf_coating_reflectance): the float32 contract of the stop-mask lookup.
+ * texels = w x h floats, row-major; u, v = stop-plane coordinates hx / stop_h, hy / stop_h (finite).  value = the
+ * transmission the march multiplies into the weight, open = 1 iff the ray survives the mask (LF_MASK_NEAREST:
+ * value = the texel hit, open = value > 0; LF_MASK_BILINEAR: as above).  Either output may be NULL. */
+lf_status lf_mask_lookup(const float* texels, int w, int h, int filter, float u, float v,
+                         float* value, int* open);
 
 /* replaces the lens-table globals of pathtracer.cpp:541-556 (Ts, red/green/blue_refr,
  * curvatures) and the constants of trace_ray_auto_* (:619-633): n interfaces, ior[3][n] row-major.

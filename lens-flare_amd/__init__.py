@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "lf_clear_ghost_buffer", "lf_draw_ghost", "lf_rasterize_textured_triangle", "lf_fill_textured_pixel",
     "lf_shift_vertex", "lf_compute_phase", "lf_irradiance_falloff", "lf_scene_trace_ray", "lf_scene_shade",
     "lf_load_lens_file", "lf_get_lens_info", "lf_set_lens_coatings", "lf_get_lens_coatings", "lf_coating_reflectance",
+    "lf_set_mask_filter", "lf_get_mask_filter", "lf_mask_lookup",
     "lf_set_pupil_target", "lf_get_pupil_target", "lf_aim_at_exit_pupil", "lf_paraxial_exit_pupil", "lf_set_ghost_accumulate",
     "lf_set_lens_camera", "lf_get_lens_camera", "lf_set_lens_camera_aim", "lf_paraxial_entrance_pupil", "lf_focus_lens", "lf_focus_lens_from_pupil",
     "lf_get_scene_counters", "lf_reset_scene_counters", "lf_set_flare_arithmetic",
@@ -214,6 +215,24 @@ def coating_reflectance(n_in, n_film, n_out, thickness_nm, lambda_nm, cos_in):
     if st != 0:
         raise LensFlareError(st, "lf_coating_reflectance")
     return float(out[0]), float(out[1]), float(out[2])
+
+
+# how the march and the lens camera read the stop mask (lf_set_mask_filter)
+MASK_NEAREST, MASK_BILINEAR = 0, 1
+
+
+def mask_lookup(texels, u, v, filter=MASK_BILINEAR):
+    """(value, open) of the stop-mask lookup in the march's float32 arithmetic (lf_mask_lookup, host only) at the
+    stop-plane point (u, v) = (hx, hy) / stop_h: the transmission multiplied into the weight, and whether the ray
+    survives the mask."""
+    t = np.ascontiguousarray(texels, np.float32)
+    h, w = t.shape
+    value, alive = C.c_float(), C.c_int()
+    st = load_library().lf_mask_lookup(_fp(t, C.c_float), w, h, int(filter), C.c_float(u), C.c_float(v),
+                                       C.byref(value), C.byref(alive))
+    if st != 0:
+        raise LensFlareError(st, "lf_mask_lookup")
+    return float(value.value), int(alive.value)
 
 
 # Fraunhofer lines of the three index columns of the shipped prescriptions (C, d, F)
@@ -444,6 +463,15 @@ class LensFlare:
         texels = np.ascontiguousarray(texels, np.float32)
         h, w = texels.shape
         self._ck(self.lib.lf_set_aperture(self.ctx, int(slot), _fp(texels, C.c_float), w, h))
+
+    def set_mask_filter(self, filter):
+        """MASK_NEAREST (default) or MASK_BILINEAR: how the march and the lens camera read the stop mask."""
+        self._ck(self.lib.lf_set_mask_filter(self.ctx, int(filter)))
+
+    def mask_filter(self):
+        f = C.c_int()
+        self._ck(self.lib.lf_get_mask_filter(self.ctx, C.byref(f)))
+        return f.value
 
     def aperture_stats(self, slot):
         st = ApertureStats()

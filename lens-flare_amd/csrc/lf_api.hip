@@ -159,6 +159,51 @@ lf_status upload_paraxial(lf_ctx* ctx) {
   return LF_OK;
 }
 
+// how far from the centre the mask is open (a sampling parameter for lf_aim_at_exit_pupil, not pixel
+// arithmetic): the far corner of the outermost texel > 0, as the march maps texels onto [-h, h]^2.  grow2 = 1
+// (LF_MASK_BILINEAR): every open texel's footprint grown by half a texel on every side, [x - 0.5, x + 1.5]
+double mask_open_radius(const float* texels, int width, int height, int grow2) {
+  double r2max = 0.0;
+  const double hw = 0.5 * width, hh = 0.5 * height, g = 0.5 * grow2;
+  for (int y = 0; y < height; y++)
+    for (int x = 0; x < width; x++)
+      if (texels[(size_t)y * width + x] > 0.0f) {
+        const double ex = std::max(std::fabs(x - g - hw), std::fabs(x + 1 + g - hw)) / hw;
+        const double ey = std::max(std::fabs(y - g - hh), std::fabs(y + 1 + g - hh)) / hh;
+        r2max = std::max(r2max, ex * ex + ey * ey);
+      }
+  return std::sqrt(r2max);
+}
+
+// What follows the stop mask AND how it is read (lf_set_aperture(STARBURST), lf_set_mask_filter): the open radius,
+// the occupancy grid of the cull pre-pass, the support texture of the bilinear lookup; a resident cull table and
+// the lens camera's calibration are stale.
+lf_status derive_stop_mask(lf_ctx* ctx) {
+  LfApertureDev& a = ctx->ap[LF_APERTURE_STARBURST];
+  const int width = a.w, height = a.h;
+  const float* texels = ctx->mask_host.data();
+  const int grow2 = ctx->mask_filter == LF_MASK_BILINEAR ? 1 : 0;   // half texels the open footprint grows by
+  a.open_radius = mask_open_radius(texels, width, height, grow2);
+  // occupancy of the stop mask for the march's cull pre-pass (lf_cull.hip): which of kCullOcc x kCullOcc cells
+  // of the mask holds a texel > 0 (a texel belongs to every cell it touches; in half-texel units under the filter)
+  for (int r = 0; r < kCullOcc; r++) ctx->cull_occ[r] = 0u;
+  const long long w2 = 2ll * width, h2 = 2ll * height;
+  for (int y = 0; y < height; y++)
+    for (int x = 0; x < width; x++)
+      if (texels[(size_t)y * width + x] > 0.0f) {
+        const long long xa = std::max(0ll, 2ll * x - grow2), xb = std::min(w2, 2ll * (x + 1) + grow2);
+        const long long ya = std::max(0ll, 2ll * y - grow2), yb = std::min(h2, 2ll * (y + 1) + grow2);
+        const int cx0 = (int)(xa * kCullOcc / w2), cx1 = (int)((xb * kCullOcc - 1) / w2);
+        const int cy0 = (int)(ya * kCullOcc / h2), cy1 = (int)((yb * kCullOcc - 1) / h2);
+        for (int cy = cy0; cy <= cy1 && cy < kCullOcc; cy++)
+          for (int cx = cx0; cx <= cx1 && cx < kCullOcc; cx++) ctx->cull_occ[cy] |= 1u << cx;
+      }
+  ctx->mask_generation++;
+  ctx->lenscam_dirty = true;   // the stop mask is part of the lens camera's exposure calibration
+  if (grow2) return lfk_mask_support(ctx);
+  return LF_OK;
+}
+
 }  // namespace
 
 // host: the float constants of coated_fraction (lf_march_events.h) for one (interface, direction, wavelength)
@@ -388,41 +433,19 @@ lf_status lf_set_aperture(lf_ctx* ctx, lf_aperture_slot slot, const float* texel
   a.valid = false;
   lf_status st;
   LF_HIP(ctx, hipStreamSynchronize(ctx->stream));  // kernels in flight may read the old texels / spectrum
-  if ((st = dev_alloc(ctx, &a.texels, (size_t)width * height)) != LF_OK) return st;
+  // (the stop mask's slot keeps room for its support texture, 2 w x 2 h, behind the texels: lf_set_mask_filter)
+  if ((st = dev_alloc(ctx, &a.texels, (size_t)width * height * (slot == LF_APERTURE_STARBURST ? 5 : 1))) != LF_OK) return st;
   a.w = width; a.h = height;
   LF_HIP(ctx, hipMemcpyAsync(a.texels, texels, sizeof(float) * (size_t)width * height,
                              hipMemcpyHostToDevice, ctx->stream));
   if ((st = lfk_aperture_stats(ctx, slot)) != LF_OK) return st;
-  {
-    // how far from the centre the mask is open (a sampling parameter for lf_aim_at_exit_pupil, not pixel
-    // arithmetic): the far corner of the outermost texel > 0, as the march maps texels onto [-h, h]^2
-    double r2max = 0.0;
-    const double hw = 0.5 * width, hh = 0.5 * height;
-    for (int y = 0; y < height; y++)
-      for (int x = 0; x < width; x++)
-        if (texels[(size_t)y * width + x] > 0.0f) {
-          const double ex = std::max(std::fabs(x - hw), std::fabs(x + 1 - hw)) / hw;
-          const double ey = std::max(std::fabs(y - hh), std::fabs(y + 1 - hh)) / hh;
-          r2max = std::max(r2max, ex * ex + ey * ey);
-        }
-    a.open_radius = std::sqrt(r2max);
-  }
   a.valid = true;
-  if (slot == LF_APERTURE_STARBURST) {
-    // occupancy of the stop mask for the march's cull pre-pass (lf_cull.hip): which of kCullOcc x kCullOcc cells
-    // of the mask holds a texel > 0 (a texel belongs to every cell it touches)
-    for (int r = 0; r < kCullOcc; r++) ctx->cull_occ[r] = 0u;
-    for (int y = 0; y < height; y++)
-      for (int x = 0; x < width; x++)
-        if (texels[(size_t)y * width + x] > 0.0f) {
-          const int cx0 = (int)((long long)x * kCullOcc / width), cx1 = (int)(((long long)(x + 1) * kCullOcc - 1) / width);
-          const int cy0 = (int)((long long)y * kCullOcc / height), cy1 = (int)(((long long)(y + 1) * kCullOcc - 1) / height);
-          for (int cy = cy0; cy <= cy1 && cy < kCullOcc; cy++)
-            for (int cx = cx0; cx <= cx1 && cx < kCullOcc; cx++) ctx->cull_occ[cy] |= 1u << cx;
-        }
-    ctx->mask_generation++;
+  if (slot != LF_APERTURE_STARBURST) {
+    a.open_radius = mask_open_radius(texels, width, height, 0);
+  } else {
+    ctx->mask_host.assign(texels, texels + (size_t)width * height);
+    if ((st = derive_stop_mask(ctx)) != LF_OK) { a.valid = false; return st; }
     ctx->spectrum_valid = false;
-    ctx->lenscam_dirty = true;   // the stop mask is part of the lens camera's exposure calibration
     size_t rows = a.host_stats.max_y >= a.host_stats.min_y
                       ? (size_t)(a.host_stats.max_y - a.host_stats.min_y + 1) : 1;
     if ((st = dev_alloc(ctx, &ctx->spectrum, (size_t)width * width)) != LF_OK) return st;
@@ -1352,6 +1375,47 @@ lf_status lf_irradiance_falloff(lf_ctx* ctx, int x, int y, double radius, double
     return lf_fail(ctx, LF_ERR_STATE, "MT19937 jitter selected but no table (frame was resized?)");
   LF_HIP(ctx, hipSetDevice(ctx->device));
   return lfk_irradiance_falloff(ctx, x, y, radius, rgb);
+}
+
+// ---------------------------------------------------------------- stop-mask filter --------------
+lf_status lf_set_mask_filter(lf_ctx* ctx, int filter) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (filter != LF_MASK_NEAREST && filter != LF_MASK_BILINEAR)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_mask_filter: LF_MASK_NEAREST or LF_MASK_BILINEAR");
+  if (filter == ctx->mask_filter) return LF_OK;
+  ctx->mask_filter = filter;
+  if (!ctx->ap[LF_APERTURE_STARBURST].valid) return LF_OK;   // (lf_set_aperture derives everything under the filter set)
+  LF_HIP(ctx, hipSetDevice(ctx->device));
+  LF_HIP(ctx, hipStreamSynchronize(ctx->stream));            // kernels in flight may read the support texture
+  return derive_stop_mask(ctx);
+}
+
+lf_status lf_get_mask_filter(lf_ctx* ctx, int* filter) {
+  if (!ctx || !filter) return LF_ERR_INVALID;
+  *filter = ctx->mask_filter;
+  return LF_OK;
+}
+
+lf_status lf_mask_lookup(const float* texels, int w, int h, int filter, float u, float v, float* value, int* open) {
+  if (!texels || w <= 0 || h <= 0 || w > 4096 || h > 4096 || !std::isfinite(u) || !std::isfinite(v)) return LF_ERR_INVALID;
+  if (filter != LF_MASK_NEAREST && filter != LF_MASK_BILINEAR) return LF_ERR_INVALID;
+  // the stop event's mapping (stop_event, lf_march_events.h) with hx * inv_h = u
+  const float fu = std::fmaf(u, 1.0f, 1.0f) * (0.5f * (float)w);
+  const float fv = std::fmaf(v, 1.0f, 1.0f) * (0.5f * (float)h);
+  if (!std::isfinite(fu) || !std::isfinite(fv)) return LF_ERR_INVALID;
+  float a;
+  bool alive;
+  if (filter == LF_MASK_BILINEAR) {
+    alive = lfm::lf_mask_bilinear(texels, w, h, fu, fv, a);
+  } else {
+    const int ix = std::min(std::max((int)std::min(std::max(fu, -1.0f), (float)w), 0), w - 1);
+    const int iy = std::min(std::max((int)std::min(std::max(fv, -1.0f), (float)h), 0), h - 1);
+    a = texels[(size_t)iy * w + ix];
+    alive = a > 0.0f;
+  }
+  if (value) *value = a;
+  if (open) *open = alive ? 1 : 0;
+  return LF_OK;
 }
 
 // ---------------------------------------------------------------- coatings ----------------------

@@ -782,7 +782,7 @@ struct PathTally {
 // the events of the path's own sequence, K wavelengths together, tallies, the lobe test, the weighted second march
 // (W1 = false) and the fixed-point add into the tile's LDS sums at pixel slot acc_slot.  Shared by the two culled
 // kernels below: lane = pixel (k_march_cull) and lane = one compacted (pixel, sample) item (k_march_items).
-template <int K, bool W1, bool COAT>
+template <int K, bool W1, int VAR>
 __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                                                    const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
                                                    const LfWeightRow* __restrict__ wrec_table, const float* __restrict__ mask,
@@ -827,7 +827,7 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
 #pragma unroll
         for (int j = 0; j < K; j++) {
           if (K > 1 && __builtin_expect(alive[j] == 0ull, 0)) { okv[j] = 0ull; gv[j] = 0ull; continue; }
-          okv[j] = stop_event<W1>(r[j], wr.dzv, wr.h2, inv_stop_h, mask, a.mw, a.mh);
+          okv[j] = stop_event_var<W1, VAR>(r[j], wr.dzv, wr.h2, inv_stop_h, mask, a.mw, a.mh);
           gv[j] = okv[j];
           died |= alive[j] & ~okv[j];
         }
@@ -846,7 +846,7 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
             if (K > 1 && __builtin_expect(alive[j] == 0ull, 0)) { okv[j] = 0ull; gv[j] = 0ull; continue; }
             okv[j] = surface_event<W1>(r[j], wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, wr.cn22[j], wr.rn2[j],
                                        wr.delta[j], wr.h2, false, false, wr.sgn, gv[j], ww.fs[j], ww.fo[j], ww.fi[j],
-                                       CoatSel<COAT>{wrec_table, ww.coat, j});
+                                       CoatSel<VAR>{wrec_table, ww.coat, j});
             died |= alive[j] & ~okv[j];
           }
         } else if (kind == (unsigned)LF_EV_REFLECT) {      // a curved mirror: two rows of every pair
@@ -855,7 +855,7 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
             if (K > 1 && __builtin_expect(alive[j] == 0ull, 0)) { okv[j] = 0ull; gv[j] = 0ull; continue; }
             okv[j] = surface_event<W1>(r[j], wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, wr.cn22[j], wr.rn2[j],
                                        wr.delta[j], wr.h2, true, false, wr.sgn, gv[j], ww.fs[j], ww.fo[j], ww.fi[j],
-                                       CoatSel<COAT>{wrec_table, ww.coat, j});
+                                       CoatSel<VAR>{wrec_table, ww.coat, j});
             died |= alive[j] & ~okv[j];
           }
         } else {
@@ -865,7 +865,7 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
             okv[j] = surface_event<W1>(r[j], wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, wr.cn22[j], wr.rn2[j],
                                        wr.delta[j], wr.h2, (kind & LF_EV_REFLECT) != 0, (kind & LF_EV_FLAT) != 0,
                                        wr.sgn, gv[j], ww.fs[j], ww.fo[j], ww.fi[j],
-                                       CoatSel<COAT>{wrec_table, ww.coat, j});
+                                       CoatSel<VAR>{wrec_table, ww.coat, j});
             died |= alive[j] & ~okv[j];
           }
         }
@@ -909,7 +909,7 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
         { const float ns = lens->n_start[l]; rw.dx *= ns; rw.dy *= ns; rw.dz *= ns; }
         T.n_rm_lane += (unsigned long long)((unsigned)n_ev * (unsigned)__popcll(lj));
         T.n_rm_rows += (unsigned)n_ev;
-        weighted_remarch<COAT>(rw, seq, n_ev, j, recs, wrecs, wrec_table, mask, inv_stop_h, a.mw, a.mh);
+        weighted_remarch<VAR>(rw, seq, n_ev, j, recs, wrecs, wrec_table, mask, inv_stop_h, a.mw, a.mh);
       }
       const float qq = lobe_q(rw.dx, rw.dy, rw.dz, sx, sy, sz, sun_ss, inv_1mc);
       const float om = 1.0f - qq;
@@ -953,7 +953,7 @@ __device__ __forceinline__ lanemask surface_rows(Ray (&r)[K], const lanemask (&a
   return died;
 }
 
-template <int K, bool COAT>
+template <int K, int VAR>
 __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                                                   const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
                                                   const LfWeightRow* __restrict__ wrec_table, const float* __restrict__ mask,
@@ -1023,7 +1023,7 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
 #pragma unroll
           for (int j = 0; j < K; j++) {
             if (K > 1 && __builtin_expect(alive[j] == 0ull, 0)) { okv[j] = 0ull; gv[j] = 0ull; continue; }
-            okv[j] = stop_event<false>(r[j], wr.dzv, wr.h2, inv_stop_h, mask, a.mw, a.mh);
+            okv[j] = stop_event_var<false, VAR>(r[j], wr.dzv, wr.h2, inv_stop_h, mask, a.mw, a.mh);
             gv[j] = okv[j];
             died |= alive[j] & ~okv[j];
           }
@@ -1077,7 +1077,7 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
             { const float ns = lens->n_start[l]; rw.dx *= ns; rw.dy *= ns; rw.dz *= ns; }
             T.n_rm_lane += (unsigned long long)((unsigned)n_ev * (unsigned)__popcll(lj));
             T.n_rm_rows += (unsigned)n_ev;
-            weighted_remarch<COAT>(rw, seq, n_ev, j, recs, wrecs, wrec_table, mask, inv_stop_h, a.mw, a.mh);
+            weighted_remarch<VAR>(rw, seq, n_ev, j, recs, wrecs, wrec_table, mask, inv_stop_h, a.mw, a.mh);
             const float qq = lobe_q(rw.dx, rw.dy, rw.dz, sx, sy, sz, sun_ss, inv_1mc);
             const float om = 1.0f - qq;
             float contrib = __fdiv_rn(rw.wn, rw.wd) * (om * om);
@@ -1114,8 +1114,9 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
                               // a workgroup holds 2 waves per SIMD, so 5 runs as 4: 47 ms against 38 on the bench frame)
 #endif
 // MODE 0: every started path alone; 1 = SHARED (one table entry per wave and sample, the leg once: march_started_set)
-// COAT: the lens has a film somewhere (lf_set_lens_coatings): the weighted march can evaluate one
-template <int K, bool W1, int MODE, bool COAT>
+// VAR (lf_march_events.h): what the weighted march can evaluate -- kVarCoat: the lens has a film somewhere
+// (lf_set_lens_coatings); kVarFilt: the stop mask is read bilinearly (lf_set_mask_filter)
+template <int K, bool W1, int MODE, int VAR>
 __global__ __launch_bounds__(64 * kWgWaves, (K == 1 ? 8 : MODE == 1 ? LF_SHARED_WAVES : 6))
 void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                   const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
@@ -1227,7 +1228,7 @@ void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restri
         const unsigned long long todo = crow[entry];
         if (todo == 0ull) continue;
         const StartRay s0 = aim_at_pupil(X, Y, pa0, pb0, pupil_h, vz_u, geom_norm);
-        march_started_set<K, COAT>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, todo, active_mask, X, Y, s0, lane, s_acc, s_meta, T);
+        march_started_set<K, VAR>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, todo, active_mask, X, Y, s0, lane, s_acc, s_meta, T);
         continue;
       }
       unsigned long long mine, todo;
@@ -1246,7 +1247,7 @@ void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restri
         const int q = __builtin_ctzll(left_q);
         left_q &= left_q - 1ull;
         const lanemask start_mask = active_mask & __ballot(((mine >> q) & 1ull) != 0ull);   // (all active lanes when the wave shares a cell)
-        march_started_path<K, W1, COAT>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, q, start_mask, X, Y, s0, lane, lane, s_acc, T);
+        march_started_path<K, W1, VAR>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, q, start_mask, X, Y, s0, lane, lane, s_acc, T);
       }
     }
     __syncthreads();
@@ -1323,7 +1324,7 @@ constexpr int kItemCap = 16384;      // items of a chunk (2 bytes each)
 constexpr int kItemChunk = 256;      // samples per chunk at most (8 bits of an item; the pixel takes 6)
 constexpr int kItemCellCache = 64;   // chunks of up to this many samples keep each (sample, pixel)'s table cell between the two listing passes
 
-template <int K, bool COAT>
+template <int K, int VAR>
 __global__ __launch_bounds__(64 * kWgWaves, 6)      // (42 KB of LDS lists: three workgroups per CU)
 void k_march_items(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                    const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
@@ -1478,7 +1479,7 @@ void k_march_items(const LfLensDev* __restrict__ lens, const LfPairsDev* __restr
       const float X = -(((float)x + jx) - half_w) * pitch;
       const float Y = -(((float)y + jy) - half_h) * pitch;
       const StartRay s0 = aim_at_pupil(X, Y, fmaf(2.0f, ua, -1.0f), fmaf(2.0f, ub, -1.0f), pupil_h, vz_u, geom_norm);
-      march_started_path<K, false, COAT>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, q, __ballot(have), X, Y, s0, lane, px, s_acc, T);
+      march_started_path<K, false, VAR>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, q, __ballot(have), X, Y, s0, lane, px, s_acc, T);
     }
     __syncthreads();
     c0 += chn;
@@ -1706,6 +1707,9 @@ lf_status lfk_cull_finish(lf_ctx* ctx, uint64_t hash) {
     a.pupil_h = L.pupil_h; a.vz = L.pupil_z - L.z_sensor; a.geom_norm = L.geom_norm; a.inv_stop_h = 1.0f / L.stop_h;
     a.lobe_thr = lf_march_lobe_thr(L);
     a.mw = m.w; a.mh = m.h;
+    // under LF_MASK_BILINEAR the audit's (unchanged) nearest lookup reads the support texture behind the texels
+    const float* audit_mask = m.texels;
+    if (ctx->mask_filter == LF_MASK_BILINEAR) { audit_mask = m.texels + (size_t)m.w * m.h; a.mw = 2 * m.w; a.mh = 2 * m.h; }
     const uint64_t k = (ctx->cull_audit_seq++) * 0x9e3779b97f4a7c15ull ^ hash;
     a.key = make_uint2((unsigned)k, (unsigned)(k >> 32));
     a.density = ctx->cull_audit_density;
@@ -1714,7 +1718,7 @@ lf_status lfk_cull_finish(lf_ctx* ctx, uint64_t hash) {
     hipEvent_t ev = lf_timing_begin(ctx, LFK_CULL_AUDIT);
     hipLaunchKernelGGL(k_cull_audit, grid, dim3(256), 0, ctx->stream, ctx->lens_dev, ctx->pairs_dev,
                        (const int*)(ctx->prog_dev + ctx->prog_seq_off), (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),
-                       m.texels, a, ctx->cull_dev, ctx->cull_popc_dev + 1);
+                       audit_mask, a, ctx->cull_dev, ctx->cull_popc_dev + 1);
     lf_timing_end(ctx, LFK_CULL_AUDIT, ev);
     LF_HIP(ctx, hipGetLastError());
   }
@@ -1952,14 +1956,16 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
   if (ctx->cull_no_prefix) c.prefix_ok = 0;
   c.P = ctx->cull_P; c.m = ctx->cull_m; c.m_shift = ctx->cull_m == 4 ? 2 : ctx->cull_m == 2 ? 1 : 0;
   hipEvent_t ev = lf_timing_begin(ctx, LFK_MARCH);
-#define LF_LAUNCH_CULL1(KK, WW, SS)  do { if (coated) LF_LAUNCH_CULL2(KK, WW, SS, true); else LF_LAUNCH_CULL2(KK, WW, SS, false); } while (0)
+#define LF_LAUNCH_CULL1(KK, WW, SS)  do { switch (var) { case kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarCoatFilt); break; case kVarFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarFilt); break; \
+                                                      case kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarCoat); break; default: LF_LAUNCH_CULL2(KK, WW, SS, kVarBare); break; } } while (0)
 #define LF_LAUNCH_CULL2(KK, WW, SS, CC)                                                                       \
   hipLaunchKernelGGL((k_march_cull<KK, WW, SS, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                         \
                      (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),                                  \
                      (const LfWeightRow*)(ctx->prog_dev + ctx->prog_wrec_off), m.texels, a, c, ctx->ghost,   \
                      ctx->accum, ctx->counters_dev)
-#define LF_LAUNCH_ITEMS(KK)  do { if (coated) LF_LAUNCH_ITEMS2(KK, true); else LF_LAUNCH_ITEMS2(KK, false); } while (0)
+#define LF_LAUNCH_ITEMS(KK)  do { switch (var) { case kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarCoatFilt); break; case kVarFilt: LF_LAUNCH_ITEMS2(KK, kVarFilt); break; \
+                                              case kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarCoat); break; default: LF_LAUNCH_ITEMS2(KK, kVarBare); break; } } while (0)
 #define LF_LAUNCH_ITEMS2(KK, CC)                                                                             \
   hipLaunchKernelGGL((k_march_items<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                         \
@@ -1969,7 +1975,7 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
 #define LF_LAUNCH_CULL(KK) do { if (items) LF_LAUNCH_ITEMS(KK); else if (weights_first) LF_LAUNCH_CULL1(KK, true, 0); \
                                 else if (shared_leg) LF_LAUNCH_CULL1(KK, false, 1); else LF_LAUNCH_CULL1(KK, false, 0); } while (0)
   const bool weights_first = ctx->cull_weights_first;   // (lf_test_knob: the weight on every executed event)
-  const bool coated = ctx->coat.n > 0;                   // the variant that evaluates films (lf_set_lens_coatings)
+  const int var = lf_march_variant(ctx);                // the variant that evaluates films / the bilinear mask
   // every pixel its own pupil point (no sub-cells at all): the compacted march.  (2 x 2 sub-cells, where the lanes of a
   // wave still look their cells up one by one, stay with k_march_cull: 48 against 59 ms on the bench frame)
   bool items = ctx->march_sub_bits == 0;

@@ -79,7 +79,7 @@ constexpr int kMaxSunLightArgs = 32;
 struct LfSunLightArgs { double v[6 * kMaxSunLightArgs]; };
 
 struct LfApertureDev {
-  float* texels = nullptr;  // w*h
+  float* texels = nullptr;  // w*h (the STARBURST slot: 5 w h, the support texture of lf_set_mask_filter behind them)
   int w = 0, h = 0;
   lf_aperture_stats* stats = nullptr;  // device copy
   lf_aperture_stats host_stats{};
@@ -432,6 +432,8 @@ struct lf_ctx {
   float raw_semi_ap[LF_MAX_SURFACES] = {};
   float pupil_target_h = 0.0f, pupil_target_z = 0.0f;   // lf_set_pupil_target; h <= 0: the rear element
   LfCoatings coat;                                        // lf_set_lens_coatings (cleared by lf_set_lens)
+  int mask_filter = LF_MASK_NEAREST;                      // lf_set_mask_filter (a setting of the context: nothing clears it)
+  std::vector<float> mask_host;                           // the STARBURST slot's texels (occupancy / open radius follow the filter)
   bool ghost_accumulate = false;                          // lf_set_ghost_accumulate
   LfLensDev* lens_dev = nullptr;
   LfPairsDev pairs{};
@@ -493,7 +495,7 @@ struct lf_ctx {
   uint64_t cull_audit_seq = 0;                 // tables audited by this context: keys the audit's rays
   bool lens_lambda_monotonic = true;           // every glass disperses the same way along the wavelength columns (lf_derive_lens)
   unsigned cull_occ[kCullOcc] = {};            // occupancy of the stop mask (host, lf_set_aperture)
-  uint64_t mask_generation = 0;                // bumped by lf_set_aperture(STARBURST)
+  uint64_t mask_generation = 0;                // bumped by lf_set_aperture(STARBURST) and by a switch of lf_set_mask_filter
   bool last_march_culled = false;              // what the last lf_trace_ghosts ran
   int march_k = 1;                             // wavelengths (rays per lane) that walk together
   int march_fix_bits = 36;                     // the last launch's fixed-point exponent (lf_get_march_fix_bits)
@@ -565,6 +567,10 @@ inline void lf_install_split(lf_ctx* ctx, const LfSplit& s) {
   }
   ctx->split = s;
 }
+// the kernel variant of the weighted march (lf_march_events.h: kVarBare .. kVarCoatFilt)
+inline int lf_march_variant(const lf_ctx* ctx) {
+  return (ctx->coat.n > 0 ? 1 : 0) | (ctx->mask_filter == LF_MASK_BILINEAR ? 2 : 0);
+}
 // the cull table is not this context's alone: shared between ranks, or built only in part (the frame dealt by blocks)
 inline bool lf_cull_table_split(const lf_ctx* ctx) {
   return ctx->split.table != LfSplit::kOwn || ctx->split.deal == LfSplit::kBlocks;
@@ -598,6 +604,7 @@ lf_status lf_lenscam_prepare(lf_ctx* ctx);            // table + calibration up 
 lf_status lf_upload_primary_table(lf_ctx* ctx);       // LfPrimaryDev from ctx->lens (k_lens_rays needs it too)
 void lf_fill_lenscam_args(const lf_ctx* ctx, LfLensCamArgs* a);
 lf_status lf_build_march_tables(lf_ctx* ctx, std::vector<LfEventRow>& rows, std::vector<int>& skip);
+lf_status lfk_mask_support(lf_ctx* ctx);              // the support texture of the bilinear stop mask, behind the texels
 lf_status lfk_native_sqrt(lf_ctx* ctx, const float* d_x, float* d_y, size_t n);
 lf_status lfk_native_rcp(lf_ctx* ctx, const float* d_x, float* d_y, size_t n);
 void lf_apply_pupil_target(lf_ctx* ctx);

@@ -96,7 +96,7 @@ __device__ unsigned long long* g_lit_map[8];
 #ifndef LF_SKIP_DEAD_LAMBDA
 #define LF_SKIP_DEAD_LAMBDA 1   // experiments (profiles/r04_march_variants.txt): 0 = no per-wavelength liveness branch
 #endif
-template <int K, bool COAT>   // COAT: the lens has a film somewhere (lf_set_lens_coatings)
+template <int K, int VAR>   // VAR (lf_march_events.h): kVarCoat = the lens has a film somewhere, kVarFilt = bilinear stop mask
 __global__ __launch_bounds__(64 * kWgWaves, (K == 1 ? 8 : 6))
 void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
              const int* __restrict__ seq_table, const LfProgHdr* __restrict__ hdr_table,
@@ -441,7 +441,7 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
             for (int j = 0; j < K; j++) {
               if (LF_SKIP_DEAD_LAMBDA && K > 1 && __builtin_expect(alive[j] == 0ull, 0)) { okv[j] = 0ull; continue; }
               LF_HIST(2, alive[j]);
-              okv[j] = stop_event<kW1>(r[j], cur.dzv, cur.h2, inv_stop_h, mask, a.mw, a.mh);
+              okv[j] = stop_event_var<kW1, VAR>(r[j], cur.dzv, cur.h2, inv_stop_h, mask, a.mw, a.mh);
               died |= alive[j] & ~okv[j];
             }
             if (__builtin_expect(died != 0ull, 0)) {
@@ -566,12 +566,12 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
                   const float w_fo = j == 0 ? ww.fo[0] : j == 1 ? ww.fo[1] : ww.fo[2];
                   const float w_fi = j == 0 ? ww.fi[0] : j == 1 ? ww.fi[1] : ww.fi[2];
                   if (wfl & LF_EV_STOP) {
-                    (void)stop_event<true>(rw, wr.dzv, wr.h2, inv_stop_h, mask, a.mw, a.mh);
+                    (void)stop_event_var<true, VAR>(rw, wr.dzv, wr.h2, inv_stop_h, mask, a.mw, a.mh);
                   } else {
                     lanemask geom_ok;
                     (void)surface_event<true>(rw, wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, w_cn22, w_rn2, w_delta, wr.h2,
                                               (wfl & LF_EV_REFLECT) != 0, (wfl & LF_EV_FLAT) != 0, wr.sgn, geom_ok,
-                                              w_fs, w_fo, w_fi, CoatSel<COAT>{wrec_table, ww.coat, j});
+                                              w_fs, w_fo, w_fi, CoatSel<VAR>{wrec_table, ww.coat, j});
                   }
                 }
                 }
@@ -653,7 +653,7 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
 // the prescription (the same event arithmetic as the ghost march); out = {origin xyz on the front
 // element, unit direction xyz towards the scene, transmitted weight, alive flag} in lens space
 // (z along the axis, light travels +z, the scene is at z < 0).
-template <bool COAT>   // COAT: the lens has a film somewhere (lf_set_lens_coatings)
+template <int VAR>   // VAR: as k_march's
 __global__ __launch_bounds__(256) void k_lens_rays(const LfLensDev* __restrict__ lens,
                                                    const LfPrimaryDev* __restrict__ prim,
                                                    const float* __restrict__ mask, int mw, int mh,
@@ -667,13 +667,29 @@ __global__ __launch_bounds__(256) void k_lens_rays(const LfLensDev* __restrict__
   const float pa = active ? pupil_uv[2 * i] : 0.0f, pb = active ? pupil_uv[2 * i + 1] : 0.0f;
   const StartRay s0 = aim_at_pupil(X, Y, pa, pb, lens->pupil_h, lens->pupil_z - lens->z_sensor, lens->geom_norm);
   Ray r{X, Y, 0.0f, fmaf(X, X, Y * Y), s0.dx, s0.dy, s0.dz, s0.w0, 1.0f};
-  const bool alive = primary_path<COAT>(prim, lambda, r, mask, mw, mh, lane);
+  const bool alive = primary_path<VAR>(prim, lambda, r, mask, mw, mh, lane);
   if (active) {
     float* o = out + 8 * (size_t)i;
     o[0] = r.px; o[1] = r.py; o[2] = prim->front_zv + r.hz; o[3] = r.dx; o[4] = r.dy; o[5] = r.dz;
     o[6] = alive ? __fdiv_rn(r.wn, r.wd) : 0.0f;
     o[7] = alive ? 1.0f : 0.0f;
   }
+}
+
+// The support texture of the bilinear stop mask (lf_set_mask_filter; DESIGN.md section 5, "the support texture"):
+// S is 2 mw x 2 mh, separable per axis with clamped indices, S[2 i] = max(t[i - 1], t[i]), S[2 i + 1] =
+// max(t[i], t[i + 1]) of t = max(texel, 0): the nearest lookup of the geometry-only march, run on (S, 2 mw, 2 mh),
+// lands in S[2 i] for fu in [i, i + 1/2) and in S[2 i + 1] for fu in [i + 1/2, i + 1) (2 fu is exact), so S > 0 is
+// "one of the four texels of the bilinear footprint is open".  Built when the mask or the filter changes, not per frame.
+__global__ __launch_bounds__(256) void k_mask_support(const float* __restrict__ texels, int mw, int mh,
+                                                      float* __restrict__ S) {
+  const int sx = (int)(blockIdx.x * blockDim.x + threadIdx.x), sy = (int)blockIdx.y;
+  if (sx >= 2 * mw || sy >= 2 * mh) return;
+  const int xa = max((sx - 1) >> 1, 0), xb = min((sx + 1) >> 1, mw - 1);   // sx = 2 i: i - 1, i;  2 i + 1: i, i + 1
+  const int ya = max((sy - 1) >> 1, 0), yb = min((sy + 1) >> 1, mh - 1);
+  const float m0 = fmaxf(texels[(size_t)ya * mw + xa], texels[(size_t)ya * mw + xb]);
+  const float m1 = fmaxf(texels[(size_t)yb * mw + xa], texels[(size_t)yb * mw + xb]);
+  S[(size_t)sy * (size_t)(2 * mw) + sx] = fmaxf(fmaxf(m0, m1), 0.0f);
 }
 
 __global__ void k_native_sqrt(const float* __restrict__ x, float* __restrict__ y, size_t n) {
@@ -1337,7 +1353,8 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
     if (st != LF_OK) return st;
   } else {
   hipEvent_t ev = lf_timing_begin(ctx, LFK_MARCH);
-#define LF_LAUNCH_MARCH(KK)  do { if (ctx->coat.n > 0) LF_LAUNCH_MARCH2(KK, true); else LF_LAUNCH_MARCH2(KK, false); } while (0)
+#define LF_LAUNCH_MARCH(KK)  do { switch (lf_march_variant(ctx)) { case kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarCoatFilt); break; case kVarFilt: LF_LAUNCH_MARCH2(KK, kVarFilt); break; \
+                                   case kVarCoat: LF_LAUNCH_MARCH2(KK, kVarCoat); break; default: LF_LAUNCH_MARCH2(KK, kVarBare); break; } } while (0)
 #define LF_LAUNCH_MARCH2(KK, CC)                                                                   \
   hipLaunchKernelGGL((k_march<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                \
@@ -1372,8 +1389,8 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
 
 lf_status lfk_march(lf_ctx* ctx, int spp, uint64_t key) {
 #ifdef LF_MARCH_ALL_WEIGHTS
-  if (ctx->coat.n > 0)
-    return lf_fail(ctx, LF_ERR_INVALID, "LF_MARCH_ALL_WEIGHTS (timing ablation): a coated lens is not supported");
+  if (ctx->coat.n > 0 || ctx->mask_filter != LF_MASK_NEAREST)
+    return lf_fail(ctx, LF_ERR_INVALID, "LF_MARCH_ALL_WEIGHTS (timing ablation): a coated lens / a filtered mask is not supported");
 #endif
   const int n = ctx->pairs.n;
   ctx->cull_chunks = 1;
@@ -1421,6 +1438,15 @@ lf_status lfk_native_rcp(lf_ctx* ctx, const float* d_x, float* d_y, size_t n) {
   return LF_OK;
 }
 
+// the support texture behind the STARBURST slot's texels (the slot holds 5 w h floats: lf_set_aperture)
+lf_status lfk_mask_support(lf_ctx* ctx) {
+  const LfApertureDev& m = ctx->ap[LF_APERTURE_STARBURST];
+  hipLaunchKernelGGL(k_mask_support, dim3((unsigned)((2 * m.w + 255) / 256), (unsigned)(2 * m.h)), dim3(256), 0, ctx->stream,
+                     m.texels, m.w, m.h, m.texels + (size_t)m.w * m.h);
+  LF_HIP(ctx, hipGetLastError());
+  return LF_OK;
+}
+
 lf_status lfk_lens_rays(lf_ctx* ctx, int lambda, int n, const float* d_xy, const float* d_uv,
                         float* d_out) {
   const LfApertureDev& m = ctx->ap[LF_APERTURE_STARBURST];
@@ -1429,12 +1455,16 @@ lf_status lfk_lens_rays(lf_ctx* ctx, int lambda, int n, const float* d_xy, const
                              ctx->stream));
   lf_status st = lf_upload_primary_table(ctx);
   if (st != LF_OK) return st;
-  if (ctx->coat.n > 0)
-    hipLaunchKernelGGL(k_lens_rays<true>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       ctx->lens_dev, ctx->primary_dev, m.texels, m.w, m.h, lambda, n, d_xy, d_uv, d_out);
-  else
-    hipLaunchKernelGGL(k_lens_rays<false>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,
-                       ctx->lens_dev, ctx->primary_dev, m.texels, m.w, m.h, lambda, n, d_xy, d_uv, d_out);
+#define LF_LAUNCH_LENS_RAYS(VV)                                                                         \
+  hipLaunchKernelGGL(k_lens_rays<VV>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,     \
+                     ctx->lens_dev, ctx->primary_dev, m.texels, m.w, m.h, lambda, n, d_xy, d_uv, d_out)
+  switch (lf_march_variant(ctx)) {
+    case kVarCoatFilt: LF_LAUNCH_LENS_RAYS(kVarCoatFilt); break;
+    case kVarFilt: LF_LAUNCH_LENS_RAYS(kVarFilt); break;
+    case kVarCoat: LF_LAUNCH_LENS_RAYS(kVarCoat); break;
+    default: LF_LAUNCH_LENS_RAYS(kVarBare); break;
+  }
+#undef LF_LAUNCH_LENS_RAYS
   LF_HIP(ctx, hipGetLastError());
   return LF_OK;
 }

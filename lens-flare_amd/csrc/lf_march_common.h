@@ -116,10 +116,11 @@ __device__ __forceinline__ LfProgHdr load_phdr(const LfProgHdr* __restrict__ bas
 
 // The weighted march of ONE path for wavelength j of group g (recs / wrecs: the group's records; wrec_table: group
 // 0's, where the film offsets count from) along its own sequence (n_ev dwords at w): the same arithmetic on the ray as
-// the geometry-only march, plus the Fresnel / aperture weight -- and, COAT (the kernels launched for a lens with a
-// film), a coated row's film.  The culled kernels' re-march of a lit path (k_march's path tree keeps the same loop
+// the geometry-only march, plus the Fresnel / aperture weight -- and, by the kernel's variant VAR (kVarCoat: launched
+// for a lens with a film; kVarFilt: for a context under LF_MASK_BILINEAR), a coated row's film and the bilinear mask.
+// The culled kernels' re-march of a lit path (k_march's path tree keeps the same loop
 // inline: folded into this function, its K = 2 instantiation spilled 13 SGPRs more).
-template <bool COAT>
+template <int VAR>
 __device__ __forceinline__ void weighted_remarch(Ray& rw, const int* __restrict__ w, int n_ev, int j, const LfProgRow* __restrict__ recs,
                                                  const LfWeightRow* __restrict__ wrecs,
                                                  const LfWeightRow* __restrict__ wrec_table, const float* __restrict__ mask,
@@ -136,12 +137,12 @@ __device__ __forceinline__ void weighted_remarch(Ray& rw, const int* __restrict_
     const float w_fo = j == 0 ? ww.fo[0] : j == 1 ? ww.fo[1] : ww.fo[2];
     const float w_fi = j == 0 ? ww.fi[0] : j == 1 ? ww.fi[1] : ww.fi[2];
     if (wfl & LF_EV_STOP) {
-      (void)stop_event<true>(rw, wr.dzv, wr.h2, inv_stop_h, mask, mw, mh);
+      (void)stop_event_var<true, VAR>(rw, wr.dzv, wr.h2, inv_stop_h, mask, mw, mh);
     } else {
       lanemask geom_ok;
       (void)surface_event<true>(rw, wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, w_cn22, w_rn2, w_delta, wr.h2,
                                 (wfl & LF_EV_REFLECT) != 0, (wfl & LF_EV_FLAT) != 0, wr.sgn, geom_ok, w_fs, w_fo, w_fi,
-                                CoatSel<COAT>{wrec_table, ww.coat, j});
+                                CoatSel<VAR>{wrec_table, ww.coat, j});
     }
   }
 }

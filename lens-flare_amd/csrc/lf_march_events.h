@@ -100,6 +100,28 @@ __host__ __device__ inline void coated_fraction(float sq, float ct, const LfCoat
   if (Ns_) { *Ns_ = N[0]; *Ds_ = D[0]; *Np_ = N[1]; *Dp_ = D[1]; }
 }
 
+// ---- the filtered stop mask ("mask filter") -------------------------------------
+// The bilinear lookup of LF_MASK_BILINEAR at texel coordinates (fu, fv) (texel i has its centre at i + 0.5):
+// the value a the weight is multiplied by, and whether the ray survives: ANY of the four texels open, not
+// a > 0 (the geometry-only march reads that from the support texture, and both must agree).  The indices are
+// clamped BEFORE the loads: a dead lane's NaN never addresses outside the texture.  Host and device:
+// lf_mask_lookup runs it too.
+__host__ __device__ inline bool lf_mask_bilinear(const float* __restrict__ mask, int mw, int mh, float fu, float fv,
+                                                 float& a) {
+  const float gx = fu - 0.5f, gy = fv - 0.5f;
+  const float bx = floorf(gx), by = floorf(gy);
+  const float fx = gx - bx, fy = gy - by;
+  // clamped as floats, before the conversion (fmaxf drops a NaN: texel 0, as anywhere left of it)
+  const int ix = (int)fminf(fmaxf(bx, -1.0f), (float)mw), iy = (int)fminf(fmaxf(by, -1.0f), (float)mh);
+  const int x0 = ix < 0 ? 0 : ix > mw - 1 ? mw - 1 : ix, x1 = ix + 1 > mw - 1 ? mw - 1 : ix + 1;
+  const int y0 = iy < 0 ? 0 : iy > mh - 1 ? mh - 1 : iy, y1 = iy + 1 > mh - 1 ? mh - 1 : iy + 1;
+  const float t00 = fmaxf(mask[y0 * mw + x0], 0.0f), t10 = fmaxf(mask[y0 * mw + x1], 0.0f);
+  const float t01 = fmaxf(mask[y1 * mw + x0], 0.0f), t11 = fmaxf(mask[y1 * mw + x1], 0.0f);
+  const float a0 = fmaf(fx, t10 - t00, t00), a1 = fmaf(fx, t11 - t01, t01);
+  a = fmaf(fy, a1 - a0, a0);
+  return fmaxf(fmaxf(t00, t10), fmaxf(t01, t11)) > 0.0f;
+}
+
 // The transmitted weight is carried as a fraction wn / wd: every Fresnel factor is a ratio of
 // two cheap products, so the march multiplies numerators and denominators separately and divides
 // ONCE, and only for the ~0.4 % of rays that end inside the sun's lobe.
@@ -227,7 +249,9 @@ __device__ __forceinline__ lanemask surface_event(Ray& r, float dzv, float c, fl
 }
 
 // the stop: flat pass-through, clipped by its housing and by the aperture mask
-template <bool W>
+// FILT (only with W: the weighted march of a context under LF_MASK_BILINEAR, lf_set_mask_filter) reads the mask
+// through lf_mask_bilinear below instead of the nearest texel; every other instantiation is the nearest lookup.
+template <bool W, bool FILT = false>
 __device__ __forceinline__ lanemask stop_event(Ray& r, float dzv, float h2, float inv_h,
                                                const float* __restrict__ mask, int mw, int mh) {
   const float t = -(r.hz + dzv) * lf_rcp(r.dz);
@@ -235,6 +259,13 @@ __device__ __forceinline__ lanemask stop_event(Ray& r, float dzv, float h2, floa
   const float r2 = fmaf(hx, hx, hy * hy);
   const float fu = fmaf(hx, inv_h, 1.0f) * (0.5f * (float)mw);
   const float fv = fmaf(hy, inv_h, 1.0f) * (0.5f * (float)mh);
+  if (W && FILT) {
+    float a;
+    const bool open = lf_mask_bilinear(mask, mw, mh, fu, fv, a);
+    r.wn *= a;
+    r.px = hx; r.py = hy; r.hz = 0.0f; r.r2 = r2;
+    return __ballot(r2 <= h2) & __ballot(open);
+  }
   int ix = (int)fu, iy = (int)fv;  // NaN / out-of-range of a dead lane is clamped, never faults
   ix = min(max(ix, 0), mw - 1);
   iy = min(max(iy, 0), mh - 1);
@@ -242,6 +273,22 @@ __device__ __forceinline__ lanemask stop_event(Ray& r, float dzv, float h2, floa
   if (W) r.wn *= a;
   r.px = hx; r.py = hy; r.hz = 0.0f; r.r2 = r2;
   return __ballot(r2 <= h2) & __ballot(a > 0.0f);
+}
+
+// ---- the kernel variants of the weighted march ------------------------------------------------------
+// What the weight of a ray may have to evaluate beyond bare glass and the nearest texel is chosen at compile
+// time, so that a context without it launches the kernels it always launched: bit 0 = a film somewhere on the
+// lens (lf_set_lens_coatings), bit 1 = the bilinear stop mask (lf_set_mask_filter).
+enum : int { kVarBare = 0, kVarCoat = 1, kVarFilt = 2, kVarCoatFilt = 3 };
+// The stop of a kernel instantiated for variant VAR.  Under the filter the geometry-only march (W = false) runs
+// the UNCHANGED nearest lookup on the support texture S (2 mw x 2 mh floats behind the texels, k_mask_support:
+// S > 0 exactly where one of the four texels of the bilinear footprint is open), the weighted march the
+// bilinear lookup on the texels: both find the same rays alive, bit for bit.
+template <bool W, int VAR>
+__device__ __forceinline__ lanemask stop_event_var(Ray& r, float dzv, float h2, float inv_h,
+                                                   const float* __restrict__ mask, int mw, int mh) {
+  if ((VAR & kVarFilt) && !W) return stop_event<false>(r, dzv, h2, inv_h, mask + mw * mh, 2 * mw, 2 * mh);
+  return stop_event<W, (VAR & kVarFilt) != 0>(r, dzv, h2, inv_h, mask, mw, mh);
 }
 
 // ---- one sensor sample's start ray ("sample") --------------------------------
@@ -346,8 +393,8 @@ struct CoatRec {
                    __int_as_float(v[4]), __int_as_float(v[5]), __int_as_float(v[6]), __int_as_float(v[7])};
   }
 };
-// what a kernel instantiated with / without film support (COAT) passes to surface_event
-template <bool COAT> using CoatSel = typename std::conditional<COAT, CoatRec, NoCoat>::type;
+// what a kernel instantiated with / without film support (bit kVarCoat of its variant) passes to surface_event
+template <int VAR> using CoatSel = typename std::conditional<(VAR & kVarCoat) != 0, CoatRec, NoCoat>::type;
 // ... and of a row of the primary table (the wavelength may differ between lanes: a plain load)
 struct CoatPrimary {
   const LfPrimaryRow* row;
@@ -361,7 +408,7 @@ struct CoatPrimary {
 // of pack_program) is wave-uniform and arrives through the scalar cache.  Returns whether this
 // lane's ray left the front element; r then holds the exit state (hz relative to interface 0's vertex,
 // K = the unit direction in air) and wn / wd the transmitted weight.
-template <bool COAT>
+template <int VAR>
 __device__ __forceinline__ bool primary_path(const LfPrimaryDev* __restrict__ P, int lambda, Ray& r,
                                              const float* __restrict__ mask, int mw, int mh, int lane) {
   { const float ns = P->n_start[lambda]; r.dx *= ns; r.dy *= ns; r.dz *= ns; }   // K = n d
@@ -371,9 +418,9 @@ __device__ __forceinline__ bool primary_path(const LfPrimaryDev* __restrict__ P,
     const LfPrimaryRow& w = P->row[e];
     lanemask ok, geom_ok;
     if (w.kind & LF_EV_STOP) {
-      ok = stop_event<true>(r, w.dzv, w.h2, P->inv_stop_h, mask, mw, mh);
+      ok = stop_event<true, (VAR & kVarFilt) != 0>(r, w.dzv, w.h2, P->inv_stop_h, mask, mw, mh);
     } else {
-      if (COAT)
+      if (VAR & kVarCoat)
         ok = surface_event<true>(r, w.dzv, w.curv, w.ch, w.c2, w.sc, w.cn22[lambda], w.rn2[lambda],
                                  w.delta[lambda], w.h2, false, (w.kind & LF_EV_FLAT) != 0, -1.0f, geom_ok,
                                  w.fs[lambda], w.fo[lambda], w.fi[lambda], CoatPrimary{&w, lambda});
