@@ -563,6 +563,15 @@ lf_status lf_trace_ghosts(lf_ctx* ctx, int spp, uint64_t key);
  * lf_counters / lf_get_executed_events count the rays that were started.
  *   mode 1 (default): on; the table is reused while lens, pairs, sun, frame, pupil disc, mask and sample
  *                     count are unchanged.   2: on, rebuilt at every lf_trace_ghosts.
+ *   What a rebuild recomputes: only what depends on the sun -- each surviving box's last test, its exit footprint against
+ *   the lobe, in one pass over a tree the context keeps.  What it does NOT recompute: the marches of the boxes' 15 rays and
+ *   every decision before that test (apertures, the mask's grid, lost samples), which depend on the lens, the frame, the
+ *   blocks, the mask, the pairs and the rank's share alone: built by the first launch that sees them, rebuilt when one of
+ *   them changes (a host that changes them at every launch pays no build per frame: after a tree that was never reused, the
+ *   next is built only for inputs seen on two launches running), freed by lf_destroy.  The tree is device memory the context
+ *   holds between launches: 4 bytes per (path, own block, cell) box of every level + 48 bytes per undecided box, under a
+ *   budget of 8 GiB (the 1080p 46-path frame: DESIGN.md section 5); a tree beyond the budget is not kept and every rebuild
+ *   marches its boxes as before.  The tables are the same bit for bit either way.
  *   mode 0: off -- every sample marches every selected path (rounds 1-4; the shared-leg path tree).
  * Applies to at most 128 paths and 4096 samples per pixel; beyond, lf_trace_ghosts marches everything (lf_get_cull_reason says why).
  * lf_get_cull_info: {mode, did the last lf_trace_ghosts cull, blocks_x, blocks_y, cells per block (the pupil
@@ -609,6 +618,8 @@ lf_status lf_get_cull_audit(lf_ctx* ctx, uint64_t* rays, uint64_t* lit, int* lau
  *   "cull_force" 0/1            keep the culled march whatever the table starts (small test frames)
  *   "cull_weights_first" 0/1    the Fresnel / mask weight on EVERY executed event (SURVEY 8d's unit), same pixels
  *   "cull_no_prefix" 0/1        every started path marched alone from the sensor (round 5's culled march), same pixels
+ *   "cull_cache" 0/1            0: no cached tree -- every pre-pass marches its boxes (the tree a context holds is kept), same table
+ *   "cull_cache_max_mb" MiB     the cached tree's byte budget (default 8192)
  *   "cull_general_kernel" 0/1   build the table with the kernel that takes its rules as arguments (must give the shipped one's table)
  *   "cull_strict", "cull_strict_lost", "cull_slack", "cull_keep_partial", "cull_disable", "cull_margin", "cull_lobe_k",
  *   "cull_lost_rel", "cull_lost_abs"   the pre-pass rules round 5 REPLACED (they lose lit rays on some prescriptions:

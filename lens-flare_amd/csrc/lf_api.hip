@@ -73,7 +73,8 @@ void lf_timing_end(lf_ctx* ctx, int kernel, hipEvent_t start, hipStream_t stream
 namespace {
 
 const char* kKernelNames[LFK_COUNT] = {"march", "flare_layer", "ghost_raster", "dft",
-                                       "frame_setup", "tonemap", "exchange", "scene_term", "cull_prepass", "cull_audit"};
+                                       "frame_setup", "tonemap", "exchange", "scene_term", "cull_prepass", "cull_audit",
+                                       "cull_cache_build"};
 
 // the reference's hard-coded prescription (pathtracer.cpp:541-556); literals narrowed to float
 // where the reference narrows them
@@ -296,6 +297,7 @@ lf_status lf_destroy(lf_ctx* ctx) {
   (void)lf_comm_destroy(ctx);
   if (ctx->comm_stage) (void)hipFree(ctx->comm_stage);
   free_frame_buffers(ctx);
+  lf_cull_cache_free(ctx);
   for (auto& t : ctx->timed) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
   for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
   for (int s = 0; s < 2; s++) {
@@ -1078,6 +1080,8 @@ lf_status lf_test_knob(lf_ctx* ctx, const char* name, double value) {
   if (n == "cull_force") { ctx->cull_force = iv != 0; return LF_OK; }
   if (n == "cull_weights_first") { ctx->cull_weights_first = iv != 0; return LF_OK; }
   if (n == "cull_no_prefix") { ctx->cull_no_prefix = iv != 0; return LF_OK; }
+  if (n == "cull_cache") { ctx->cull_cache_on = iv != 0; return LF_OK; }            // (0: the pre-pass marches its boxes at every build)
+  if (n == "cull_cache_max_mb") { ctx->cull_cache_max_mb = value; return LF_OK; }   // (the cached tree's byte budget, MiB)
   if (n == "scene_compact") { ctx->scene_compact = iv < 0 ? -1 : iv != 0; return LF_OK; }
   if (n == "comm_force_exchange") { ctx->comm_force_exchange = iv != 0; return LF_OK; }
   if (n == "scene_lens_strided") { ctx->scene_lens_strided = iv < 0 ? -1 : iv != 0; return LF_OK; }

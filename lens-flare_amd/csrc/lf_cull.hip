@@ -555,16 +555,43 @@ __device__ __forceinline__ float ship_extent(const ShipFoot& f, float geo_margin
                   fabsf(fmaf(f.gxx, nx, f.gxy * ny)) + fabsf(fmaf(f.gyx, nx, f.gyy * ny));
   return fminf(f.ball, fmaf(geo_margin, e, f.slack));
 }
+// the last test of a box that got through whole, the ONLY place the sun enters the pre-pass: its exit footprint (in direction
+// space) lies wholly outside the lobe.  One function for the pre-pass (footprint in registers) and the per-frame resolve of the
+// cached footprints (k_cull_resolve: the same twelve floats from memory), so that both decide every box alike, bit for bit.
+__device__ __forceinline__ bool ship_lobe_culls(const ShipFoot& f, float geo_margin, float sx, float sy, float rho) {
+  const float ex = sx - f.cx, ey = sy - f.cy;
+  const float dist = lf_sqrt(fmaf(ex, ex, ey * ey));
+  const float id = dist > 0.0f ? lf_rcp(dist) : 0.0f;
+  return dist - kShipLobeK * ship_extent(f, geo_margin, ex * id, ey * id) > rho;
+}
 
-__global__ __launch_bounds__(LF_CULL_WG, LF_CULL_WAVES) void k_cull_level(const LfLensDev* __restrict__ lens,
+// ---- the sun-independent part of the pre-pass, cached (lfk_cull_prepass) ------------------------------------------
+// Everything a box's fate depends on before the lobe test -- the lens, the frame, the blocks, the mask's grid, the pairs, the
+// rank's share -- stays the same while the sun moves.  The cache holds, per level and (path, own block, cell), one slot:
+// kSlotCulled / kSlotKept where the kernel decides the box before the lobe test, kSlotFoot + i where it reaches it (i: the
+// box's exit footprint, 12 floats, in the level's compacted array).  Children exist for every box that is not culled.
+constexpr unsigned kSlotCulled = 0u, kSlotKept = 1u, kSlotFoot = 2u;
+constexpr int kCullMaxLevels = 8;
+struct CullCacheOut {
+  unsigned* slots;         // this level's [path][own block][cell]
+  float4* foots;           // this level's footprints, 3 x float4 each
+  unsigned* foot_count;    // ... how many were appended
+  unsigned foot_cap;
+  unsigned n_mine;         // blocks this rank builds
+};
+
+// BUILD = false: the pre-pass as it ships (k_cull_level).  BUILD = true (k_cull_level_build): the same rules up to the lobe
+// test, which is replaced by "emit the box's slot and footprint"; children of kept AND undecided boxes are listed.
+template <bool BUILD>
+__device__ __forceinline__ void cull_level_body(const LfLensDev* __restrict__ lens,
                                                     const LfPairsDev* __restrict__ pairs,
                                                     const int* __restrict__ seq_table,
-                                                    const LfProgRow* __restrict__ rec_table, CullLevelArgs a,
+                                                    const LfProgRow* __restrict__ rec_table, const CullLevelArgs& a,
                                                     const unsigned* __restrict__ items,
                                                     const unsigned* __restrict__ counts, unsigned items_stride,
                                                     unsigned* __restrict__ next, unsigned* __restrict__ next_counts,
                                                     unsigned long long* __restrict__ table,
-                                                    unsigned long long* __restrict__ stats) {
+                                                    unsigned long long* __restrict__ stats, const CullCacheOut& co) {
   const int q = blockIdx.y;
   const unsigned PP = (unsigned)(a.P * a.P);
   const unsigned n_blk = (unsigned)(a.blocks_x * a.blocks_y);
@@ -720,18 +747,40 @@ __global__ __launch_bounds__(LF_CULL_WG, LF_CULL_WAVES) void k_cull_level(const 
     // the path is complete.  A box that lost samples is bounded by nothing: kept.  A whole one: where can it point?
     if (live != kAll) { keep = true; why = 1; }
   }
-  if (__ballot(!culled && !keep) != 0ull) {
-    const ShipFoot f = ship_footprint<true>(r, a.margin, 2e-5f);
-    const float ex = a.sx - f.cx, ey = a.sy - f.cy;
-    const float dist = lf_sqrt(fmaf(ex, ex, ey * ey));
-    const float id = dist > 0.0f ? lf_rcp(dist) : 0.0f;
-    if (!culled && !keep) {
-      if (dist - kShipLobeK * ship_extent(f, a.geo_margin, ex * id, ey * id) > a.rho) { culled = true; why = 6; }
-      else { keep = true; why = 3; }
+  if constexpr (BUILD) {
+    // (lanes that are not valid are `culled`)
+    const bool foot = !culled && !keep;
+    const lanemask fm = __ballot(foot);
+    unsigned slot = kSlotKept;
+    if (fm != 0ull) {
+      const ShipFoot f = ship_footprint<true>(r, a.margin, 2e-5f);
+      unsigned base = 0u;
+      if (lane == (int)__builtin_ctzll(fm)) base = atomicAdd(co.foot_count, (unsigned)__popcll(fm));
+      base = __shfl(base, (int)__builtin_ctzll(fm));
+      const unsigned at = base + (unsigned)__popcll(fm & ((1ull << lane) - 1ull));
+      if (foot && at < co.foot_cap) {
+        float4* const o = co.foots + (size_t)at * 3;
+        o[0] = make_float4(f.cx, f.cy, f.g1x, f.g1y);
+        o[1] = make_float4(f.g2x, f.g2y, f.gxx, f.gxy);
+        o[2] = make_float4(f.gyx, f.gyy, f.slack, f.ball);
+        slot = kSlotFoot + at;
+      }
     }
+    // (the slots start as kSlotCulled; a rank's blocks are rank, rank + n, ...: own index blk / n)
+    if (!culled) co.slots[((size_t)q * co.n_mine + (size_t)(blk / a.share_n)) * PP + (unsigned)cell] = slot;
+    keep = !culled;
+  } else {
+    if (__ballot(!culled && !keep) != 0ull) {
+      const ShipFoot f = ship_footprint<true>(r, a.margin, 2e-5f);
+      if (!culled && !keep) {
+        if (ship_lobe_culls(f, a.geo_margin, a.sx, a.sy, a.rho)) { culled = true; why = 6; }
+        else { keep = true; why = 3; }
+      }
+    }
+    if (stats && valid && why) atomicAdd(&stats[why], 1ull);
   }
-  if (stats && valid && why) atomicAdd(&stats[why], 1ull);
   const bool enabled = valid && keep;
+  if (BUILD && a.last) return;
   if (a.last) {
     if (valid && enabled) {
       unsigned long long* row = table + lf_cull_row_of_block(blk, a.share_n, a.share_nb) * (size_t)(a.P * a.P + 1);
@@ -765,6 +814,77 @@ __global__ __launch_bounds__(LF_CULL_WG, LF_CULL_WAVES) void k_cull_level(const 
       }
     }
   }
+}
+
+__global__ __launch_bounds__(LF_CULL_WG, LF_CULL_WAVES) void k_cull_level(const LfLensDev* __restrict__ lens,
+                                                    const LfPairsDev* __restrict__ pairs,
+                                                    const int* __restrict__ seq_table,
+                                                    const LfProgRow* __restrict__ rec_table, CullLevelArgs a,
+                                                    const unsigned* __restrict__ items,
+                                                    const unsigned* __restrict__ counts, unsigned items_stride,
+                                                    unsigned* __restrict__ next, unsigned* __restrict__ next_counts,
+                                                    unsigned long long* __restrict__ table,
+                                                    unsigned long long* __restrict__ stats) {
+  cull_level_body<false>(lens, pairs, seq_table, rec_table, a, items, counts, items_stride, next, next_counts, table, stats, CullCacheOut{});
+}
+__global__ __launch_bounds__(LF_CULL_WG, LF_CULL_WAVES) void k_cull_level_build(const LfLensDev* __restrict__ lens,
+                                                    const LfPairsDev* __restrict__ pairs,
+                                                    const int* __restrict__ seq_table,
+                                                    const LfProgRow* __restrict__ rec_table, CullLevelArgs a,
+                                                    const unsigned* __restrict__ items,
+                                                    const unsigned* __restrict__ counts, unsigned items_stride,
+                                                    unsigned* __restrict__ next, unsigned* __restrict__ next_counts,
+                                                    CullCacheOut co) {
+  cull_level_body<true>(lens, pairs, seq_table, rec_table, a, items, counts, items_stride, next, next_counts, nullptr, nullptr, co);
+}
+
+// The per-frame resolve of a cached tree: one thread = one finest cell of one own block, a wave = an 8 x 8 patch of them (its
+// lanes share their ancestors: the coarse levels' reads are broadcasts).  Per path, from the coarsest level down: a culled
+// ancestor ends the walk, a kept one goes down, an undecided one takes the pre-pass's lobe test on its stored footprint.
+// What survives to the finest level sets the path's bit: one plain store per cell, the row's summary word by one atomic
+// per wave.  No lists, no per-box atomics, nothing for the host to read.
+struct CullResolveArgs {
+  int P_final, n_levels, n_paths, patches;     // patches of 8 x 8 cells per axis of a block
+  int share_rank, share_n, share_nb;
+  unsigned n_mine, n_waves;
+  float sx, sy, rho, geo_margin;
+  const unsigned* slots[kCullMaxLevels];
+  const float4* foots[kCullMaxLevels];
+};
+__global__ __launch_bounds__(256) void k_cull_resolve(CullResolveArgs a, unsigned long long* __restrict__ table) {
+  const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);
+  if (wave >= a.n_waves) return;
+  const int lane = (int)(threadIdx.x & 63u);
+  const unsigned pp = (unsigned)(a.patches * a.patches);
+  const unsigned own = wave / pp, patch = wave % pp;
+  const int ci = (int)(patch % (unsigned)a.patches) * 8 + (lane & 7), cj = (int)(patch / (unsigned)a.patches) * 8 + (lane >> 3);
+  const bool valid = ci < a.P_final && cj < a.P_final;
+  const int blk = a.share_rank + a.share_n * (int)own;
+  unsigned long long bits = 0ull;
+  for (int q = 0; q < a.n_paths; q++) {
+    bool alive = valid;
+    for (int lv = 0; lv < a.n_levels; lv++) {
+      if (__ballot(alive) == 0ull) break;
+      const int sh = a.n_levels - 1 - lv;
+      const int Pl = a.P_final >> sh;
+      if (alive) {
+        const unsigned s = a.slots[lv][((size_t)q * a.n_mine + own) * (size_t)(Pl * Pl) + (size_t)((cj >> sh) * Pl + (ci >> sh))];
+        if (s == kSlotCulled) alive = false;
+        else if (s >= kSlotFoot) {
+          const float4* const p = a.foots[lv] + (size_t)(s - kSlotFoot) * 3;
+          const float4 v0 = p[0], v1 = p[1], v2 = p[2];
+          const ShipFoot f{v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w};
+          if (ship_lobe_culls(f, a.geo_margin, a.sx, a.sy, a.rho)) alive = false;
+        }
+      }
+    }
+    if (alive) bits |= 1ull << q;
+  }
+  unsigned long long* const row = table + lf_cull_row_of_block(blk, a.share_n, a.share_nb) * (size_t)(a.P_final * a.P_final + 1);
+  if (valid) row[cj * a.P_final + ci] = bits;
+  unsigned long long any = bits;
+  for (int o = 32; o > 0; o >>= 1) any |= __shfl_xor(any, o);
+  if (lane == 0 && any != 0ull) atomicOr(&row[a.P_final * a.P_final], any);
 }
 
 // ---- the march of the enabled paths ---------------------------------------------------------------------
@@ -1756,6 +1876,135 @@ static LfCullSlab lf_cull_slab_of(const lf_ctx* ctx, int blk_log2) {
   return slab;
 }
 
+// The ball and the dispersion slack grow with the level (a coarse box is more curved than 15 rays show); the zonotope's
+// generators are inflated by the same factor at every level: lowered one level at a time, each loses its first lit ray
+// between x 0.9 and x 1.0 (a zonotope is EXACT for the linear part of the map, the measured slack covers the rest:
+// profiles/r05_march_variants.txt)
+static float cull_level_margin(float margin, int P) {
+  return margin * (P >= 64 ? 1.0f : P >= 32 ? 1.15f : P >= 16 ? 1.4f : 2.0f);
+}
+
+void lf_cull_cache_free(lf_ctx* ctx) {
+  LfCullCache& C = ctx->cull_cache;
+  if (C.slots) (void)hipFree(C.slots);
+  for (float*& f : C.foots) { if (f) (void)hipFree(f); f = nullptr; }
+  C.slots = nullptr; C.key = 0; C.reused = false; C.n_levels = 0; C.bytes = 0;
+}
+
+// Build the cached tree for `key`: the levels of the pre-pass as lfk_cull_prepass runs them (work lists per path, their lengths
+// read back between levels -- it runs once), by the pre-pass's own kernel body with the lobe test replaced by "emit".
+// *fits = false (nothing resident): the tree exceeds the budget.
+static lf_status cull_cache_build(lf_ctx* ctx, CullLevelArgs a, const int* levels, int n_levels, size_t nblk, uint64_t key, bool* fits) {
+  LfCullCache& C = ctx->cull_cache;
+  const lf_ctx::CullRules& R = ctx->cull_rules;
+  *fits = false;
+  LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  lf_cull_cache_free(ctx);
+  const double budget = ctx->cull_cache_max_mb * 1048576.0;
+  const size_t n_mine = (nblk + (size_t)a.share_n - 1 - (size_t)a.share_rank) / (size_t)a.share_n;
+  size_t slot_entries = 0;
+  for (int lv = 0; lv < n_levels; lv++) { C.slot_off[lv] = slot_entries; slot_entries += (size_t)a.n_paths * n_mine * (size_t)levels[lv] * levels[lv]; }
+  if (n_mine == 0 || (double)slot_entries * sizeof(unsigned) > budget) return LF_OK;
+  unsigned* lists[2] = {nullptr, nullptr};
+  size_t lists_cap[2] = {0, 0};
+  unsigned* foot_count = nullptr;
+  lf_status st = LF_OK;
+  bool ok = true;
+  auto fail = [&](hipError_t e, const char* what) { st = lf_fail(ctx, LF_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); ok = false; };
+#define LF_TRY(expr) do { if (ok) { hipError_t e_ = (expr); if (e_ != hipSuccess) fail(e_, #expr); } } while (0)
+  hipEvent_t ev = lf_timing_begin(ctx, LFK_CULL_CACHE_BUILD);
+  LF_TRY(hipMalloc((void**)&C.slots, slot_entries * sizeof(unsigned)));
+  LF_TRY(hipMalloc((void**)&foot_count, kCullMaxLevels * sizeof(unsigned)));
+  LF_TRY(hipMemsetAsync(C.slots, 0, slot_entries * sizeof(unsigned), ctx->stream));
+  LF_TRY(hipMemsetAsync(foot_count, 0, kCullMaxLevels * sizeof(unsigned), ctx->stream));
+  LF_TRY(hipMemsetAsync(ctx->cull_counts, 0, 8 * kCullMaxPaths * sizeof(unsigned), ctx->stream));
+  C.bytes = slot_entries * sizeof(unsigned);
+  C.n_mine = (unsigned)n_mine;
+  unsigned max_items = 0;
+  size_t total_items = 0;
+  bool within = true;
+  int lv = 0;
+  for (; ok && lv < n_levels; lv++) {
+    a.P = levels[lv];
+    a.last = lv + 1 == n_levels ? 1 : 0;
+    a.margin = cull_level_margin(R.margin, a.P);
+    a.geo_margin = R.margin;
+    const size_t n_items = lv == 0 ? n_mine * (size_t)a.P * a.P : (size_t)max_items;
+    if (lv == 0) total_items = n_items * (size_t)a.n_paths;
+    if (n_items == 0) { lv = n_levels; break; }
+    // every box of the level may reach the lobe test -- room for all of them, or for what the budget leaves (a level that
+    // appends more does not fit); compacted to what was appended, below
+    if (total_items > 0xfffffff0ull) { within = false; break; }
+    const size_t foot_cap = (size_t)std::min((double)total_items, std::floor((budget - (double)C.bytes) / 48.0));
+    if (foot_cap == 0) { within = false; break; }
+    LF_TRY(hipMalloc((void**)&C.foots[lv], foot_cap * 48));
+    const unsigned in_stride = a.list_stride;
+    unsigned* next = nullptr;
+    unsigned out_stride = 0;
+    if (!a.last) {
+      const size_t need = n_items * 4;
+      if (need > 0x7fffffffull) { within = false; break; }
+      out_stride = (unsigned)need;
+      const size_t total = need * (size_t)a.n_paths;
+      const int slot = lv & 1;
+      if (total > lists_cap[slot]) {
+        LF_TRY(hipStreamSynchronize(ctx->stream));
+        if (lists[slot]) (void)hipFree(lists[slot]);
+        lists[slot] = nullptr; lists_cap[slot] = 0;
+        LF_TRY(hipMalloc((void**)&lists[slot], total * sizeof(unsigned)));
+        lists_cap[slot] = total;
+      }
+      next = lists[slot];
+    }
+    if (!ok) break;
+    CullLevelArgs k = a;
+    k.list_stride = a.last ? in_stride : out_stride;
+    CullCacheOut co;
+    co.slots = C.slots + C.slot_off[lv]; co.foots = (float4*)C.foots[lv]; co.foot_count = foot_count + lv;
+    co.foot_cap = (unsigned)foot_cap; co.n_mine = (unsigned)n_mine;
+    const dim3 grid((unsigned)((n_items + LF_CULL_WG - 1) / LF_CULL_WG), (unsigned)a.n_paths);
+    hipLaunchKernelGGL(k_cull_level_build, grid, dim3(LF_CULL_WG), 0, ctx->stream, ctx->lens_dev, ctx->pairs_dev,
+                       (const int*)(ctx->prog_dev + ctx->prog_seq_off), (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),
+                       k, lv == 0 ? nullptr : lists[(lv - 1) & 1], lv == 0 ? nullptr : ctx->cull_counts + (size_t)(lv - 1) * kCullMaxPaths,
+                       in_stride, next, ctx->cull_counts + (size_t)lv * kCullMaxPaths, co);
+    LF_TRY(hipGetLastError());
+    a.list_stride = out_stride;
+    unsigned cnt[kCullMaxPaths] = {};
+    unsigned n_foot = 0;
+    if (!a.last) LF_TRY(hipMemcpyAsync(cnt, ctx->cull_counts + (size_t)lv * kCullMaxPaths, sizeof(cnt), hipMemcpyDeviceToHost, ctx->stream));
+    LF_TRY(hipMemcpyAsync(&n_foot, foot_count + lv, sizeof(n_foot), hipMemcpyDeviceToHost, ctx->stream));
+    LF_TRY(hipStreamSynchronize(ctx->stream));
+    if (!ok) break;
+    if ((size_t)n_foot > foot_cap) { within = false; break; }        // beyond the budget
+    C.n_foot[lv] = n_foot;
+    // keep what was appended
+    if ((size_t)n_foot < foot_cap) {
+      float* tight = nullptr;
+      if (n_foot > 0) {
+        LF_TRY(hipMalloc((void**)&tight, (size_t)n_foot * 48));
+        LF_TRY(hipMemcpy(tight, C.foots[lv], (size_t)n_foot * 48, hipMemcpyDeviceToDevice));
+      }
+      if (ok) { (void)hipFree(C.foots[lv]); C.foots[lv] = tight; } else if (tight) (void)hipFree(tight);
+    }
+    C.bytes += (size_t)n_foot * 48;
+    max_items = 0; total_items = 0;
+    for (int q = 0; q < a.n_paths; q++) {
+      const unsigned c = std::min(cnt[q], out_stride);
+      max_items = std::max(max_items, c); total_items += c;
+    }
+  }
+#undef LF_TRY
+  lf_timing_end(ctx, LFK_CULL_CACHE_BUILD, ev);
+  for (unsigned* l : lists) if (l) (void)hipFree(l);
+  if (foot_count) (void)hipFree(foot_count);
+  if (!ok || !within) { lf_cull_cache_free(ctx); return st; }
+  C.n_levels = n_levels;
+  for (int i = 0; i < n_levels; i++) C.levels[i] = levels[i];
+  C.key = key; C.reused = false;
+  *fits = true;
+  return LF_OK;
+}
+
 lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp) {
   const LfLensDev& L = ctx->lens;
   const lf_ctx::CullRules& R = ctx->cull_rules;
@@ -1818,6 +2067,25 @@ lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp) {
     h = fnv(h, how, sizeof(how));
   }
   if (h == 0) h = 1;
+  // ... and the cached tree's key: the same with the sun taken out
+  uint64_t hk = 0xcbf29ce484222325ull;
+  {
+    CullLevelArgs ka = a;
+    ka.sx = 0.0f; ka.sy = 0.0f; ka.rho = 0.0f;
+    LfLensDev Lk = L;
+    Lk.sun_dir[0] = Lk.sun_dir[1] = Lk.sun_dir[2] = 0.0f;
+    Lk.sun_radiance[0] = Lk.sun_radiance[1] = Lk.sun_radiance[2] = 0.0f;
+    Lk.sun_inv_one_minus_cos = 0.0f;
+    Lk.sun_ss = 0.0f;
+    hk = fnv(hk, &ka, sizeof(ka));
+    hk = fnv(hk, levels, sizeof(int) * (size_t)n_levels);
+    hk = fnv(hk, &Lk, sizeof(Lk));
+    hk = fnv(hk, ctx->pairs.ij, sizeof(int) * 2 * (size_t)ctx->pairs.n);
+    hk = fnv(hk, &ctx->mask_generation, sizeof(ctx->mask_generation));
+    const int how[4] = {slab.rank, slab.n, (int)ctx->split.table, slab.own_rows_only ? 1 : 0};
+    hk = fnv(hk, how, sizeof(how));
+    if (hk == 0) hk = 1;
+  }
   const size_t nblk = (size_t)a.blocks_x * a.blocks_y;
   const size_t rows = (size_t)a.share_nb * (size_t)a.share_n;         // (= nblk unless shared: equal slabs, the last ones padded)
   const size_t row_entries = (size_t)a.P_final * a.P_final + 1;
@@ -1849,18 +2117,43 @@ lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp) {
 #ifdef LF_EXPERIMENTS
   if (std::getenv("LF_CULL_STATS")) LF_HIP(ctx, hipMalloc((void**)&stats_dev, 32 * sizeof(unsigned long long)));
 #endif
+  // The cached tree (see k_cull_resolve).  Not for a test's rules or the general kernel, nor for a selection split over two
+  // tables (their keys would alternate).  Policy: built by the first launch that sees a key -- but once a tree was dropped
+  // before any launch reused it (a host that animates focus or zoom), only for a key seen on two launches running.
+  bool cached = false;
+  if (ctx->cull_cache_on && !ctx->cull_rules_custom && R.disable == 0 && ctx->cull_chunks <= 1 && n_levels <= kCullMaxLevels) {
+    LfCullCache& C = ctx->cull_cache;
+    if (C.key == hk) { cached = true; C.reused = true; }
+    else {
+      if (C.key != 0) { C.thrash = !C.reused; LF_HIP(ctx, hipStreamSynchronize(ctx->stream)); lf_cull_cache_free(ctx); }
+      if ((hk != C.nofit_key || ctx->cull_cache_max_mb != C.nofit_mb) && (!C.thrash || C.last_key == hk)) {
+        const lf_status st = cull_cache_build(ctx, a, levels, n_levels, nblk, hk, &cached);
+        if (st != LF_OK) return st;
+        if (!cached) { C.nofit_key = hk; C.nofit_mb = ctx->cull_cache_max_mb; }
+      }
+    }
+    C.last_key = hk;
+  }
   hipEvent_t ev = lf_timing_begin(ctx, LFK_CULL);
   LF_HIP(ctx, hipMemsetAsync(ctx->cull_dev, 0, entries * sizeof(unsigned long long), ctx->stream));
   LF_HIP(ctx, hipMemsetAsync(ctx->cull_counts, 0, 8 * kCullMaxPaths * sizeof(unsigned), ctx->stream));
+  if (cached) {
+    const LfCullCache& C = ctx->cull_cache;
+    CullResolveArgs ra;
+    std::memset(&ra, 0, sizeof(ra));
+    ra.P_final = a.P_final; ra.n_levels = C.n_levels; ra.n_paths = a.n_paths; ra.patches = (a.P_final + 7) / 8;
+    ra.share_rank = a.share_rank; ra.share_n = a.share_n; ra.share_nb = a.share_nb;
+    ra.n_mine = C.n_mine; ra.n_waves = C.n_mine * (unsigned)(ra.patches * ra.patches);
+    ra.sx = a.sx; ra.sy = a.sy; ra.rho = a.rho; ra.geo_margin = R.margin;
+    for (int lv = 0; lv < C.n_levels; lv++) { ra.slots[lv] = C.slots + C.slot_off[lv]; ra.foots[lv] = (const float4*)C.foots[lv]; }
+    hipLaunchKernelGGL(k_cull_resolve, dim3((ra.n_waves + 3u) / 4u), dim3(256), 0, ctx->stream, ra, ctx->cull_dev);
+    LF_HIP(ctx, hipGetLastError());
+  }
   unsigned max_items = 0;     // of the level about to run (per path); level 0 runs every box
-  for (int lv = 0; lv < n_levels; lv++) {
+  for (int lv = 0; lv < n_levels && !cached; lv++) {
     a.P = levels[lv];
     a.last = lv + 1 == n_levels ? 1 : 0;
-    // The ball and the dispersion slack grow with the level (a coarse box is more curved than 15 rays show); the zonotope's
-    // generators are inflated by the same factor at every level: lowered one level at a time, each loses its first lit ray
-    // between x 0.9 and x 1.0 (a zonotope is EXACT for the linear part of the map, the measured slack covers the rest:
-    // profiles/r05_march_variants.txt)
-    a.margin = R.margin * (a.P >= 64 ? 1.0f : a.P >= 32 ? 1.15f : a.P >= 16 ? 1.4f : 2.0f);
+    a.margin = cull_level_margin(R.margin, a.P);
     a.geo_margin = R.margin;
     const size_t n_mine = (nblk + (size_t)a.share_n - 1 - (size_t)a.share_rank) / (size_t)a.share_n;   // blocks this rank builds
     const size_t n_items = lv == 0 ? n_mine * (size_t)a.P * a.P : (size_t)max_items;

@@ -289,6 +289,26 @@ struct LfSplit {
 // A slab of cull table rows: this context builds the rows of the blocks b with b % n == rank (nb rows, lf_cull_row_of_block)
 // -- and, own_rows_only (the frame dealt by blocks), nobody completes the others.  {0, 1, 0, false}: the whole table.
 struct LfCullSlab { int rank = 0, n = 1, nb = 0; bool own_rows_only = false; };
+// The pre-pass's sun-independent part, kept across launches (lf_cull.hip: k_cull_level_build fills it, k_cull_resolve turns it
+// into a launch's table).  Per level one slot per (path, own block, cell) and the exit footprints of the boxes whose fate the
+// sun decides.  `key`: the pre-pass's hash with the sun taken out.
+struct LfCullCache {
+  uint64_t key = 0;                  // of the resident tree (0 = none)
+  bool reused = false;               // a launch after the one that built it found it valid
+  int n_levels = 0;
+  int levels[8] = {};
+  unsigned n_mine = 0;               // own blocks
+  unsigned* slots = nullptr;         // every level's slots, one allocation
+  size_t slot_off[8] = {};           // ... where a level's begin (entries)
+  float* foots[8] = {};              // per level: n_foot x 12 floats
+  size_t n_foot[8] = {};
+  size_t bytes = 0;                  // resident: slots + footprints
+  // the policy (lfk_cull_prepass): a host that changes the key at every launch must not pay a build per frame
+  bool thrash = false;               // a tree was dropped before it was ever reused: build only a key seen twice running
+  uint64_t last_key = 0;             // the previous cacheable launch's key
+  uint64_t nofit_key = 0;            // this key's tree exceeded the budget `nofit_mb`: today's path, no second attempt
+  double nofit_mb = 0.0;
+};
 
 // ---- lens camera (round 4): the scene imaged through the prescription --------------------------
 // The primary path N-1 .. 0 of a sensor sample (the ray travels -z, against the light), one row per
@@ -334,7 +354,7 @@ constexpr int kSceneCounters = 4;
 
 // ---- timing ---------------------------------------------------------------------------------
 enum LfKernelId { LFK_MARCH = 0, LFK_FLARE_LAYER, LFK_GHOST_RASTER, LFK_DFT, LFK_FRAME_SETUP,
-                  LFK_TONEMAP, LFK_EXCHANGE, LFK_SCENE, LFK_CULL, LFK_CULL_AUDIT, LFK_COUNT };
+                  LFK_TONEMAP, LFK_EXCHANGE, LFK_SCENE, LFK_CULL, LFK_CULL_AUDIT, LFK_CULL_CACHE_BUILD, LFK_COUNT };
 
 struct LfTimedLaunch { int kernel; hipEvent_t start, stop; };
 
@@ -455,6 +475,9 @@ struct lf_ctx {
   unsigned* cull_counts = nullptr;             // [levels][kCullMaxPaths] list lengths
   int cull_m = 1;                              // table cells per axis inside one stratum
   LfCullSlab cull_resident;                    // the layout of the RESIDENT table (written by lfk_cull_prepass alone)
+  LfCullCache cull_cache;
+  bool cull_cache_on = true;                   // lf_test_knob("cull_cache")
+  double cull_cache_max_mb = 8192.0;           // lf_test_knob("cull_cache_max_mb"): the cache's byte budget (8 GiB)
   uint64_t cull_hash_pending = 0;              // of the slab lf_cull_prepare built (the host's exchange is outstanding)
   bool cull_prepare_only = false;              // (lf_cull_prepare is inside lfk_march)
   bool cull_fresh = false;                     // lf_cull_commit just completed the table: the next launch takes it even in mode 2
@@ -616,6 +639,7 @@ int lf_cull_reason_of(const lf_ctx* ctx, int G);                       // lf_cul
 int lf_cull_block_log2(const lf_ctx* ctx, int spp, int n_lambda);      // log2 of a cull block's side in pixels (-1: none applies)
 lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp);
 lf_status lfk_cull_finish(lf_ctx* ctx, uint64_t hash);
+void lf_cull_cache_free(lf_ctx* ctx);               // lf_destroy
 lf_status lfk_cull_prepare(lf_ctx* ctx, int spp);   // lf_march.hip          // the table is complete: count what it starts
 // lf_group.hip: in-place all-gather of equal slabs of u64 on the communicator's stream, ordered after what the main
 // stream has queued and before what it queues next

@@ -1404,6 +1404,7 @@ lf_status lfk_march(lf_ctx* ctx, int spp, uint64_t key) {
   bool culled = true;
   int reason = LF_CULL_APPLIED;
   const int half = (n + 1) / 2;
+  ctx->cull_chunks = 2;      // (the pre-pass keeps no cached tree for a selection split over two tables)
   for (int c = 0; c < 2 && st == LF_OK; c++) {
     LfPairsDev P;
     std::memset(&P, 0, sizeof(P));
