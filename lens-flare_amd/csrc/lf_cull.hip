@@ -898,6 +898,17 @@ struct PathTally {
   unsigned n_light = 0;   // per lane
 };
 
+// What a lit ray's contribution is multiplied by per channel c, for wavelength l: sun_radiance[c] * lambda_rgb[l][c], wave-uniform
+// and constant for a launch -- formed ONCE per workgroup (the same single float multiply) into LDS at [3 l + c], where the
+// re-march's epilogue reads it instead of through six waited scalar loads per lit (path, wavelength).  Before the kernel's
+// first barrier.
+__device__ __forceinline__ void march_channel_factors(const LfLensDev* __restrict__ lens, float* __restrict__ s_chan, int tid) {
+  if (tid < LF_MAX_LAMBDA * 3) {
+    const int l = tid / 3, c = tid - 3 * l;
+    s_chan[tid] = l < lens->n_lambda ? lens->sun_radiance[c] * lens->lambda_rgb[l][c] : 0.0f;
+  }
+}
+
 // One STARTED path q of one sensor sample per lane (start ray X, Y, s0; lanes in start_mask), every wavelength group:
 // the events of the path's own sequence, K wavelengths together, tallies, the lobe test, the weighted second march
 // (W1 = false) and the fixed-point add into the tile's LDS sums at pixel slot acc_slot.  Shared by the two culled
@@ -908,7 +919,8 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
                                                    const LfWeightRow* __restrict__ wrec_table, const float* __restrict__ mask,
                                                    const MarchArgs& a, int q, lanemask start_mask, float X, float Y,
                                                    const StartRay& s0, int lane, int acc_slot,
-                                                   unsigned long long* __restrict__ s_acc, PathTally& T) {
+                                                   unsigned long long* __restrict__ s_acc, const float* __restrict__ s_chan,
+                                                   PathTally& T) {
   const int n_lambda = lens->n_lambda, prog_recs = pairs->prog_recs;
   const int n_groups = (n_lambda + K - 1) / K;
   const float inv_stop_h = a.inv_stop_h, lobe_thr = a.lobe_thr;
@@ -1038,7 +1050,7 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
       T.n_light += contrib > 0.0f ? 1u : 0u;
 #pragma unroll
       for (int c = 0; c < 3; c++) {
-        const float v = contrib * (lens->sun_radiance[c] * lens->lambda_rgb[l][c]);
+        const float v = contrib * s_chan[l * 3 + c];
         const unsigned long long fx = (unsigned long long)(v * 68719476736.0f);
         if (fx) atomicAdd(&s_acc[acc_slot * 3 + c], fx);
       }
@@ -1079,7 +1091,8 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
                                                   const LfWeightRow* __restrict__ wrec_table, const float* __restrict__ mask,
                                                   const MarchArgs& a, unsigned long long todo, lanemask active_mask, float X, float Y,
                                                   const StartRay& s0, int lane, unsigned long long* __restrict__ s_acc,
-                                                  const int2* __restrict__ s_meta, PathTally& T) {
+                                                  const int2* __restrict__ s_meta, const float* __restrict__ s_chan,
+                                                  PathTally& T) {
   const int n_lambda = lens->n_lambda, prog_recs = pairs->prog_recs;
   const int n_groups = (n_lambda + K - 1) / K;
   const float inv_stop_h = a.inv_stop_h, lobe_thr = a.lobe_thr;
@@ -1205,14 +1218,15 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
             T.n_light += contrib > 0.0f ? 1u : 0u;
 #pragma unroll
             for (int c = 0; c < 3; c++) {
-              const float v = contrib * (lens->sun_radiance[c] * lens->lambda_rgb[l][c]);
+              const float v = contrib * s_chan[l * 3 + c];
               const unsigned long long fx = (unsigned long long)(v * 68719476736.0f);
               if (fx) atomicAdd(&s_acc[lane * 3 + c], fx);
             }
           }
         }
       }
-      if (!forked) break;                     // (the primary path: the common leg to its end, nothing after it)
+      if (!forked || left == 0ull) break;     // (the primary path: the common leg to its end, nothing after it; the group's last started path: the loop ends here
+                                              // anyway, and nobody reads the leg again -- no take-back)
       // back to the common leg where path q left it
 #pragma unroll
       for (int j = 0; j < K; j++) { r[j] = p[j]; alive[j] = palive[j]; }
@@ -1248,8 +1262,10 @@ void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restri
   __shared__ int s_next, s_nlist;
   __shared__ unsigned short s_list[kListMax];
   __shared__ int2 s_meta[MODE == 1 ? kCullMaxPaths : 1];      // per path: events << 16 | events of the common leg; first row of its sequence
+  __shared__ float s_chan[LF_MAX_LAMBDA * 3];
   const int tid = threadIdx.x;
   if (tid < 64 * 3) s_acc[tid] = 0ull;
+  march_channel_factors(lens, s_chan, tid);
   if (tid < kMarchCounters) s_cnt[tid] = 0ull;
   if (tid == 0) { s_next = 0; s_nlist = 0; }
   if (MODE == 1 && tid < pairs->n && tid < kCullMaxPaths) {
@@ -1348,7 +1364,7 @@ void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restri
         const unsigned long long todo = crow[entry];
         if (todo == 0ull) continue;
         const StartRay s0 = aim_at_pupil(X, Y, pa0, pb0, pupil_h, vz_u, geom_norm);
-        march_started_set<K, VAR>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, todo, active_mask, X, Y, s0, lane, s_acc, s_meta, T);
+        march_started_set<K, VAR>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, todo, active_mask, X, Y, s0, lane, s_acc, s_meta, s_chan, T);
         continue;
       }
       unsigned long long mine, todo;
@@ -1367,7 +1383,7 @@ void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restri
         const int q = __builtin_ctzll(left_q);
         left_q &= left_q - 1ull;
         const lanemask start_mask = active_mask & __ballot(((mine >> q) & 1ull) != 0ull);   // (all active lanes when the wave shares a cell)
-        march_started_path<K, W1, VAR>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, q, start_mask, X, Y, s0, lane, lane, s_acc, T);
+        march_started_path<K, W1, VAR>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, q, start_mask, X, Y, s0, lane, lane, s_acc, s_chan, T);
       }
     }
     __syncthreads();
@@ -1457,8 +1473,10 @@ void k_march_items(const LfLensDev* __restrict__ lens, const LfPairsDev* __restr
   __shared__ int s_next;
   __shared__ unsigned short s_items[kItemCap];
   __shared__ unsigned short s_cell[kItemCellCache * 64];      // the table cell of every (sample of the chunk, pixel): count -> fill
+  __shared__ float s_chan[LF_MAX_LAMBDA * 3];
   const int tid = threadIdx.x;
   if (tid < 64 * 3) s_acc[tid] = 0ull;
+  march_channel_factors(lens, s_chan, tid);
   if (tid < kMarchCounters) s_cnt[tid] = 0ull;
   __syncthreads();
 
@@ -1599,7 +1617,7 @@ void k_march_items(const LfLensDev* __restrict__ lens, const LfPairsDev* __restr
       const float X = -(((float)x + jx) - half_w) * pitch;
       const float Y = -(((float)y + jy) - half_h) * pitch;
       const StartRay s0 = aim_at_pupil(X, Y, fmaf(2.0f, ua, -1.0f), fmaf(2.0f, ub, -1.0f), pupil_h, vz_u, geom_norm);
-      march_started_path<K, false, VAR>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, q, __ballot(have), X, Y, s0, lane, px, s_acc, T);
+      march_started_path<K, false, VAR>(lens, pairs, seq_table, rec_table, wrec_table, mask, a, q, __ballot(have), X, Y, s0, lane, px, s_acc, s_chan, T);
     }
     __syncthreads();
     c0 += chn;

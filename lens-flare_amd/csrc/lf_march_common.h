@@ -3,6 +3,8 @@
 // launch arguments, the scalar-cache row loads and the sun's lobe.  Device code; nothing here is part of the ABI.
 #pragma once
 
+#include <cstddef>
+
 #include "lf_internal.h"
 #include "lf_march_events.h"
 
@@ -114,6 +116,14 @@ __device__ __forceinline__ LfProgHdr load_phdr(const LfProgHdr* __restrict__ bas
   return h;
 }
 
+// ONE dword of a weight record through the scalar cache: what a single wavelength's re-march reads of it -- fs[j], fo[j],
+// fi[j] (base = the group's weight records + 4 j bytes) and the record's film offset -- where load_wrec's sixteen
+// dwords would land on the registers the callers hold across the row loop
+__device__ __forceinline__ int load_wrec_dword(const void* __restrict__ base, unsigned off) {
+  typedef const char __attribute__((address_space(4))) * cptr;
+  return *(const int __attribute__((address_space(4)))*)((cptr)(base) + off);
+}
+
 // The weighted march of ONE path for wavelength j of group g (recs / wrecs: the group's records; wrec_table: group
 // 0's, where the film offsets count from) along its own sequence (n_ev dwords at w): the same arithmetic on the ray as
 // the geometry-only march, plus the Fresnel / aperture weight -- and, by the kernel's variant VAR (kVarCoat: launched
@@ -125,24 +135,31 @@ __device__ __forceinline__ void weighted_remarch(Ray& rw, const int* __restrict_
                                                  const LfWeightRow* __restrict__ wrecs,
                                                  const LfWeightRow* __restrict__ wrec_table, const float* __restrict__ mask,
                                                  float inv_stop_h, int mw, int mh) {
-  for (int left = n_ev; left > 0; --left, ++w) {
-    const unsigned se = (unsigned)*(const int __attribute__((address_space(4)))*)(w);
-    const LfProgRow wr = load_prec(recs, se & 0xffffu);
-    const LfWeightRow ww = load_wrec(wrecs, se & 0xffffu);
-    const unsigned wfl = se >> 16;
+  const char* const wj = (const char*)wrecs + 4 * j;
+  // (the sequence dword one row ahead, unconditionally: the table ends on a spare dword -- pack_program)
+  unsigned se = (unsigned)*(const int __attribute__((address_space(4)))*)(w);
+  for (int left = n_ev; left > 0; --left) {
+    const unsigned cur = se;
+    se = (unsigned)*(const int __attribute__((address_space(4)))*)(++w);
+    // the record and the row's weight scalars together, at the top of the row
+    const unsigned off = cur & 0xffffu;
+    const LfProgRow wr = load_prec(recs, off);
+    const float w_fs = __int_as_float(load_wrec_dword(wj, off + (unsigned)offsetof(LfWeightRow, fs)));
+    const float w_fo = __int_as_float(load_wrec_dword(wj, off + (unsigned)offsetof(LfWeightRow, fo)));
+    const float w_fi = __int_as_float(load_wrec_dword(wj, off + (unsigned)offsetof(LfWeightRow, fi)));
+    int w_coat = 0;
+    if (VAR & kVarCoat) w_coat = load_wrec_dword(wrecs, off + (unsigned)offsetof(LfWeightRow, coat));   // (only a film kernel reads it)
+    const unsigned wfl = cur >> 16;
     const float w_cn22 = j == 0 ? wr.cn22[0] : j == 1 ? wr.cn22[1] : wr.cn22[2];
     const float w_rn2 = j == 0 ? wr.rn2[0] : j == 1 ? wr.rn2[1] : wr.rn2[2];
     const float w_delta = j == 0 ? wr.delta[0] : j == 1 ? wr.delta[1] : wr.delta[2];
-    const float w_fs = j == 0 ? ww.fs[0] : j == 1 ? ww.fs[1] : ww.fs[2];
-    const float w_fo = j == 0 ? ww.fo[0] : j == 1 ? ww.fo[1] : ww.fo[2];
-    const float w_fi = j == 0 ? ww.fi[0] : j == 1 ? ww.fi[1] : ww.fi[2];
     if (wfl & LF_EV_STOP) {
       (void)stop_event_var<true, VAR>(rw, wr.dzv, wr.h2, inv_stop_h, mask, mw, mh);
     } else {
       lanemask geom_ok;
       (void)surface_event<true>(rw, wr.dzv, wr.curv, wr.ch, wr.c2, wr.sc, w_cn22, w_rn2, w_delta, wr.h2,
                                 (wfl & LF_EV_REFLECT) != 0, (wfl & LF_EV_FLAT) != 0, wr.sgn, geom_ok, w_fs, w_fo, w_fi,
-                                CoatSel<VAR>{wrec_table, ww.coat, j});
+                                CoatSel<VAR>{wrec_table, w_coat, j});
     }
   }
 }
