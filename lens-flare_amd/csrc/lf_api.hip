@@ -185,7 +185,7 @@ lf_status derive_stop_mask(lf_ctx* ctx) {
   const float* texels = ctx->mask_host.data();
   const int grow2 = ctx->mask_filter == LF_MASK_BILINEAR ? 1 : 0;   // half texels the open footprint grows by
   a.open_radius = mask_open_radius(texels, width, height, grow2);
-  // occupancy of the stop mask for the march's cull pre-pass (lf_cull.hip): which of kCullOcc x kCullOcc cells
+  // occupancy of the stop mask for the march's cull pre-pass (lf_cull_prepass.hip): which of kCullOcc x kCullOcc cells
   // of the mask holds a texel > 0 (a texel belongs to every cell it touches; in half-texel units under the filter)
   for (int r = 0; r < kCullOcc; r++) ctx->cull_occ[r] = 0u;
   const long long w2 = 2ll * width, h2 = 2ll * height;
@@ -309,7 +309,7 @@ lf_status lf_destroy(lf_ctx* ctx) {
                   ctx->prog_dev, ctx->sun_lights_dev,
                   ctx->scene_dev.nodes, ctx->scene_dev.prims, ctx->scene_dev.normals, ctx->scene_dev.materials,
                   ctx->scene_dev.lights, ctx->env_block, ctx->probe_dev, ctx->scene_counters_dev,
-                  ctx->primary_dev, ctx->cull_dev, ctx->cull_list[0], ctx->cull_list[1], ctx->cull_counts, ctx->cull_popc_dev,
+                  ctx->primary_dev, ctx->cull_dev, ctx->cull_lists.list[0], ctx->cull_lists.list[1], ctx->cull_counts, ctx->cull_popc_dev,
                   ctx->tail_acc, ctx->tail_done};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);

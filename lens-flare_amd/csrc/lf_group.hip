@@ -424,7 +424,7 @@ lf_status lf_comm_gather_async(lf_ctx* ctx, int which) {
   return LF_OK;
 }
 
-// The cull pre-pass shared between the ranks (lf_cull.hip): every rank has built the slab of table rows that is its
+// The cull pre-pass shared between the ranks (lf_cull_prepass.hip): every rank has built the slab of table rows that is its
 // own; ONE in-place all-gather of equal slabs completes the table everywhere.  On the communicator's stream -- the only
 // stream RCCL calls of this context are ever queued on, so that every rank issues them in one order (the previous
 // frame's exchange, then this) -- after what the main stream has queued (the pre-pass), and the main stream goes on

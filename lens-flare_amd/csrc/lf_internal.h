@@ -219,7 +219,7 @@ void lf_coat_constants(float n_in, float m, float n_out, float thickness_nm, flo
 //                  tallied per logical path, exactly as if each had been marched on its own)
 enum { LF_EV_REST1 = 8, LF_EV_SAVE0 = 0x10, LF_EV_SAVE1 = 0x20, LF_EV_END = 0x40, LF_EV_REST0 = 0x80 };
 
-// ---- path culling (round 5; lf_cull.hip) ------------------------------------------------------------
+// ---- path culling (round 5; lf_cull_prepass.hip builds the table, lf_cull.hip marches what it starts) ----------
 // Which paths can carry light from the sun to which part of the sensor through which part of the pupil: for
 // every block of 64 x 64 sensor pixels and every cell of a P x P grid over the pupil square (P = G * m: m x m
 // cells inside each of the march's G x G strata -- a wave aims all its lanes at ONE sub-cell of its stratum, so
@@ -286,10 +286,13 @@ struct LfSplit {
   LfSplit with_deal(Deal d, int r, int k) const { LfSplit s = *this; s.deal = d; s.rank = r; s.n = k; return s; }
   LfSplit with_table(Table t, int r = 0, int k = 1) const { LfSplit s = *this; s.table = t; s.table_rank = r; s.table_n = k; return s; }
 };
+// The work lists of the pre-pass's levels (lf_cull_prepass.hip cull_run_levels): level lv writes list[lv & 1], per path
+// list_stride entries, and the next level reads it.  Grown on demand; cap in entries.
+struct LfCullLists { unsigned* list[2] = {nullptr, nullptr}; size_t cap[2] = {0, 0}; };
 // A slab of cull table rows: this context builds the rows of the blocks b with b % n == rank (nb rows, lf_cull_row_of_block)
 // -- and, own_rows_only (the frame dealt by blocks), nobody completes the others.  {0, 1, 0, false}: the whole table.
 struct LfCullSlab { int rank = 0, n = 1, nb = 0; bool own_rows_only = false; };
-// The pre-pass's sun-independent part, kept across launches (lf_cull.hip: k_cull_level_build fills it, k_cull_resolve turns it
+// The pre-pass's sun-independent part, kept across launches (lf_cull_prepass.hip: k_cull_level_build fills it, k_cull_resolve turns it
 // into a launch's table).  Per level one slot per (path, own block, cell) and the exit footprints of the boxes whose fate the
 // sun decides.  `key`: the pre-pass's hash with the sun taken out.
 struct LfCullCache {
@@ -465,13 +468,12 @@ struct lf_ctx {
   int march_tail_tiles = -1, march_tail_groups = -1;   // lf_test_knob: the tail's size (-1: one round of resident workgroups) / split
   unsigned char* prog_dev = nullptr;           // the packed program: headers, then records (lf_march.hip pack_program)
   size_t prog_cap = 0, prog_rec_off = 0, prog_wrec_off = 0, prog_seq_off = 0;   // bytes; offsets of the records / weight records / pair sequences
-  // path culling (lf_cull.hip): 0 = off (k_march walks every path of every sample), 1 = on, the table is reused
+  // path culling (lf_cull_prepass.hip, lf_cull.hip): 0 = off (k_march walks every path of every sample), 1 = on, the table is reused
   // while its inputs (lens, pairs, sun, frame, pupil disc, mask, strata) are unchanged, 2 = on, rebuilt at every launch
   int march_cull = 1;
   unsigned long long* cull_dev = nullptr;
   size_t cull_cap = 0;                         // entries allocated
-  unsigned* cull_list[2] = {nullptr, nullptr}; // work lists of the pre-pass levels (per path: list_stride entries)
-  size_t cull_list_cap[2] = {0, 0};
+  LfCullLists cull_lists;                      // work lists of the pre-pass levels, kept between launches
   unsigned* cull_counts = nullptr;             // [levels][kCullMaxPaths] list lengths
   int cull_m = 1;                              // table cells per axis inside one stratum
   LfCullSlab cull_resident;                    // the layout of the RESIDENT table (written by lfk_cull_prepass alone)
@@ -481,7 +483,7 @@ struct lf_ctx {
   uint64_t cull_hash_pending = 0;              // of the slab lf_cull_prepare built (the host's exchange is outstanding)
   bool cull_prepare_only = false;              // (lf_cull_prepare is inside lfk_march)
   bool cull_fresh = false;                     // lf_cull_commit just completed the table: the next launch takes it even in mode 2
-  unsigned long long* cull_popc_dev = nullptr; // one u64: set bits of the table (k_cull_popcount)
+  unsigned long long* cull_popc_dev = nullptr; // four u64: set bits of the table (k_cull_popcount), then {rays, lit} of its audit
   double cull_started_fraction = 0.0;          // of all (block, cell, path) combinations, what the resident table starts
   // Above this the culled march loses to the path tree: it marches every started path on its own and with its
   // weight, the tree shares legs and lets rays die early (measured crossover on the 1080p frame: a sun of 0.2 rad
@@ -490,7 +492,7 @@ struct lf_ctx {
   double cull_max_fraction = 0.10;             // + 1.6 / paths: see lfk_march
   uint64_t cull_hash = 0;                      // of the inputs the resident table was built from (0 = none)
   int cull_bx = 0, cull_by = 0, cull_cells = 0, cull_G = 0, cull_P = 0, cull_blk_log2 = 6;
-  // The pre-pass's rules.  What ships is ONE set (lf_cull.hip k_cull_level, constants in the kernel); a test may install
+  // The pre-pass's rules.  What ships is ONE set (lf_cull_prepass.hip k_cull_level, constants in the kernel); a test may install
   // another through lf_test_knob ("cull_strict", ...: the rules round 5 replaced, kept to show what the audit is for) --
   // the table is then built by k_cull_level_general, which reads them from here.
   struct CullRules {
@@ -507,9 +509,8 @@ struct lf_ctx {
   int scene_lens_strided = -1;                 // lf_test_knob("scene_lens_strided"): k_scene_lens's wave tile: -1 by the tree's size, 0 / 1
   bool bvh_median = false;                     // lf_test_knob("bvh_median"): the round-2 median-split tree (A/B of the SAH tree)
   int bvh_leaf_max = 2;                        // lf_test_knob("bvh_leaf"): primitives per leaf at most (1 .. 4)
-  // the audit of what the table drops (lf_cull.hip k_cull_audit): rays per dropped (block, cell, path), 0 = off
+  // the audit of what the table drops (lf_cull_prepass.hip k_cull_audit): rays per dropped (block, cell, path), 0 = off
   int cull_audit_density = 1;
-  unsigned long long* cull_audit_dev = nullptr;   // {rays, lit} of the table being completed
   unsigned long long cull_audit_rays = 0, cull_audit_lit = 0;   // since lf_reset_counters
   int cull_audit_tripped = 0;                  // launches since lf_reset_counters whose table an audit ray refuted
   uint64_t cull_bad_hash = 0;                  // the resident table was refuted: its launches march everything
@@ -632,19 +633,21 @@ lf_status lfk_native_sqrt(lf_ctx* ctx, const float* d_x, float* d_y, size_t n);
 lf_status lfk_native_rcp(lf_ctx* ctx, const float* d_x, float* d_y, size_t n);
 void lf_apply_pupil_target(lf_ctx* ctx);
 int lf_march_fix_bits(const LfLensDev& L, int n_paths, int spp);
-// lf_cull.hip (a = the launch's arguments as lfk_march set them up: lf_march_common.h)
-namespace lfm { struct MarchArgs; }
+// lf_cull_prepass.hip: the cull table
 bool lf_cull_applies(const lf_ctx* ctx, int G);
 int lf_cull_reason_of(const lf_ctx* ctx, int G);                       // lf_cull_reason: LF_CULL_APPLIED or why not
 int lf_cull_block_log2(const lf_ctx* ctx, int spp, int n_lambda);      // log2 of a cull block's side in pixels (-1: none applies)
 lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp);
-lf_status lfk_cull_finish(lf_ctx* ctx, uint64_t hash);
+lf_status lfk_cull_finish(lf_ctx* ctx, uint64_t hash);                 // the table is complete: count what it starts, audit it
 void lf_cull_cache_free(lf_ctx* ctx);               // lf_destroy
-lf_status lfk_cull_prepare(lf_ctx* ctx, int spp);   // lf_march.hip          // the table is complete: count what it starts
+// lf_cull.hip: the march of what the table starts (a = the launch's arguments as lfk_march set them up: lf_march_common.h)
+namespace lfm { struct MarchArgs; }
+lf_status lfk_march_culled(lf_ctx* ctx, const lfm::MarchArgs& a, size_t blocks, size_t dyn_lds);
+// lf_march.hip
+lf_status lfk_cull_prepare(lf_ctx* ctx, int spp);
 // lf_group.hip: in-place all-gather of equal slabs of u64 on the communicator's stream, ordered after what the main
 // stream has queued and before what it queues next
 lf_status lf_comm_allgather_u64_inplace(lf_ctx* ctx, unsigned long long* base, size_t count_per_rank);
-lf_status lfk_march_culled(lf_ctx* ctx, const lfm::MarchArgs& a, size_t blocks, size_t dyn_lds);
 void lf_derive_lens(lf_ctx* ctx, int n, int stop, int n_lambda, const float* radius,
                     const float* thickness, const float* ior, const float* semi_ap,
                     float sensor_w_mm);

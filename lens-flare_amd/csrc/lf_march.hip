@@ -799,7 +799,7 @@ void lf_derive_lens(lf_ctx* ctx, int n, int stop, int n_lambda, const float* rad
     L.n_start[l] = n_before;   // the medium between the last interface and the sensor
   }
   // do all glasses disperse the same way along the wavelength columns?  (the cull's pre-pass brackets the spectrum by
-  // its first and last column: lf_cull.hip; a table with a column out of order marches everything instead)
+  // its first and last column: lf_cull_prepass.hip; a table with a column out of order marches everything instead)
   ctx->lens_lambda_monotonic = true;
   {
     int way = 0;
@@ -1332,7 +1332,7 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
                        std::ldexp(1.0, -fix_shift));
     LF_HIP(ctx, hipGetLastError());
   }
-  // the paths a pre-pass found able to reach the light (lf_cull.hip) -- or every path of every sample
+  // the paths a pre-pass found able to reach the light (lf_cull_prepass.hip, lf_cull.hip) -- or every path of every sample
   ctx->cull_reason = lf_cull_reason_of(ctx, a.G);
   ctx->last_march_culled = ctx->cull_reason == LF_CULL_APPLIED;
   if (ctx->last_march_culled) {

@@ -402,7 +402,7 @@ void geo_lens_samples(const geo_lens* L, int W, int H, int ns, const uint32_t ke
   }
 }
 
-/* The device's path culling (lens-flare_amd/csrc/lf_cull.hip, lf_get_cull_table): table[block][cell] = mask of the
+/* The device's path culling (lens-flare_amd/csrc/lf_cull_prepass.hip, lf_get_cull_table): table[block][cell] = mask of the
  * paths the device STARTS for sample cell `cell` (its pupil stratum s < G*G, else entry `cells`) of the pixels of
  * sensor block (x / block_px, y / block_px), block_px = 16, 32, 64 or 128.  With a table installed geo_trace still marches EVERY path -- its pixels are the
  * full enumeration's, so that equality with the device's pixels proves that nothing the device skipped could

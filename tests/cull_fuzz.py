@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Randomised search for a frame on which the culled march differs from the full enumeration.
 
-The cull pre-pass (lens-flare_amd/csrc/lf_cull.hip) drops (sensor block, pupil cell, path) boxes on the evidence of 15
+The cull pre-pass (lens-flare_amd/csrc/lf_cull_prepass.hip) drops (sensor block, pupil cell, path) boxes on the evidence of 15
 rays per box; its margins were set by comparing with the full enumeration on the frames of profiles/cull_check.py and
 cull_block_size.py.  This script draws frames those scans did not: random suns over the field, lobe widths from 0.17 to
 9 degrees, the shipped masks and synthetic ones (rings, slits, polygons, speckle), refocused / scaled / bent

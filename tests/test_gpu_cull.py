@@ -1,5 +1,5 @@
-"""Path culling of the geometric march (lens-flare_amd/csrc/lf_cull.hip, round 5; no reference counterpart -- the
-reference draws 13 fixed pairs per channel as quads, src/pathtracer/pathtracer.cpp:735-762).  lf_trace_ghosts starts
+"""Path culling of the geometric march (lens-flare_amd/csrc/lf_cull_prepass.hip and lf_cull.hip, round 5; no reference
+counterpart -- the reference draws 13 fixed pairs per channel as quads, src/pathtracer/pathtracer.cpp:735-762).  lf_trace_ghosts starts
 only the paths a pre-pass found able to carry light from the sun to a block of the sensor through a cell of the
 pupil.  What must hold, and is held here:
 

@@ -1,5 +1,5 @@
-"""The cull pre-pass's cached tree (lens-flare_amd/csrc/lf_cull.hip: k_cull_level_build, k_cull_resolve; no reference
-counterpart).  Everything the pre-pass decides before a box's last test is independent of the sun; a context keeps it --
+"""The cull pre-pass's cached tree (lens-flare_amd/csrc/lf_cull_prepass.hip: k_cull_level_build, k_cull_resolve; no
+reference counterpart).  Everything the pre-pass decides before a box's last test is independent of the sun; a context keeps it --
 per level a slot per (path, own block, cell) and the exit footprints of the undecided boxes -- and a launch with a new sun
 resolves its table from that in one pass.  What must hold, and is held here:
 
@@ -226,6 +226,36 @@ def test_fallbacks(pkg, lf):
         lf.test_knob("cull_general_kernel", 0)
     t, f = _table(lf, spp, True)
     assert np.array_equal(t, ref) and f == fref and _builds(lf) == 1
+
+
+def test_a_budget_for_the_slots_but_not_the_footprints(pkg, lf):
+    """a build that has STARTED gives up: the budget admits the slots of every level and some 200 footprints, the first level
+    appends about 1e6 (the kernel counts them all and writes those below its capacity).  The launch takes the uncached
+    pre-pass; the key is remembered as one that does not fit under this budget, and built under a larger one."""
+    W, H, spp = 400, 224, 16
+    lens, _ = _lens(pkg)
+    _setup(pkg, lf, W, H)
+    ref, fref = _table(lf, spp, False)
+    info = lf.cull_info()
+    glass = lens["n"] - 1                                    # all pairs of the interfaces that are not the stop, + the primary path
+    paths = 1 + glass * (glass - 1) // 2
+    levels = [info["P"]]
+    while levels[0] % 2 == 0 and levels[0] // 2 >= 8:
+        levels.insert(0, levels[0] // 2)
+    assert len(levels) == 2 and info["block_px"] == 16
+    slots_mb = 4.0 * paths * info["blocks_x"] * info["blocks_y"] * sum(P * P for P in levels) / 2.0 ** 20
+    lf.test_knob("cull_cache_max_mb", slots_mb + 0.01)
+    t, f = _table(lf, spp, True)
+    n1 = _builds(lf)
+    print(f"slots {slots_mb:.3f} MiB, {paths} paths, levels {levels}: cull_cache_build events after the first launch {n1}")
+    assert np.array_equal(t, ref) and f == fref
+    assert n1 == 1                                           # the build that began and gave up is timed
+    t, f = _table(lf, spp, True)                             # the same key and budget: no second attempt
+    assert np.array_equal(t, ref) and f == fref and _builds(lf) == n1
+    lf.test_knob("cull_cache_max_mb", 8192)
+    for _ in range(2):                                       # built once, then reused
+        t, f = _table(lf, spp, True)
+        assert np.array_equal(t, ref) and f == fref and _builds(lf) == n1 + 1
 
 
 def test_a_key_that_changes_at_every_launch_is_not_rebuilt(pkg, lf):
