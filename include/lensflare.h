@@ -119,8 +119,9 @@ lf_status lf_get_aperture_stats(lf_ctx* ctx, lf_aperture_slot slot, lf_aperture_
  * The lit set therefore grows by half a texel around the open region (it contains the nearest filter's); the cull
  * pre-pass, the audit and lf_aim_at_exit_pupil's open radius follow it.  A setting of the context: it survives
  * lf_set_aperture, lf_set_lens and lf_set_frame.  It does NOT affect the starburst DFT, the LF_APERTURE_GHOST slot
- * or lf_get_aperture_stats, which keep reading the texels as they are.  The CPU oracles (oracle/) do not follow
- * filtered frames, as they do not follow coated ones.  Only the weighted re-march of a lit path and the lens
+ * or lf_get_aperture_stats, which keep reading the texels as they are.  Of the CPU oracles (oracle/) the float64 tracer follows
+ * filtered frames and coated ones (lfo.g64_set_mask_filter, lfo.g64_set_films: tests/test_gpu_lens_camera_variants.py
+ * holds the lens camera to it); the float32 bit-exact oracle follows neither.  Only the weighted re-march of a lit path and the lens
  * camera's primary path pay for the four loads: the bench frame (c3) takes 44.6 ms under LF_MASK_BILINEAR against
  * 43.6 ms (x 1.023, profiles/mask_filter_cost.json); a context under LF_MASK_NEAREST runs the kernels it always ran.
  * Other values of filter: LF_ERR_INVALID. */

@@ -28,8 +28,16 @@
  * them, but the ray is marked fragile, followed as if every fragile decision had passed, and the
  * contribution it then could make is summed per pixel in `frag`.  A faithful float32 evaluation
  * then satisfies  |pixel32 - pixel64| <= tol * pixel64 + frag  with tol far below 1e-4.
+ *
+ * Films and the bilinear stop (lf_set_lens_coatings, lf_set_mask_filter): process-global settings, off by
+ * default (g64_set_films, g64_set_mask_filter) -- with neither set every result is bit for bit what it was
+ * before they existed.  A film changes the reflectance of its interface (Airy's single-film formula in complex
+ * arithmetic, written from the textbook below), never the geometry.  Under the filter the stop's weight is
+ * continuous across texel edges, so cause bit 2 is not raised; a ray carries a SLOPE ALLOWANCE instead: how
+ * far a move of eps_mm at the stop can change its weight (stop_bilinear), added into `frag`.
  */
 #define _GNU_SOURCE
+#include <complex.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdlib.h>
@@ -104,8 +112,48 @@ typedef struct {
   int fragile;
   int dead;      /* 0 alive, else cause: 1 mask/stop, 2 aperture/miss, 3 total reflection */
   int cause;     /* why fragile, bits: 1 the rim of a clear aperture / of the stop's housing, 2 a mask texel's edge,
-                    4 the critical angle, 8 a grazing miss of a sphere */
+                    4 the critical angle, 8 a grazing miss of a sphere, 16 (filter) the edge of the open footprints */
+  double slope;  /* (filter) how much a move of eps_mm at the stop can change the weight, first order */
 } g64_ray;
+
+/* single-layer films (lf_set_lens_coatings): float values held in doubles; n_surf == 0: none */
+static int g64_film_n = 0;
+static double g64_film_lambda[G64_MAX_LAMBDA], g64_film_d[G64_MAX_SURF], g64_film_m[G64_MAX_LAMBDA][G64_MAX_SURF];
+/* index: n_lambda rows of n_surf film indices; thickness_nm[k] == 0: interface k is bare */
+void g64_set_films(int n_surf, int n_lambda, const double* lambda_nm, const double* thickness_nm, const double* index) {
+  g64_film_n = 0;
+  if (n_surf <= 0 || n_surf > G64_MAX_SURF || n_lambda <= 0 || n_lambda > G64_MAX_LAMBDA) return;
+  for (int l = 0; l < n_lambda; l++) {
+    g64_film_lambda[l] = lambda_nm[l];
+    for (int k = 0; k < n_surf; k++) g64_film_m[l][k] = index[l * n_surf + k];
+  }
+  for (int k = 0; k < n_surf; k++) g64_film_d[k] = thickness_nm[k];
+  g64_film_n = n_surf;
+}
+/* how the stop's mask is read (lf_set_mask_filter): 0 the nearest texel, 1 bilinear */
+static int g64_filter = 0;
+void g64_set_mask_filter(int filter) { g64_filter = filter != 0; }
+
+/* Airy's reflectance of one homogeneous film (index m, thickness d) between n1 (the ray arrives in it, at
+ * cos_i) and n2, for light of vacuum wavelength lambda (d and lambda in the same unit): per polarisation the
+ * two faces' Fresnel amplitudes r01, r12 and the round trip's phase 2 beta = 4 pi m d cos(theta_m) / lambda,
+ *   r = (r01 + r12 e^{2 i beta}) / (1 + r01 r12 e^{2 i beta}),   R = (|r_s|^2 + |r_p|^2) / 2
+ * (Born & Wolf, Principles of Optics, section 1.6.4; Hecht, Optics, section 9.7).  Not totally reflecting. */
+static double film_reflectance(double n1, double m, double n2, double d, double lambda, double cos_i) {
+  const double sin_i = sqrt(fmax(0.0, 1.0 - cos_i * cos_i));
+  const double sin_m = n1 * sin_i / m, sin_t = n1 * sin_i / n2;      /* Snell, face by face */
+  const double complex cos_m = csqrt(1.0 - sin_m * sin_m);            /* (evanescent in the film: imaginary) */
+  const double cos_t = sqrt(fmax(0.0, 1.0 - sin_t * sin_t));
+  const double complex round_trip = cexp(I * (4.0 * M_PI * m * d / lambda) * cos_m);
+  const double complex s01 = (n1 * cos_i - m * cos_m) / (n1 * cos_i + m * cos_m);
+  const double complex s12 = (m * cos_m - n2 * cos_t) / (m * cos_m + n2 * cos_t);
+  const double complex p01 = (m * cos_i - n1 * cos_m) / (m * cos_i + n1 * cos_m);
+  const double complex p12 = (n2 * cos_m - m * cos_t) / (n2 * cos_m + m * cos_t);
+  const double complex rs = (s01 + s12 * round_trip) / (1.0 + s01 * s12 * round_trip);
+  const double complex rp = (p01 + p12 * round_trip) / (1.0 + p01 * p12 * round_trip);
+  const double Rs = creal(rs * conj(rs)), Rp = creal(rp * conj(rp));
+  return 0.5 * (Rs + Rp);
+}
 
 /* one spherical (or flat) glass interface: refraction or mirror reflection */
 static void glass(const g64_lens* L, const g64_system* S, int lam, int k, int mirror, g64_ray* r) {
@@ -156,10 +204,13 @@ static void glass(const g64_lens* L, const g64_system* S, int lam, int k, int mi
     const double rs = (n1 * cos_i - n2 * cos_t) / (n1 * cos_i + n2 * cos_t);
     const double rp = (n2 * cos_i - n1 * cos_t) / (n2 * cos_i + n1 * cos_t);
     reflectance = 0.5 * (rs * rs + rp * rp);
+    if (k < g64_film_n && g64_film_d[k] > 0.0)
+      reflectance = film_reflectance(n1, g64_film_m[lam][k], n2, g64_film_d[k], g64_film_lambda[lam], cos_i);
   }
   if (mirror) {
     r->w *= reflectance;
     r->w_pot *= reflectance;
+    r->slope *= reflectance;
     r->d = add(r->d, scale(n, 2.0 * cos_i));
   } else {
     if (tir) {
@@ -170,14 +221,74 @@ static void glass(const g64_lens* L, const g64_system* S, int lam, int k, int mi
     }
     r->w *= 1.0 - reflectance;
     r->w_pot *= tir ? 1.0 : 1.0 - reflectance;
+    r->slope *= tir ? 1.0 : 1.0 - reflectance;
     r->d = normalise(add(scale(r->d, eta), scale(n, eta * cos_i - cos_t)));
   }
+  r->o = hit;
+}
+
+/* one cell of the bilinear mask ("Mask filter"): the four texels around grid point
+ * (i0, j0) .. (i0 + 1, j0 + 1) -- texel centres at i + 1/2, indices clamped, negative texels count as 0 -- at
+ * the fractions (fx, fy): the value, its partial derivatives per texel, and whether any of the four is open */
+static int bilinear_cell(const float* mask, int mw, int mh, int i0, int j0, double fx, double fy, double* a,
+                         double* da_du, double* da_dv) {
+  const int xa = i0 < 0 ? 0 : i0 > mw - 1 ? mw - 1 : i0, xb = i0 + 1 < 0 ? 0 : i0 + 1 > mw - 1 ? mw - 1 : i0 + 1;
+  const int ya = j0 < 0 ? 0 : j0 > mh - 1 ? mh - 1 : j0, yb = j0 + 1 < 0 ? 0 : j0 + 1 > mh - 1 ? mh - 1 : j0 + 1;
+  const double t00 = fmax(mask[ya * mw + xa], 0.0), t10 = fmax(mask[ya * mw + xb], 0.0);
+  const double t01 = fmax(mask[yb * mw + xa], 0.0), t11 = fmax(mask[yb * mw + xb], 0.0);
+  *a = (1.0 - fy) * ((1.0 - fx) * t00 + fx * t10) + fy * ((1.0 - fx) * t01 + fx * t11);
+  *da_du = (1.0 - fy) * (t10 - t00) + fy * (t11 - t01);
+  *da_dv = (1.0 - fx) * (t01 - t00) + fx * (t11 - t10);
+  return t00 > 0.0 || t10 > 0.0 || t01 > 0.0 || t11 > 0.0;
+}
+
+/* the stop under the bilinear filter.  The weight is continuous in the hit point, so no texel edge is a
+ * decision; what float32's position error (eps_mm, in texels: delta) can do is move the weight along its slope.
+ * The ray's allowance grows by  (the weight it arrives with) x (|da/dfu| delta_u + |da/dfv| delta_v),  the
+ * derivatives those of the cell the ray is in -- and, within delta of a cell's border, the larger of both
+ * sides', as the bilinear's slope jumps there.  Whether the ray is ALIVE (any of the four texels open) is
+ * still a decision: within delta of a border beyond which that changes the ray is fragile (bit 16); its weight
+ * there is within the allowance of 0, so following it costs next to nothing. */
+static void stop_bilinear(const g64_lens* L, const g64_system* S, int k, const float* mask, int mw, int mh,
+                          g64_ray* r) {
+  const double t = (S->vertex_z[k] - r->o.z) / r->d.z;
+  const vec hit = add(r->o, scale(r->d, t));
+  const double h = L->semi_ap[k];
+  const double rho = sqrt(hit.x * hit.x + hit.y * hit.y);
+  if (fabs(rho - h) < L->eps_mm) { r->fragile = 1; r->cause |= 1; }
+  const int outside = rho > h;
+  const double gx = (hit.x / h + 1.0) * (0.5 * mw) - 0.5, gy = (hit.y / h + 1.0) * (0.5 * mh) - 0.5;
+  const double i0 = floor(gx), j0 = floor(gy), fx = gx - i0, fy = gy - j0;
+  const double delta_u = L->eps_mm / h * 0.5 * mw, delta_v = L->eps_mm / h * 0.5 * mh;
+  double a, gu, gv;
+  const int open = bilinear_cell(mask, mw, mh, (int)i0, (int)j0, fx, fy, &a, &gu, &gv);
+  gu = fabs(gu); gv = fabs(gv);
+  for (int sy = -1; sy <= 1; sy++)
+    for (int sx = -1; sx <= 1; sx++) {
+      if (!sx && !sy) continue;
+      if ((sx < 0 && fx > delta_u) || (sx > 0 && 1.0 - fx > delta_u)) continue;
+      if ((sy < 0 && fy > delta_v) || (sy > 0 && 1.0 - fy > delta_v)) continue;
+      double b, bu, bv;
+      if (bilinear_cell(mask, mw, mh, (int)i0 + sx, (int)j0 + sy, fx - sx, fy - sy, &b, &bu, &bv) != open) {
+        r->fragile = 1; r->cause |= 16;
+      }
+      gu = fmax(gu, fabs(bu)); gv = fmax(gv, fabs(bv));
+    }
+  if (outside || !open) {
+    if (!r->dead) r->dead = 1;
+    r->w = 0.0;
+    if (!r->fragile) return;
+  }
+  r->slope = r->slope * a + r->w_pot * (gu * delta_u + gv * delta_v);
+  r->w *= a;
+  r->w_pot *= a;
   r->o = hit;
 }
 
 /* the stop: a plane with a round housing and the aperture mask (nearest texel) */
 static void stop_plane(const g64_lens* L, const g64_system* S, int k, const float* mask, int mw, int mh,
                        g64_ray* r) {
+  if (g64_filter) { stop_bilinear(L, S, k, mask, mw, mh, r); return; }
   const double t = (S->vertex_z[k] - r->o.z) / r->d.z;
   const vec hit = add(r->o, scale(r->d, t));
   const double h = L->semi_ap[k];
@@ -285,6 +396,19 @@ int g64_trace_ray_ex(const g64_lens* L, int lam, int i, int j, double p[3], doub
   return r.dead;
 }
 
+/* ... and the slope allowance of a ray that crossed a filtered stop: out = {fragile, potential weight, allowance} */
+int g64_trace_ray_slope(const g64_lens* L, int lam, int i, int j, double p[3], double d[3], double* w,
+                        const float* mask, int mw, int mh, int* n_events, double out[3]) {
+  g64_system S;
+  lay_out(L, &S);
+  g64_ray r = {V(p[0], p[1], p[2]), V(d[0], d[1], d[2]), *w, *w, 0, 0};
+  const int ev = follow(L, &S, lam, i, j, mask, mw, mh, &r);
+  p[0] = r.o.x; p[1] = r.o.y; p[2] = r.o.z; d[0] = r.d.x; d[1] = r.d.y; d[2] = r.d.z; *w = r.w;
+  if (n_events) *n_events = ev;
+  out[0] = (double)r.fragile; out[1] = r.w_pot; out[2] = r.slope;
+  return r.dead;
+}
+
 double g64_sensor_z(const g64_lens* L) {
   g64_system S;
   lay_out(L, &S);
@@ -304,6 +428,25 @@ static int g64_xs = 3;   /* the library's default: columns 8 apart */
 void g64_set_tile_stride_log2(int xs) { g64_xs = xs; }
 static int g64_x0 = 0, g64_x1 = 1 << 30;
 void g64_set_x_window(int x0, int x1) { g64_x0 = x0; g64_x1 = x1; }
+
+/* the ray from the sensor point (X, Y) mm to the point (a, b) of the pupil square [-1, 1]^2, mapped to the
+ * disc the samples aim at; returns the start weight: the disc's solid angle x cos^4 */
+static double aim(const g64_lens* L, const g64_system* S, double X, double Y, double a, double b, vec* origin, vec* dir) {
+  /* concentric square -> disc (Shirley & Chiu) */
+  double qx = 0.0, qy = 0.0;
+  if (a != 0.0 || b != 0.0) {
+    if (fabs(a) > fabs(b)) { const double th = (M_PI / 4.0) * (b / a); qx = a * cos(th); qy = a * sin(th); }
+    else { const double th = (M_PI / 4.0) * (a / b); qx = b * sin(th); qy = b * cos(th); }
+  }
+  const int last = L->n_surf - 1;
+  const double pupil_h = g64_pupil_h > 0.0 ? g64_pupil_h : L->semi_ap[last];
+  const double pupil_z = g64_pupil_h > 0.0 ? g64_pupil_z : S->vertex_z[last];
+  *origin = V(X, Y, S->sensor_z);
+  *dir = normalise(sub(V(pupil_h * qx, pupil_h * qy, pupil_z), *origin));
+  const double dist = S->sensor_z - pupil_z;
+  const double cos2 = dir->z * dir->z;
+  return (M_PI * pupil_h * pupil_h / (dist * dist)) * cos2 * cos2;
+}
 
 /* The estimator's sample: sensor point and rear-pupil point of sample s of
  * pixel (x, y).  Returns the start direction and the start weight. */
@@ -335,21 +478,7 @@ static double sample_ray(const g64_lens* L, const g64_system* S, int W, int H, i
   const double pitch = L->sensor_w_mm / W;
   const double X = -((x + unit_interval(rnd[0])) - 0.5 * W) * pitch;
   const double Y = -((y + unit_interval(rnd[1])) - 0.5 * H) * pitch;
-  /* concentric square -> disc (Shirley & Chiu) */
-  const double a = 2.0 * ua - 1.0, b = 2.0 * ub - 1.0;
-  double qx = 0.0, qy = 0.0;
-  if (a != 0.0 || b != 0.0) {
-    if (fabs(a) > fabs(b)) { const double th = (M_PI / 4.0) * (b / a); qx = a * cos(th); qy = a * sin(th); }
-    else { const double th = (M_PI / 4.0) * (a / b); qx = b * sin(th); qy = b * cos(th); }
-  }
-  const int last = L->n_surf - 1;
-  const double pupil_h = g64_pupil_h > 0.0 ? g64_pupil_h : L->semi_ap[last];
-  const double pupil_z = g64_pupil_h > 0.0 ? g64_pupil_z : S->vertex_z[last];
-  *origin = V(X, Y, S->sensor_z);
-  *dir = normalise(sub(V(pupil_h * qx, pupil_h * qy, pupil_z), *origin));
-  const double dist = S->sensor_z - pupil_z;
-  const double cos2 = dir->z * dir->z;
-  return (M_PI * pupil_h * pupil_h / (dist * dist)) * cos2 * cos2;
+  return aim(L, S, X, Y, 2.0 * ua - 1.0, 2.0 * ub - 1.0, origin, dir);
 }
 
 /* The device's path culling (lf_get_cull_table), as in lf_geo_oracle.c: with a table installed the IMAGE is still
@@ -440,6 +569,7 @@ void g64_trace(const g64_lens* L, int W, int H, int y0, int y1, int spp, const u
               const double colour = L->sun_radiance[ch] * L->lambda_rgb[lam][ch];
               if (!r.dead) sum[ch] += r.w * shade * colour;
               if (r.fragile) fsum[ch] += r.w_pot * shade * colour;
+              if (r.slope > 0.0) fsum[ch] += r.slope * shade * colour;
               /* ... and by cause (a ray with several: each of them), if the caller asked (g64_set_cause_buffer) */
               if (r.fragile && g64_cause)
                 for (int k = 0; k < 4; k++)
@@ -476,7 +606,25 @@ void g64_lens_samples(const g64_lens* L, int W, int H, int ns, const uint32_t ke
       double* q = out + 10 * ((size_t)i * ns + s);
       const vec dn = normalise(r.d);
       q[0] = r.o.x; q[1] = r.o.y; q[2] = r.o.z; q[3] = dn.x; q[4] = dn.y; q[5] = dn.z;
-      q[6] = r.dead ? 0.0 : r.w; q[7] = r.w_pot; q[8] = (double)r.fragile; q[9] = (double)r.dead;
+      q[6] = r.dead ? 0.0 : r.w; q[7] = r.w_pot + r.slope; q[8] = (double)r.fragile; q[9] = (double)r.dead;
     }
+  }
+}
+
+/* lf_generate_lens_rays in float64: the primary paths from n sensor points xy (mm) through the pupil-square
+ * points uv in [-1, 1]^2 (both the float32 values the device is given); out: n x 10 as g64_lens_samples */
+void g64_lens_rays(const g64_lens* L, int lam, int n, const float* xy, const float* uv, const float* mask, int mw,
+                   int mh, double* out) {
+  g64_system S;
+  lay_out(L, &S);
+  for (int i = 0; i < n; i++) {
+    vec o, d;
+    const double w0 = aim(L, &S, xy[2 * i], xy[2 * i + 1], uv[2 * i], uv[2 * i + 1], &o, &d);
+    g64_ray r = {o, d, w0, w0, 0, 0};
+    follow(L, &S, lam, -1, -1, mask, mw, mh, &r);
+    double* q = out + 10 * (size_t)i;
+    const vec dn = normalise(r.d);
+    q[0] = r.o.x; q[1] = r.o.y; q[2] = r.o.z; q[3] = dn.x; q[4] = dn.y; q[5] = dn.z;
+    q[6] = r.dead ? 0.0 : r.w; q[7] = r.w_pot + r.slope; q[8] = (double)r.fragile; q[9] = (double)r.dead;
   }
 }

@@ -634,6 +634,43 @@ def g64_trace_ray_ex(lens, lam, i, j, p, d, w=1.0, mask=None, **eps):
     return st, np.array(pp[:]), np.array(dd[:]), ww.value, ne.value, int(out[0]), out[1]
 
 
+def g64_trace_ray_slope(lens, lam, i, j, p, d, w=1.0, mask=None, **eps):
+    """g64_trace_ray_ex + the slope allowance of a ray that crossed a filtered stop (g64_set_mask_filter):
+    -> (dead, exit point, exit direction, weight, events, fragile, potential weight, allowance)"""
+    L = g64_lens(lens, **eps)
+    if mask is None:
+        mask = np.ones((4, 4), np.float32)
+    mask = np.ascontiguousarray(mask, np.float32)
+    pp = (C.c_double * 3)(*[float(v) for v in p])
+    dd = (C.c_double * 3)(*[float(v) for v in d])
+    ww = C.c_double(w)
+    ne = C.c_int()
+    out = (C.c_double * 3)()
+    st = lib().g64_trace_ray_slope(C.byref(L), int(lam), int(i), int(j), pp, dd, C.byref(ww), _p(mask, C.c_float),
+                                   mask.shape[1], mask.shape[0], C.byref(ne), out)
+    return st, np.array(pp[:]), np.array(dd[:]), ww.value, ne.value, int(out[0]), out[1], out[2]
+
+
+def g64_set_films(coatings=None):
+    """The float64 tracer follows single-layer films (lf_set_lens_coatings): coatings = the dict load_lens_file
+    returns under "coatings" (lambda_nm[l], thickness_nm[k], index[l, k] or one value per interface / for all),
+    every number rounded through float32 as the device receives it; None clears them (the default).  A process-
+    global setting: use it in try ... finally.  The float32 oracle knows no films."""
+    if coatings is None:
+        lib().g64_set_films(0, 0, None, None, None)
+        return
+    lam = np.ascontiguousarray(np.asarray(coatings["lambda_nm"], np.float32).ravel(), np.float64)
+    d = np.ascontiguousarray(np.asarray(coatings["thickness_nm"], np.float32).ravel(), np.float64)
+    m = np.ascontiguousarray(np.broadcast_to(np.asarray(coatings["index"], np.float32), (len(lam), len(d))), np.float64)
+    lib().g64_set_films(len(d), len(lam), _p(lam, C.c_double), _p(d, C.c_double), _p(m, C.c_double))
+
+
+def g64_set_mask_filter(filter=0):
+    """The float64 tracer reads the stop's mask as lf_set_mask_filter says: 0 the nearest texel (the default),
+    1 bilinear.  A process-global setting: use it in try ... finally.  The float32 oracle knows the nearest only."""
+    lib().g64_set_mask_filter(int(filter))
+
+
 def g64_set_x_window(x0=0, x1=1 << 30):
     """g64_trace only traces columns [x0, x1) (default: all)."""
     lib().g64_set_x_window(int(x0), int(x1))
@@ -681,7 +718,9 @@ def geo_lens_samples(lens, W, H, ns, key, lam, pixels, mask):
 
 
 def g64_lens_samples(lens, W, H, ns, key, lam, pixels, mask, sub_bits=6, **eps):
-    """float64 tracer: (n_pix, ns, 10) {origin, unit direction, weight, potential weight, fragile, dead}."""
+    """float64 tracer: (n_pix, ns, 10) {origin, unit direction, weight, potential weight, fragile, dead}.
+    Under g64_set_mask_filter(1) the potential weight includes the ray's slope allowance: for a ray that is
+    not fragile, column 7 - column 6 is how much float32's position error at the stop can move its weight."""
     L = g64_lens(lens, **eps)
     pixels = np.ascontiguousarray(pixels, np.int32)
     mask = np.ascontiguousarray(mask, np.float32)
@@ -689,6 +728,18 @@ def g64_lens_samples(lens, W, H, ns, key, lam, pixels, mask, sub_bits=6, **eps):
     k = (C.c_uint32 * 2)(key & 0xffffffff, (key >> 32) & 0xffffffff)
     lib().g64_lens_samples(C.byref(L), int(W), int(H), int(ns), k, int(sub_bits), int(lam), _p(pixels, C.c_int),
                            len(pixels), _p(mask, C.c_float), mask.shape[1], mask.shape[0], _p(out, C.c_double))
+    return out
+
+
+def g64_lens_rays(lens, lam, xy, uv, mask, **eps):
+    """lf_generate_lens_rays as the float64 tracer computes it: n x 10 as g64_lens_samples."""
+    L = g64_lens(lens, **eps)
+    xy = np.ascontiguousarray(xy, np.float32).reshape(-1, 2)
+    uv = np.ascontiguousarray(uv, np.float32).reshape(-1, 2)
+    mask = np.ascontiguousarray(mask, np.float32)
+    out = np.zeros((len(xy), 10), np.float64)
+    lib().g64_lens_rays(C.byref(L), int(lam), len(xy), _p(xy, C.c_float), _p(uv, C.c_float), _p(mask, C.c_float),
+                        mask.shape[1], mask.shape[0], _p(out, C.c_double))
     return out
 
 
