@@ -258,7 +258,7 @@ lf_status lf_create(lf_ctx** out, int device) {
   // (changes the sampling pattern; the oracles / tests use the default, 6)
   if (const char* sb = std::getenv("LF_MARCH_SUB_BITS")) {
     int v = std::atoi(sb);
-    if (v >= 0 && v <= 8) ctx->march_sub_bits = v;
+    if (v >= 0 && v <= kMaxSubcellBits) ctx->march_sub_bits = v;
   }
 #endif
   default_paraxial_lens(ctx->pl);
@@ -941,7 +941,7 @@ lf_status lf_set_ghost_pairs(lf_ctx* ctx, const int* pairs, int n_pairs, int inc
 
 lf_status lf_set_pupil_subcells(lf_ctx* ctx, int bits) {
   if (!ctx) return LF_ERR_INVALID;
-  if (bits < 0 || bits > 8) return lf_fail(ctx, LF_ERR_INVALID, "pupil sub-cell bits must be 0..8");
+  if (bits < 0 || bits > kMaxSubcellBits) return lf_fail(ctx, LF_ERR_INVALID, "pupil sub-cell bits must be 0..8");
   ctx->march_sub_bits = bits;
   return LF_OK;
 }

@@ -27,7 +27,8 @@ namespace {
 using namespace lfm;
 
 constexpr int kWgWaves = 8;
-constexpr int kListMax = 4096;   // samples of one tile's workgroup (spp / sgroups) listed at a time
+constexpr int kListBits = 12;
+constexpr int kListMax = 1 << kListBits;   // samples of one tile's workgroup (spp / sgroups) listed at a time
 
 // what a wave tallies while it marches (slots of lf_counters / lf_get_march_stats)
 struct PathTally {
@@ -166,6 +167,10 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
       lit_any |= lit[j];
     }
     if (lit_any == 0ull) continue;
+    if (!W1) {
+      lit_any = lobe_gate<K>(r, lit, sx, sy, sz, sun_ss, inv_1mc);
+      if (lit_any == 0ull) continue;
+    }
     for (int j = 0; j < K; j++) {        // not unrolled (W1 = false): one copy of the weighted march
       lanemask lj = lit[0];
 #pragma unroll
@@ -336,6 +341,7 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
           lit[j] = alive[j] & __ballot(cg > lobe_thr);
           lit_any |= lit[j];
         }
+        if (lit_any != 0ull) lit_any = lobe_gate<K>(r, lit, sx, sy, sz, sun_ss, inv_1mc);
         if (lit_any != 0ull) {
           for (int j = 0; j < K; j++) {        // not unrolled: one copy of the weighted march
             lanemask lj = lit[0];
@@ -398,7 +404,10 @@ void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restri
   __shared__ unsigned long long s_acc[64 * 3];
   __shared__ unsigned long long s_cnt[kMarchCounters];
   __shared__ int s_next, s_nlist;
-  __shared__ unsigned short s_list[kListMax];
+  // the chunk's listed samples: the sample's place in the chunk (kListBits bits) and, above it, the pupil sub-cell the
+  // listing pass drew for it (a stratified sample's: sxi | syi << kMaxSubcellBits, what lf_set_pupil_subcells allows)
+  static_assert(2 * kMaxSubcellBits <= 32 - kListBits, "a listed sample's sub-cell does not fit beside its place in the chunk");
+  __shared__ unsigned s_list[kListMax];
   __shared__ int2 s_meta[MODE == 1 ? kCullMaxPaths : 1];      // per path: events << 16 | events of the common leg; first row of its sequence
   __shared__ float s_chan[LF_MAX_LAMBDA * 3];
   const int tid = threadIdx.x;
@@ -459,15 +468,20 @@ void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restri
     for (int k = tid; k < chunk_n; k += 64 * kWgWaves) {
       const int s = sg + (chunk0 + k) * sgroups;
       bool work = true;     // (a sample whose lanes look their cells up one by one is listed: the sample loop finds out)
+      unsigned drawn = 0u;
       if (s >= GG && !cull.multi) work = crow[cull.cells] != 0ull;
-      if (s < GG && !per_lane && !cull.multi) {
-        // the table cell of the sub-cell the wave's lanes all aim sample s at (the draw of the sample loop below)
+      if (s < GG) {
+        // the sub-cell the wave's lanes all aim sample s at: drawn HERE, once for the tile's eight waves, and kept beside the
+        // listed sample -- and its table cell, where the lanes share one
         const uint4 r2 = philox4x32_10(make_uint4(tile_id, (unsigned)s, kDomainSubcell, 0u), a.key);
         const unsigned sxi = a.sub_bits ? (r2.x >> (32 - a.sub_bits)) : 0u, syi = a.sub_bits ? (r2.y >> (32 - a.sub_bits)) : 0u;
-        const int cy = s / a.G, cx = s - cy * a.G;
-        work = crow[(cy * cull.m + (int)((syi << cull.m_shift) >> a.sub_bits)) * cull.P + cx * cull.m + (int)((sxi << cull.m_shift) >> a.sub_bits)] != 0ull;
+        drawn = sxi | (syi << kMaxSubcellBits);
+        if (!per_lane && !cull.multi) {
+          const int cy = s / a.G, cx = s - cy * a.G;
+          work = crow[(cy * cull.m + (int)((syi << cull.m_shift) >> a.sub_bits)) * cull.P + cx * cull.m + (int)((sxi << cull.m_shift) >> a.sub_bits)] != 0ull;
+        }
       }
-      if (work) s_list[atomicAdd(&s_nlist, 1)] = (unsigned short)k;
+      if (work) s_list[atomicAdd(&s_nlist, 1)] = (unsigned)k | (drawn << kListBits);
     }
     __syncthreads();
     const int n_list = s_nlist;
@@ -476,7 +490,8 @@ void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restri
       if (lane == 0) k = atomicAdd(&s_next, 1);
       k = __builtin_amdgcn_readfirstlane(k);
       if (k >= n_list) break;
-      const int s = sg + (chunk0 + (int)s_list[k]) * sgroups;       // wave-uniform
+      const unsigned listed = (unsigned)__builtin_amdgcn_readfirstlane((int)s_list[k]);
+      const int s = sg + (chunk0 + (int)(listed & (unsigned)(kListMax - 1))) * sgroups;       // wave-uniform
       // ---- sensor sample -> initial ray (the expressions of k_march / sample_start) -----------------
       const uint4 rnd = philox4x32_10(make_uint4(p, (unsigned)s, kDomainMarch, 0u), a.key);
       const float jx = u01(rnd.x), jy = u01(rnd.y);
@@ -484,9 +499,9 @@ void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restri
       int entry = -1;
       if (s < GG) {
         const int cy = s / a.G, cx = s - cy * a.G;
-        const uint4 r2 = philox4x32_10(make_uint4(tile_id, (unsigned)s, kDomainSubcell, 0u), a.key);
-        const unsigned sxi = a.sub_bits ? (r2.x >> (32 - a.sub_bits)) : 0u;
-        const unsigned syi = a.sub_bits ? (r2.y >> (32 - a.sub_bits)) : 0u;
+        // the sub-cell the wave's lanes all aim sample s at, as the listing pass drew it
+        const unsigned sxi = (listed >> kListBits) & ((1u << kMaxSubcellBits) - 1u);
+        const unsigned syi = listed >> (kListBits + kMaxSubcellBits);
         ua = ((float)cx + ((float)sxi + ua) * a.inv_sub) * a.inv_G;
         ub = ((float)cy + ((float)syi + ub) * a.inv_sub) * a.inv_G;
         if (!per_lane) entry = (cy * cull.m + (int)((syi << cull.m_shift) >> a.sub_bits)) * cull.P + cx * cull.m + (int)((sxi << cull.m_shift) >> a.sub_bits);

@@ -243,6 +243,7 @@ constexpr int kCullOcc = 32;             // the stop mask's occupancy grid: kCul
 __host__ __device__ inline size_t lf_cull_row_of_block(int b, int share_n, int share_nb) {
   return share_n > 1 ? (size_t)(b % share_n) * (size_t)share_nb + (size_t)(b / share_n) : (size_t)b;
 }
+constexpr int kMaxSubcellBits = 8;    // lf_set_pupil_subcells: at most 2^8 x 2^8 sub-cells per stratum (k_march_cull's sample list holds both indices)
 struct LfCullArgs {
   const unsigned long long* table;   // [rows][cells + 1], row = lf_cull_row_of_block(block); null = every path everywhere
   int blocks_x, blocks_y;

@@ -530,6 +530,8 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
               }
             }
 #endif
+            // (the epilogue's exact test, made before the re-march instead of after it: lobe_gate)
+            if (!kW1 && lit_any != 0ull) lit_any = lobe_gate<K>(r, lit, sx, sy, sz, sun_ss, inv_1mc);
             if (lit_any != 0ull) {
               // rare (about 1 % of the wave-paths): march this path again, alone and with the
               // weight, along its own row sequence -- once per wavelength that has a lit lane

@@ -28,6 +28,24 @@ __device__ __forceinline__ float lobe_q(float dx, float dy, float dz, float sx, 
   return __fdiv_rn(c2, den) * inv_1mc;
 }
 
+// The lanes the weighted re-march is FOR.  The pre-test d.s > lobe_thr only selects (a 1/16 margin around the lobe); what the
+// re-march's epilogue keeps is lobe_q < 1 on the re-marched ray's direction -- which is the first march's, bit for bit (the
+// same events on the same ray).  So once the pre-test admits a lane of a completed path, the epilogue's own test is made on
+// the first march's rays: lit[j] keeps the lanes that will contribute, and a wavelength none of whose lanes will is not
+// marched again.  Behind the pre-test (a root and a division per wavelength), never on every completed path.  Returns the
+// union of the narrowed masks.
+template <int K>
+__device__ __forceinline__ lanemask lobe_gate(const Ray (&r)[K], lanemask (&lit)[K], float sx, float sy, float sz, float ss,
+                                              float inv_1mc) {
+  lanemask lit_any = 0ull;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    if (lit[j] != 0ull) lit[j] &= __ballot(lobe_q(r[j].dx, r[j].dy, r[j].dz, sx, sy, sz, ss, inv_1mc) < 1.0f);
+    lit_any |= lit[j];
+  }
+  return lit_any;
+}
+
 struct MarchArgs {
   int mw, mh, W, H, y0, y1;
   int spp, G;          // G x G pupil strata, G = floor(sqrt(spp))
