@@ -27,6 +27,7 @@ extern "C" {
 #define LF_MAX_SURFACES 16   /* interfaces per prescription (incl. the stop) */
 #define LF_MAX_LAMBDA 8      /* wavelengths per prescription */
 #define LF_MAX_FLARES 8      /* in-frame directional lights */
+#define LF_MAX_LIGHTS 8      /* lights one launch of the geometric march follows (lf_set_lights) */
 #define LF_MAX_PAIRS 128     /* ghost pairs per trace call */
 
 typedef struct lf_ctx lf_ctx;
@@ -478,6 +479,36 @@ lf_status lf_set_lambda_rgb(lf_ctx* ctx, const float* weights);
  * the range contract above), angular radius of its (smooth) lobe in radians */
 lf_status lf_set_sun(lf_ctx* ctx, const float dir[3], const float radiance[3],
                      float angular_radius);
+/* SEVERAL lights in ONE pass of the march: n_lights (1 .. LF_MAX_LIGHTS) lights, dir[3 k ..], radiance[3 k ..],
+ * angular_radius[k] as lf_set_sun's one -- each validated and stored exactly as lf_set_sun does (z < 0, finite,
+ * radiance >= 0, 0 < radius <= 1.5; the direction normalised in double, then narrowed).  The call replaces ALL
+ * lights; a refusal (LF_ERR_INVALID) leaves the previous ones installed.  lf_set_sun IS lf_set_lights(1, ...).
+ * The contract:
+ *   - the rays, their events and their fates do not depend on any light; a ray that ends inside several lobes
+ *     contributes to each one: per (ray, light k, channel c) ONE value
+ *     (u64)(contrib_k x radiance_k[c] x lambda_rgb[l][c] x 2^bits) is added, contrib_k = weight x (1 - q_k)^2
+ *     being the single light's arithmetic with light k in the sun's place;
+ *   - hence a frame of K lights is the SUM of the K single-light frames under the same key, sampling
+ *     specification and `bits`, bit for bit;
+ *   - the range contract above takes the sum over the lights of the radiances as its worst case
+ *     (lf_get_march_fix_bits); under an HDR launch every light's radiance is uploaded scaled;
+ *   - lf_counters::rays_hit_light counts (ray, light) contributions; every other counter counts rays, as with
+ *     one light;
+ *   - the cull table is built for all lights (a path starts where it can reach ANY of them: the bitwise OR of
+ *     the lights' own tables) and its audit refutes it if a dropped ray ends inside any light's lobe.
+ * A context with one light launches exactly the kernels it launched before this call existed.  More lights than
+ * LF_MAX_LIGHTS: compose launches with lf_set_ghost_accumulate.
+ * COST (the bench frame, 1080p x 256 spp, table resolved and audited inside every frame; profiles/multi_light_cost.json):
+ * one light 34.95 ms, through the parent commit's library 34.93 (spreads 0.07: the single-light kernels are the parent's);
+ * 2 / 4 / 8 lights of 0.05 rad spread over the frame in ONE launch 53.3 / 87.2 / 231.6 ms against 66.2 / 127.9 / 247.3 ms as
+ * 2 / 4 / 8 launches under lf_set_ghost_accumulate (x 0.81 / 0.68 / 0.94).  The union of the lights' tables starts 9.3 / 12.1 /
+ * 15.9 % of all paths (one light: 7.7 %); at 8 such lights that is past the fraction where the launch takes the path tree,
+ * which marches everything once -- still ahead of eight culled launches.  The resolve takes 0.58 / 0.69 / 0.85 / 1.10 ms
+ * with 1 / 2 / 4 / 8 lights. */
+lf_status lf_set_lights(lf_ctx* ctx, int n_lights, const float* dir, const float* radiance, const float* angular_radius);
+/* what lf_set_lights / lf_set_sun installed (any pointer may be NULL; arrays of LF_MAX_LIGHTS lights): the unit
+ * directions and radiances as stored, the angular radii as given; *n_lights = 0 before any light */
+lf_status lf_get_lights(lf_ctx* ctx, int* n_lights, float* dir, float* radiance, float* angular_radius);
 /* Sun hand-over from the scene to the march: turn in-frame flare `flare` of lf_find_sun_pos /
  * lf_set_flares (normalised screen position flare_origins[flare], radiance flare_radiance[flare];
  * src/pathtracer/pathtracer.cpp:32-64, camera.cpp:245-273) into the lens-space light of
@@ -490,6 +521,13 @@ lf_status lf_set_sun(lf_ctx* ctx, const float dir[3], const float radiance[3],
  * sees otherwise.  Needs lf_set_frame, lf_set_lens and a flare state.  No reference counterpart (the
  * reference's ghosts take only `angle_to_sun`, pathtracer.cpp:50, :735-762). */
 lf_status lf_set_sun_from_flares(lf_ctx* ctx, int flare, double efl_mm, float angular_radius);
+/* ... and EVERY in-frame flare of the flare state as the lights of lf_set_lights, each by lf_set_sun_from_flares'
+ * mapping, all with the same angular radius: every in-frame DirectionalLight gets its lens ghosts, as it gets its
+ * starburst.  *n_taken (may be NULL) = the lights installed.  With one flare the installed state is exactly
+ * lf_set_sun_from_flares(ctx, 0, ...)'s.  More in-frame lights than LF_MAX_LIGHTS: LF_ERR_INVALID (the message
+ * names the limit; nothing is installed) -- such a host composes launches itself: lf_set_sun_from_flares /
+ * lf_set_lights per group of lights under lf_set_ghost_accumulate. */
+lf_status lf_set_lights_from_flares(lf_ctx* ctx, double efl_mm, float angular_radius, int* n_taken);
 /* Paraxial effective focal length of a prescription at one wavelength (host arithmetic, no
  * device): the system matrix from the reference's own T / R operators (pathtracer.cpp:527-533);
  * ior_row = the n indices of that wavelength (media BEHIND each interface).  Arguments as
@@ -619,6 +657,8 @@ lf_status lf_get_cull_audit(lf_ctx* ctx, uint64_t* rays, uint64_t* lit, int* lau
  *   "cull_force" 0/1            keep the culled march whatever the table starts (small test frames)
  *   "cull_weights_first" 0/1    the Fresnel / mask weight on EVERY executed event (SURVEY 8d's unit), same pixels
  *   "cull_no_prefix" 0/1        every started path marched alone from the sensor (round 5's culled march), same pixels
+ *   "cull_ignore_light" k       -1 (default): off; k: the cull pre-pass and the resolve leave light k of lf_set_lights out -- a
+ *                               table wrong by construction; the march and the audit still see light k (the audit's test)
  *   "cull_cache" 0/1            0: no cached tree -- every pre-pass marches its boxes (the tree a context holds is kept), same table
  *   "cull_cache_max_mb" MiB     the cached tree's byte budget (default 8192)
  *   "cull_general_kernel" 0/1   build the table with the kernel that takes its rules as arguments (must give the shipped one's table)

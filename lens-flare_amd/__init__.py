@@ -21,6 +21,7 @@ DATA = os.path.join(HERE, "data")
 STATUS = {0: "LF_OK", 1: "LF_ERR_INVALID", 2: "LF_ERR_NO_DEVICE", 3: "LF_ERR_HIP",
           4: "LF_ERR_STATE", 5: "LF_ERR_OOM"}
 APERTURE_STARBURST, APERTURE_GHOST = 0, 1
+MAX_LIGHTS = 8   # LF_MAX_LIGHTS: lights one launch of the geometric march follows (set_lights)
 SAMPLE_BUFFER, GHOST_BUFFER, STARBURST_BUFFER, SCENE_BUFFER = 0, 1, 2, 3
 # the sampling specification's defaults (lf_internal.h): 64 x 64 pupil sub-cells, wave tiles with columns 8 apart
 DEFAULT_SUBCELL_BITS, DEFAULT_TILE_STRIDE = 6, 8
@@ -35,6 +36,7 @@ ABI_SYMBOLS = [
     "lf_set_direct_hemisphere_sample", "lf_collada_check", "lf_render_scene_term",
     "lf_generate_ghost_buffer", "lf_render_flare_layer", "lf_read_tile", "lf_read_pixel",
     "lf_write_to_framebuffer", "lf_save_image_rgba", "lf_device_buffer", "lf_set_lens", "lf_set_lambda_rgb", "lf_set_sun",
+    "lf_set_lights", "lf_get_lights", "lf_set_lights_from_flares",
     "lf_set_sun_from_flares", "lf_paraxial_efl", "lf_paraxial_image_scale", "lf_set_ghost_pairs", "lf_set_pupil_subcells", "lf_set_tile_stride", "lf_trace_ghosts", "lf_set_march_culling", "lf_get_cull_info", "lf_get_cull_table", "lf_get_cull_started_fraction", "lf_get_cull_reason", "lf_set_cull_audit", "lf_get_cull_audit", "lf_test_knob", "lf_comm_share_cull", "lf_set_cull_share", "lf_cull_prepare", "lf_cull_table_view", "lf_cull_commit", "lf_get_march_fix_bits", "lf_generate_lens_rays", "lf_get_counters", "lf_reset_counters", "lf_get_executed_events", "lf_get_march_stats", "lf_native_sqrt", "lf_native_rcp", "lf_set_starburst_spectrum", "lf_load_collada", "lf_march_tables",
     "lf_timing_enable", "lf_timing_reset", "lf_timing_get",
     "lf_clear_ghost_buffer", "lf_draw_ghost", "lf_rasterize_textured_triangle", "lf_fill_textured_pixel",
@@ -696,6 +698,32 @@ class LensFlare:
     def set_sun_from_flares(self, flare=0, efl_mm=0.0, angular_radius=0.05):
         self._ck(self.lib.lf_set_sun_from_flares(self.ctx, int(flare), C.c_double(efl_mm),
                                                  C.c_float(angular_radius)))
+
+    def set_lights(self, directions, radiances, angular_radii):
+        """Several lights in ONE pass of the march (lf_set_lights): n x 3 directions (z < 0), n x 3 radiances, n angular
+        radii, 1 <= n <= MAX_LIGHTS.  Replaces all lights; a refusal leaves the previous ones.  The frame is the sum of
+        the n single-light frames, bit for bit."""
+        d = np.ascontiguousarray(directions, np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(radiances, np.float32).reshape(-1, 3)
+        a = np.ascontiguousarray(angular_radii, np.float32).reshape(-1)
+        if not (len(d) == len(r) == len(a)):
+            raise ValueError("set_lights: one direction, one radiance and one angular radius per light")
+        self._ck(self.lib.lf_set_lights(self.ctx, len(d), _fp(d, C.c_float), _fp(r, C.c_float), _fp(a, C.c_float)))
+
+    def lights(self):
+        """(directions n x 3 as stored, radiances n x 3, angular radii n) of the installed lights (lf_get_lights)"""
+        n = C.c_int(0)
+        d = np.zeros((MAX_LIGHTS, 3), np.float32)
+        r = np.zeros((MAX_LIGHTS, 3), np.float32)
+        a = np.zeros(MAX_LIGHTS, np.float32)
+        self._ck(self.lib.lf_get_lights(self.ctx, C.byref(n), _fp(d, C.c_float), _fp(r, C.c_float), _fp(a, C.c_float)))
+        return d[:n.value].copy(), r[:n.value].copy(), a[:n.value].copy()
+
+    def set_lights_from_flares(self, efl_mm=0.0, angular_radius=0.05):
+        """every in-frame flare of the flare state becomes a light of the march (lf_set_lights_from_flares); returns how many"""
+        n = C.c_int(0)
+        self._ck(self.lib.lf_set_lights_from_flares(self.ctx, C.c_double(efl_mm), C.c_float(angular_radius), C.byref(n)))
+        return n.value
 
     def set_ghost_pairs(self, pairs=None, include_primary=True):
         if pairs is None or len(pairs) == 0:

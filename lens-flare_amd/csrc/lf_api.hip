@@ -539,6 +539,7 @@ lf_status lf_set_flares(lf_ctx* ctx, int n, const double* origins, const double*
   LfFlares f;
   std::memset(&f, 0, sizeof(f));
   f.n_flares = n;
+  f.n_in_frame = n;
   f.angle_to_sun = angle_to_sun;
   for (int k = 0; k < n; k++) {
     f.origin[k][0] = origins[2 * k]; f.origin[k][1] = origins[2 * k + 1];
@@ -802,24 +803,64 @@ lf_status lf_set_lambda_rgb(lf_ctx* ctx, const float* weights) {
   return LF_OK;
 }
 
+lf_status lf_set_lights(lf_ctx* ctx, int n_lights, const float* dir, const float* radiance, const float* angular_radius) {
+  if (!ctx || !dir || !radiance || !angular_radius) return LF_ERR_INVALID;
+  if (n_lights < 1 || n_lights > LF_MAX_LIGHTS)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lights: 1 .. LF_MAX_LIGHTS (" + std::to_string(LF_MAX_LIGHTS) + ") lights per launch");
+  // every light is validated before any is installed: a refusal leaves the previous lights in place
+  LfLensDev L = ctx->lens;
+  for (int k = 0; k < n_lights; k++) {
+    const float* d = dir + 3 * k;
+    const float* rad = radiance + 3 * k;
+    const float ar = angular_radius[k];
+    double n = std::sqrt((double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2]);
+    if (!(n > 0) || !(d[2] < 0) || !(ar > 0) || ar > 1.5f)
+      return lf_fail(ctx, LF_ERR_INVALID, "sun: direction must have z < 0, 0 < angular radius <= 1.5");
+    for (int c = 0; c < 3; c++)   // unsigned fixed-point sums: see lf_set_lambda_rgb; any finite magnitude is fine (lf_march_fix_bits)
+      if (!std::isfinite(rad[c]) || rad[c] < 0.0f || !std::isfinite(d[c]))
+        return lf_fail(ctx, LF_ERR_INVALID, "sun: radiance must be finite and >= 0, the direction finite");
+    for (int c = 0; c < 3; c++) {
+      L.light_dir[k][c] = (float)(d[c] / n);
+      L.light_radiance[k][c] = rad[c];
+    }
+    L.light_inv_one_minus_cos[k] = (float)(1.0 / (1.0 - std::cos((double)ar)));
+    L.light_ss[k] = (float)((double)L.light_dir[k][0] * L.light_dir[k][0] +
+                            (double)L.light_dir[k][1] * L.light_dir[k][1] +
+                            (double)L.light_dir[k][2] * L.light_dir[k][2]);
+    L.light_thr[k] = lf_march_lobe_thr_of(L.light_inv_one_minus_cos[k]);
+  }
+  for (int k = n_lights; k < LF_MAX_LIGHTS; k++) {
+    for (int c = 0; c < 3; c++) L.light_dir[k][c] = L.light_radiance[k][c] = 0.0f;
+    L.light_inv_one_minus_cos[k] = L.light_ss[k] = L.light_thr[k] = 0.0f;
+  }
+  L.n_lights = n_lights;
+  // light 0 is the sun of the single-light kernels
+  for (int c = 0; c < 3; c++) { L.sun_dir[c] = L.light_dir[0][c]; L.sun_radiance[c] = L.light_radiance[0][c]; }
+  L.sun_inv_one_minus_cos = L.light_inv_one_minus_cos[0];
+  L.sun_ss = L.light_ss[0];
+  ctx->lens = L;
+  for (int k = 0; k < LF_MAX_LIGHTS; k++) ctx->light_radius[k] = k < n_lights ? angular_radius[k] : 0.0f;
+  ctx->sun_valid = true;
+  return LF_OK;
+}
+
 lf_status lf_set_sun(lf_ctx* ctx, const float dir[3], const float radiance[3],
                      float angular_radius) {
   if (!ctx || !dir || !radiance) return LF_ERR_INVALID;
-  double n = std::sqrt((double)dir[0] * dir[0] + (double)dir[1] * dir[1] + (double)dir[2] * dir[2]);
-  if (!(n > 0) || !(dir[2] < 0) || !(angular_radius > 0) || angular_radius > 1.5f)
-    return lf_fail(ctx, LF_ERR_INVALID, "sun: direction must have z < 0, 0 < angular radius <= 1.5");
-  for (int c = 0; c < 3; c++)   // unsigned fixed-point sums: see lf_set_lambda_rgb; any finite magnitude is fine (lf_march_fix_bits)
-    if (!std::isfinite(radiance[c]) || radiance[c] < 0.0f || !std::isfinite(dir[c]))
-      return lf_fail(ctx, LF_ERR_INVALID, "sun: radiance must be finite and >= 0, the direction finite");
-  for (int c = 0; c < 3; c++) {
-    ctx->lens.sun_dir[c] = (float)(dir[c] / n);
-    ctx->lens.sun_radiance[c] = radiance[c];
+  return lf_set_lights(ctx, 1, dir, radiance, &angular_radius);
+}
+
+lf_status lf_get_lights(lf_ctx* ctx, int* n_lights, float* dir, float* radiance, float* angular_radius) {
+  if (!ctx) return LF_ERR_INVALID;
+  const int n = ctx->sun_valid ? ctx->lens.n_lights : 0;
+  if (n_lights) *n_lights = n;
+  for (int k = 0; k < n; k++) {
+    for (int c = 0; c < 3; c++) {
+      if (dir) dir[3 * k + c] = ctx->lens.light_dir[k][c];
+      if (radiance) radiance[3 * k + c] = ctx->lens.light_radiance[k][c];
+    }
+    if (angular_radius) angular_radius[k] = ctx->light_radius[k];
   }
-  ctx->lens.sun_inv_one_minus_cos = (float)(1.0 / (1.0 - std::cos((double)angular_radius)));
-  ctx->lens.sun_ss = (float)((double)ctx->lens.sun_dir[0] * ctx->lens.sun_dir[0] +
-                             (double)ctx->lens.sun_dir[1] * ctx->lens.sun_dir[1] +
-                             (double)ctx->lens.sun_dir[2] * ctx->lens.sun_dir[2]);
-  ctx->sun_valid = true;
   return LF_OK;
 }
 
@@ -878,6 +919,23 @@ lf_status lf_paraxial_image_scale(int n, int stop, const float* radius, const fl
   return paraxial_image_scale(n, stop, radius, thickness, ior_row, scale_mm) ? LF_OK : LF_ERR_INVALID;
 }
 
+// the light flare `flare` of the flare state stands for: its direction through the image scale, its radiance
+static lf_status light_of_flare(lf_ctx* ctx, const char* who, const LfFlares& f, int flare, double* efl_mm, float dir[3], float rad[3]) {
+  if (!(*efl_mm > 0.0)) {
+    // the image scale of THIS sensor position: the focal length when the sensor sits in the focal plane (the
+    // shipped prescriptions), the chief ray's landing height per unit field angle when lf_focus_lens has moved it
+    if (!paraxial_image_scale(ctx->raw_n, ctx->raw_stop, ctx->raw_radius, ctx->raw_thickness,
+                              ctx->raw_ior + (size_t)(ctx->lens.n_lambda / 2) * ctx->raw_n, efl_mm) || !(*efl_mm > 0.0))
+      return lf_fail(ctx, LF_ERR_INVALID, std::string(who) + ": the prescription images no distant point on its sensor");
+  }
+  const double sw = ctx->sensor_w_mm, sh = sw * (double)ctx->H / (double)ctx->W;
+  dir[0] = (float)((f.origin[flare][0] - 0.5) * sw / *efl_mm);
+  dir[1] = (float)((f.origin[flare][1] - 0.5) * sh / *efl_mm);
+  dir[2] = -1.0f;
+  for (int c = 0; c < 3; c++) rad[c] = (float)f.radiance[flare][c];
+  return LF_OK;
+}
+
 lf_status lf_set_sun_from_flares(lf_ctx* ctx, int flare, double efl_mm, float angular_radius) {
   if (!ctx || flare < 0 || flare >= LF_MAX_FLARES) return LF_ERR_INVALID;
   if (ctx->W == 0) return lf_fail(ctx, LF_ERR_STATE, "lf_set_sun_from_flares before lf_set_frame");
@@ -888,18 +946,36 @@ lf_status lf_set_sun_from_flares(lf_ctx* ctx, int flare, double efl_mm, float an
   LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
   LF_HIP(ctx, hipMemcpy(&f, ctx->flares, sizeof(f), hipMemcpyDeviceToHost));
   if (flare >= f.n_flares) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_sun_from_flares: no such flare in the frame");
-  if (!(efl_mm > 0.0)) {
-    // the image scale of THIS sensor position: the focal length when the sensor sits in the focal plane (the
-    // shipped prescriptions), the chief ray's landing height per unit field angle when lf_focus_lens has moved it
-    if (!paraxial_image_scale(ctx->raw_n, ctx->raw_stop, ctx->raw_radius, ctx->raw_thickness,
-                              ctx->raw_ior + (size_t)(ctx->lens.n_lambda / 2) * ctx->raw_n, &efl_mm) || !(efl_mm > 0.0))
-      return lf_fail(ctx, LF_ERR_INVALID, "lf_set_sun_from_flares: the prescription images no distant point on its sensor");
-  }
-  const double sw = ctx->sensor_w_mm, sh = sw * (double)ctx->H / (double)ctx->W;
-  const float dir[3] = {(float)((f.origin[flare][0] - 0.5) * sw / efl_mm),
-                        (float)((f.origin[flare][1] - 0.5) * sh / efl_mm), -1.0f};
-  const float rad[3] = {(float)f.radiance[flare][0], (float)f.radiance[flare][1], (float)f.radiance[flare][2]};
+  float dir[3], rad[3];
+  const lf_status st = light_of_flare(ctx, "lf_set_sun_from_flares", f, flare, &efl_mm, dir, rad);
+  if (st != LF_OK) return st;
   return lf_set_sun(ctx, dir, rad, angular_radius);
+}
+
+lf_status lf_set_lights_from_flares(lf_ctx* ctx, double efl_mm, float angular_radius, int* n_taken) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (n_taken) *n_taken = 0;
+  if (ctx->W == 0) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lights_from_flares before lf_set_frame");
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lights_from_flares before lf_set_lens");
+  if (!ctx->flares_valid) return lf_fail(ctx, LF_ERR_STATE, "no flare state: call lf_find_sun_pos or lf_set_flares");
+  LF_HIP(ctx, hipSetDevice(ctx->device));
+  LfFlares f;
+  LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  LF_HIP(ctx, hipMemcpy(&f, ctx->flares, sizeof(f), hipMemcpyDeviceToHost));
+  if (f.n_flares < 1) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lights_from_flares: no flare in the frame");
+  // (the flare state keeps LF_MAX_FLARES flares; what find_sun_pos met beyond them it only counted)
+  if (f.n_flares > LF_MAX_LIGHTS || f.n_in_frame > LF_MAX_LIGHTS)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lights_from_flares: " + std::to_string(std::max(f.n_flares, f.n_in_frame)) + " flares in the frame, one launch marches at most LF_MAX_LIGHTS = " +
+                                            std::to_string(LF_MAX_LIGHTS) + " lights (compose launches with lf_set_ghost_accumulate)");
+  float dir[3 * LF_MAX_LIGHTS], rad[3 * LF_MAX_LIGHTS], ar[LF_MAX_LIGHTS];
+  for (int k = 0; k < f.n_flares; k++) {
+    const lf_status st = light_of_flare(ctx, "lf_set_lights_from_flares", f, k, &efl_mm, dir + 3 * k, rad + 3 * k);
+    if (st != LF_OK) return st;
+    ar[k] = angular_radius;
+  }
+  const lf_status st = lf_set_lights(ctx, f.n_flares, dir, rad, ar);
+  if (st == LF_OK && n_taken) *n_taken = f.n_flares;
+  return st;
 }
 
 lf_status lf_set_ghost_pairs(lf_ctx* ctx, const int* pairs, int n_pairs, int include_primary) {
@@ -1080,6 +1156,7 @@ lf_status lf_test_knob(lf_ctx* ctx, const char* name, double value) {
   if (n == "cull_force") { ctx->cull_force = iv != 0; return LF_OK; }
   if (n == "cull_weights_first") { ctx->cull_weights_first = iv != 0; return LF_OK; }
   if (n == "cull_no_prefix") { ctx->cull_no_prefix = iv != 0; return LF_OK; }
+  if (n == "cull_ignore_light") { ctx->cull_ignore_light = iv; return LF_OK; }      // (-1: off; k: the cull table is built WITHOUT light k -- the audit's test)
   if (n == "cull_cache") { ctx->cull_cache_on = iv != 0; return LF_OK; }            // (0: the pre-pass marches its boxes at every build)
   if (n == "cull_cache_max_mb") { ctx->cull_cache_max_mb = value; return LF_OK; }   // (the cached tree's byte budget, MiB)
   if (n == "scene_compact") { ctx->scene_compact = iv < 0 ? -1 : iv != 0; return LF_OK; }

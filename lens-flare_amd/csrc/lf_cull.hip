@@ -41,7 +41,10 @@ struct PathTally {
 // and constant for a launch -- formed ONCE per workgroup (the same single float multiply) into LDS at [3 l + c], where the
 // re-march's epilogue reads it instead of through six waited scalar loads per lit (path, wavelength).  Before the kernel's
 // first barrier.
+// (a kernel of several lights, VAR & kVarLights: per light, lights_channel_factors)
+template <int VAR>
 __device__ __forceinline__ void march_channel_factors(const LfLensDev* __restrict__ lens, float* __restrict__ s_chan, int tid) {
+  if (VAR & kVarLights) { lights_channel_factors(lens, s_chan, tid, 64 * kWgWaves); return; }
   if (tid < LF_MAX_LAMBDA * 3) {
     const int l = tid / 3, c = tid - 3 * l;
     s_chan[tid] = l < lens->n_lambda ? lens->sun_radiance[c] * lens->lambda_rgb[l][c] : 0.0f;
@@ -160,6 +163,10 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
     // ---- the path is complete for nlive rays --------------------------------------------------
     T.n_scene += nlive;
     lanemask lit[K], lit_any = 0ull;
+    if (VAR & kVarLights) {
+      lit_any = lights_pretest<K, !W1>(lens, r, alive, lit);
+      if (lit_any == 0ull) continue;
+    } else {
 #pragma unroll
     for (int j = 0; j < K; j++) {
       const float cg = fmaf(r[j].dx, sx, fmaf(r[j].dy, sy, r[j].dz * sz));
@@ -170,6 +177,7 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
     if (!W1) {
       lit_any = lobe_gate<K>(r, lit, sx, sy, sz, sun_ss, inv_1mc);
       if (lit_any == 0ull) continue;
+    }
     }
     for (int j = 0; j < K; j++) {        // not unrolled (W1 = false): one copy of the weighted march
       lanemask lj = lit[0];
@@ -185,6 +193,10 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
         T.n_rm_lane += (unsigned long long)((unsigned)n_ev * (unsigned)__popcll(lj));
         T.n_rm_rows += (unsigned)n_ev;
         weighted_remarch<VAR>(rw, seq, n_ev, j, recs, wrecs, wrec_table, mask, inv_stop_h, a.mw, a.mh);
+      }
+      if (VAR & kVarLights) {
+        lights_epilogue(lens, s_chan, rw, ((lj >> lane) & 1ull) != 0ull, l, &s_acc[acc_slot * 3], T.n_light);
+        continue;
       }
       const float qq = lobe_q(rw.dx, rw.dy, rw.dz, sx, sy, sz, sun_ss, inv_1mc);
       const float om = 1.0f - qq;
@@ -335,6 +347,9 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
         // ---- the path is complete for nlive rays (as march_started_path) ---------------------------------
         T.n_scene += nlive;
         lanemask lit[K], lit_any = 0ull;
+        if (VAR & kVarLights) {
+          lit_any = lights_pretest<K, true>(lens, r, alive, lit);
+        } else {
 #pragma unroll
         for (int j = 0; j < K; j++) {
           const float cg = fmaf(r[j].dx, sx, fmaf(r[j].dy, sy, r[j].dz * sz));
@@ -342,6 +357,7 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
           lit_any |= lit[j];
         }
         if (lit_any != 0ull) lit_any = lobe_gate<K>(r, lit, sx, sy, sz, sun_ss, inv_1mc);
+        }
         if (lit_any != 0ull) {
           for (int j = 0; j < K; j++) {        // not unrolled: one copy of the weighted march
             lanemask lj = lit[0];
@@ -355,6 +371,10 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
             T.n_rm_lane += (unsigned long long)((unsigned)n_ev * (unsigned)__popcll(lj));
             T.n_rm_rows += (unsigned)n_ev;
             weighted_remarch<VAR>(rw, seq, n_ev, j, recs, wrecs, wrec_table, mask, inv_stop_h, a.mw, a.mh);
+            if (VAR & kVarLights) {
+              lights_epilogue(lens, s_chan, rw, ((lj >> lane) & 1ull) != 0ull, l, &s_acc[lane * 3], T.n_light);
+              continue;
+            }
             const float qq = lobe_q(rw.dx, rw.dy, rw.dz, sx, sy, sz, sun_ss, inv_1mc);
             const float om = 1.0f - qq;
             float contrib = __fdiv_rn(rw.wn, rw.wd) * (om * om);
@@ -409,10 +429,10 @@ void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restri
   static_assert(2 * kMaxSubcellBits <= 32 - kListBits, "a listed sample's sub-cell does not fit beside its place in the chunk");
   __shared__ unsigned s_list[kListMax];
   __shared__ int2 s_meta[MODE == 1 ? kCullMaxPaths : 1];      // per path: events << 16 | events of the common leg; first row of its sequence
-  __shared__ float s_chan[LF_MAX_LAMBDA * 3];
+  __shared__ float s_chan[(VAR & kVarLights) ? kLightChan : LF_MAX_LAMBDA * 3];
   const int tid = threadIdx.x;
   if (tid < 64 * 3) s_acc[tid] = 0ull;
-  march_channel_factors(lens, s_chan, tid);
+  march_channel_factors<VAR>(lens, s_chan, tid);
   if (tid < kMarchCounters) s_cnt[tid] = 0ull;
   if (tid == 0) { s_next = 0; s_nlist = 0; }
   if (MODE == 1 && tid < pairs->n && tid < kCullMaxPaths) {
@@ -626,10 +646,10 @@ void k_march_items(const LfLensDev* __restrict__ lens, const LfPairsDev* __restr
   __shared__ int s_next;
   __shared__ unsigned short s_items[kItemCap];
   __shared__ unsigned short s_cell[kItemCellCache * 64];      // the table cell of every (sample of the chunk, pixel): count -> fill
-  __shared__ float s_chan[LF_MAX_LAMBDA * 3];
+  __shared__ float s_chan[(VAR & kVarLights) ? kLightChan : LF_MAX_LAMBDA * 3];
   const int tid = threadIdx.x;
   if (tid < 64 * 3) s_acc[tid] = 0ull;
-  march_channel_factors(lens, s_chan, tid);
+  march_channel_factors<VAR>(lens, s_chan, tid);
   if (tid < kMarchCounters) s_cnt[tid] = 0ull;
   __syncthreads();
 
@@ -828,7 +848,11 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
   c.P = ctx->cull_P; c.m = ctx->cull_m; c.m_shift = ctx->cull_m == 4 ? 2 : ctx->cull_m == 2 ? 1 : 0;
   hipEvent_t ev = lf_timing_begin(ctx, LFK_MARCH);
 #define LF_LAUNCH_CULL1(KK, WW, SS)  do { switch (var) { case kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarCoatFilt); break; case kVarFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarFilt); break; \
-                                                      case kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarCoat); break; default: LF_LAUNCH_CULL2(KK, WW, SS, kVarBare); break; } } while (0)
+                                                      case kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarCoat); break; case kVarBare: LF_LAUNCH_CULL2(KK, WW, SS, kVarBare); break; \
+                                                      case kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarCoatFilt); break; \
+                                                      case kVarLights | kVarFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarFilt); break; \
+                                                      case kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarCoat); break; \
+                                                      default: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_CULL2(KK, WW, SS, CC)                                                                       \
   hipLaunchKernelGGL((k_march_cull<KK, WW, SS, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                         \
@@ -836,7 +860,11 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
                      (const LfWeightRow*)(ctx->prog_dev + ctx->prog_wrec_off), m.texels, a, c, ctx->ghost,   \
                      ctx->accum, ctx->counters_dev)
 #define LF_LAUNCH_ITEMS(KK)  do { switch (var) { case kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarCoatFilt); break; case kVarFilt: LF_LAUNCH_ITEMS2(KK, kVarFilt); break; \
-                                              case kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarCoat); break; default: LF_LAUNCH_ITEMS2(KK, kVarBare); break; } } while (0)
+                                              case kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarCoat); break; case kVarBare: LF_LAUNCH_ITEMS2(KK, kVarBare); break; \
+                                              case kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarCoatFilt); break; \
+                                              case kVarLights | kVarFilt: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarFilt); break; \
+                                              case kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarCoat); break; \
+                                              default: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_ITEMS2(KK, CC)                                                                             \
   hipLaunchKernelGGL((k_march_items<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                         \

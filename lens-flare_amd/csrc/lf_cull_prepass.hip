@@ -90,6 +90,10 @@ struct CullLevelArgs {
   int disable;             // experiments: bit 0 no aperture test, 1 no mask test, 2 no lobe test, 3 no all-samples-lost test
   unsigned list_stride;    // entries per path in the work lists
   unsigned occ[kCullOcc];  // occupancy rows of the stop mask
+  // several lights (lf_set_lights): sx, sy, rho of every light the table is built for (entry 0 = the three above); a box
+  // is dropped by the lobe test only if EVERY light's lobe rules it out
+  int n_lights;
+  float lsx[LF_MAX_LIGHTS], lsy[LF_MAX_LIGHTS], lrho[LF_MAX_LIGHTS];
 };
 
 // A glass event of the pre-pass: the arithmetic of surface_event<false> (lf_march_events.h) WITHOUT a clear aperture
@@ -408,11 +412,15 @@ __global__ __launch_bounds__(LF_CULL_WG, LF_CULL_WAVES) void k_cull_level_genera
   if (!culled && !keep) {
     // the path is complete: where can the box point?  (K is the unit direction in air again)
     const Foot f = footprint(true, live, 2e-5f);
-    const float ex = a.sx - f.cx, ey = a.sy - f.cy;
-    const float dist = lf_sqrt(fmaf(ex, ex, ey * ey));
-    const float id = dist > 0.0f ? lf_rcp(dist) : 0.0f;
+    bool outside = true;     // ... of every light's lobe
+    for (int k = 0; k < a.n_lights; k++) {
+      const float ex = a.lsx[k] - f.cx, ey = a.lsy[k] - f.cy;
+      const float dist = lf_sqrt(fmaf(ex, ex, ey * ey));
+      const float id = dist > 0.0f ? lf_rcp(dist) : 0.0f;
+      outside = outside && dist - a.lobe_k * extent(f, ex * id, ey * id) > a.lrho[k];
+    }
     if (partial && (a.keep_partial || a.strict == 1 || (a.strict == 2 && tir_partial))) { keep = true; why = 1; }
-    else if (dist - a.lobe_k * extent(f, ex * id, ey * id) > a.rho && !(a.disable & 4)) { culled = true; why = 6; }
+    else if (outside && !(a.disable & 4)) { culled = true; why = 6; }
     else { keep = true; why = partial ? 1 : 3; }
   }
   if (stats && valid && why) atomicAdd(&stats[why], 1ull);
@@ -552,6 +560,15 @@ __device__ __forceinline__ bool ship_lobe_culls(const ShipFoot& f, float geo_mar
   return dist - kShipLobeK * ship_extent(f, geo_margin, ex * id, ey * id) > rho;
 }
 
+// several lights: the lights (bits of `live`) whose lobe the footprint can still reach
+// (A: the kernel's arguments, CullLevelArgs / CullResolveArgs -- n_lights, lsx, lsy, lrho; k is uniform, the reads scalar)
+template <class A>
+__device__ __forceinline__ unsigned ship_lobes_reached(const ShipFoot& f, float geo_margin, unsigned live, const A& a) {
+  for (int k = 0; k < a.n_lights; k++)
+    if (((live >> k) & 1u) != 0u && ship_lobe_culls(f, geo_margin, a.lsx[k], a.lsy[k], a.lrho[k])) live &= ~(1u << k);
+  return live;
+}
+
 // ---- the sun-independent part of the pre-pass, cached (lfk_cull_prepass) ------------------------------------------
 // Everything a box's fate depends on before the lobe test -- the lens, the frame, the blocks, the mask's grid, the pairs, the
 // rank's share -- stays the same while the sun moves.  The cache holds, per level and (path, own block, cell), one slot:
@@ -569,7 +586,8 @@ struct CullCacheOut {
 
 // BUILD = false: the pre-pass as it ships (k_cull_level).  BUILD = true (k_cull_level_build): the same rules up to the lobe
 // test, which is replaced by "emit the box's slot and footprint"; children of kept AND undecided boxes are listed.
-template <bool BUILD>
+// LIGHTS: the lobe test runs over the lights of CullLevelArgs (several: k_cull_level_lights) instead of the one sun
+template <bool BUILD, bool LIGHTS = false>
 __device__ __forceinline__ void cull_level_body(const LfLensDev* __restrict__ lens,
                                                     const LfPairsDev* __restrict__ pairs,
                                                     const int* __restrict__ seq_table,
@@ -760,7 +778,9 @@ __device__ __forceinline__ void cull_level_body(const LfLensDev* __restrict__ le
     if (__ballot(!culled && !keep) != 0ull) {
       const ShipFoot f = ship_footprint<true>(r, a.margin, 2e-5f);
       if (!culled && !keep) {
-        if (ship_lobe_culls(f, a.geo_margin, a.sx, a.sy, a.rho)) { culled = true; why = 6; }
+        const bool out = LIGHTS ? ship_lobes_reached(f, a.geo_margin, (1u << a.n_lights) - 1u, a) == 0u
+                                : ship_lobe_culls(f, a.geo_margin, a.sx, a.sy, a.rho);
+        if (out) { culled = true; why = 6; }
         else { keep = true; why = 3; }
       }
     }
@@ -814,6 +834,17 @@ __global__ __launch_bounds__(LF_CULL_WG, LF_CULL_WAVES) void k_cull_level(const 
                                                     unsigned long long* __restrict__ stats) {
   cull_level_body<false>(lens, pairs, seq_table, rec_table, a, items, counts, items_stride, next, next_counts, table, stats, CullCacheOut{});
 }
+__global__ __launch_bounds__(LF_CULL_WG, LF_CULL_WAVES) void k_cull_level_lights(const LfLensDev* __restrict__ lens,
+                                                    const LfPairsDev* __restrict__ pairs,
+                                                    const int* __restrict__ seq_table,
+                                                    const LfProgRow* __restrict__ rec_table, CullLevelArgs a,
+                                                    const unsigned* __restrict__ items,
+                                                    const unsigned* __restrict__ counts, unsigned items_stride,
+                                                    unsigned* __restrict__ next, unsigned* __restrict__ next_counts,
+                                                    unsigned long long* __restrict__ table,
+                                                    unsigned long long* __restrict__ stats) {
+  cull_level_body<false, true>(lens, pairs, seq_table, rec_table, a, items, counts, items_stride, next, next_counts, table, stats, CullCacheOut{});
+}
 __global__ __launch_bounds__(LF_CULL_WG, LF_CULL_WAVES) void k_cull_level_build(const LfLensDev* __restrict__ lens,
                                                     const LfPairsDev* __restrict__ pairs,
                                                     const int* __restrict__ seq_table,
@@ -837,7 +868,13 @@ struct CullResolveArgs {
   float sx, sy, rho, geo_margin;
   const unsigned* slots[kCullMaxLevels];
   const float4* foots[kCullMaxLevels];
+  int n_lights;                                // several lights (LIGHTS): as CullLevelArgs'
+  float lsx[LF_MAX_LIGHTS], lsy[LF_MAX_LIGHTS], lrho[LF_MAX_LIGHTS];
 };
+// LIGHTS: per lane a mask of the lights still alive instead of `alive`: an undecided ancestor clears the lights whose lobe
+// its footprint cannot reach, the path's bit is set if any light survives to the finest level -- light k's bit survives exactly
+// where the single-light walk for light k survives, so the table is the bitwise OR of the lights' single-light tables
+template <bool LIGHTS>
 __global__ __launch_bounds__(256) void k_cull_resolve(CullResolveArgs a, unsigned long long* __restrict__ table) {
   const unsigned wave = blockIdx.x * 4u + (threadIdx.x >> 6);
   if (wave >= a.n_waves) return;
@@ -848,7 +885,26 @@ __global__ __launch_bounds__(256) void k_cull_resolve(CullResolveArgs a, unsigne
   const bool valid = ci < a.P_final && cj < a.P_final;
   const int blk = a.share_rank + a.share_n * (int)own;
   unsigned long long bits = 0ull;
-  for (int q = 0; q < a.n_paths; q++) {
+  for (int q = 0; LIGHTS && q < a.n_paths; q++) {
+    unsigned live = valid ? (1u << a.n_lights) - 1u : 0u;
+    for (int lv = 0; lv < a.n_levels; lv++) {
+      if (__ballot(live != 0u) == 0ull) break;
+      const int sh = a.n_levels - 1 - lv;
+      const int Pl = a.P_final >> sh;
+      if (live != 0u) {
+        const unsigned s = a.slots[lv][((size_t)q * a.n_mine + own) * (size_t)(Pl * Pl) + (size_t)((cj >> sh) * Pl + (ci >> sh))];
+        if (s == kSlotCulled) live = 0u;
+        else if (s >= kSlotFoot) {
+          const float4* const p = a.foots[lv] + (size_t)(s - kSlotFoot) * 3;
+          const float4 v0 = p[0], v1 = p[1], v2 = p[2];
+          const ShipFoot f{v0.x, v0.y, v0.z, v0.w, v1.x, v1.y, v1.z, v1.w, v2.x, v2.y, v2.z, v2.w};
+          live = ship_lobes_reached(f, a.geo_margin, live, a);
+        }
+      }
+    }
+    if (live != 0u) bits |= 1ull << q;
+  }
+  for (int q = 0; !LIGHTS && q < a.n_paths; q++) {
     bool alive = valid;
     for (int lv = 0; lv < a.n_levels; lv++) {
       if (__ballot(alive) == 0ull) break;
@@ -966,6 +1022,9 @@ struct CullAuditArgs {
   int density;
   int blk_first, blk_step;     // the blocks audited: blk_first + k blk_step (all of them; the frame dealt by blocks: this rank's)
 };
+// LIGHTS (several lights): a marched ray of a dropped box refutes the table if it ends inside ANY light's lobe (light_admits:
+// the march's own per-light test)
+template <bool LIGHTS>
 __global__ __launch_bounds__(256) void k_cull_audit(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                                                     const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
                                                     const float* __restrict__ mask, CullAuditArgs a,
@@ -1023,8 +1082,15 @@ __global__ __launch_bounds__(256) void k_cull_audit(const LfLensDev* __restrict_
         }
       }
       if (alive == 0ull) continue;
-      const float cg = fmaf(r.dx, sx, fmaf(r.dy, sy, r.dz * sz));
-      const bool lit = ((alive >> lane) & 1ull) != 0ull && cg > a.lobe_thr && lobe_q(r.dx, r.dy, r.dz, sx, sy, sz, sun_ss, inv_1mc) < 1.0f;
+      bool lit;
+      if (LIGHTS) {
+        lit = false;
+        for (int k = 0; k < lens->n_lights; k++) { float qk; lit = light_admits(lens, k, r.dx, r.dy, r.dz, qk) || lit; }
+        lit = lit && ((alive >> lane) & 1ull) != 0ull;
+      } else {
+        const float cg = fmaf(r.dx, sx, fmaf(r.dy, sy, r.dz * sz));
+        lit = ((alive >> lane) & 1ull) != 0ull && cg > a.lobe_thr && lobe_q(r.dx, r.dy, r.dz, sx, sy, sz, sun_ss, inv_1mc) < 1.0f;
+      }
       n_lit += lit ? 1u : 0u;
     }
   }
@@ -1075,7 +1141,13 @@ lf_status lfk_cull_finish(lf_ctx* ctx, uint64_t hash) {
     a.blk_first = own_rank; a.blk_step = own_n;
     const dim3 grid((unsigned)((ctx->cull_cells + 255) / 256), (unsigned)n_own_blk);
     hipEvent_t ev = lf_timing_begin(ctx, LFK_CULL_AUDIT);
-    hipLaunchKernelGGL(k_cull_audit, grid, dim3(256), 0, ctx->stream, ctx->lens_dev, ctx->pairs_dev,
+    // (the audit sees every light of the context, whatever the table was built for: lf_test_knob("cull_ignore_light"))
+    if (L.n_lights > 1)
+      hipLaunchKernelGGL(k_cull_audit<true>, grid, dim3(256), 0, ctx->stream, ctx->lens_dev, ctx->pairs_dev,
+                         (const int*)(ctx->prog_dev + ctx->prog_seq_off), (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),
+                         audit_mask, a, ctx->cull_dev, ctx->cull_popc_dev + 1);
+    else
+    hipLaunchKernelGGL(k_cull_audit<false>, grid, dim3(256), 0, ctx->stream, ctx->lens_dev, ctx->pairs_dev,
                        (const int*)(ctx->prog_dev + ctx->prog_seq_off), (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),
                        audit_mask, a, ctx->cull_dev, ctx->cull_popc_dev + 1);
     lf_timing_end(ctx, LFK_CULL_AUDIT, ev);
@@ -1281,6 +1353,13 @@ static uint64_t cull_inputs_hash(const lf_ctx* ctx, CullLevelArgs a, const int* 
     L.sun_dir[0] = L.sun_dir[1] = L.sun_dir[2] = 0.0f;
     L.sun_radiance[0] = L.sun_radiance[1] = L.sun_radiance[2] = 0.0f;
     L.sun_inv_one_minus_cos = L.sun_ss = 0.0f;
+    // ... and every light's (lf_set_lights): the tree does not depend on how many lights there are, or where
+    a.n_lights = 0;
+    std::memset(a.lsx, 0, sizeof(a.lsx)); std::memset(a.lsy, 0, sizeof(a.lsy)); std::memset(a.lrho, 0, sizeof(a.lrho));
+    L.n_lights = 0;
+    std::memset(L.light_dir, 0, sizeof(L.light_dir)); std::memset(L.light_radiance, 0, sizeof(L.light_radiance));
+    std::memset(L.light_inv_one_minus_cos, 0, sizeof(L.light_inv_one_minus_cos));
+    std::memset(L.light_ss, 0, sizeof(L.light_ss)); std::memset(L.light_thr, 0, sizeof(L.light_thr));
   }
   uint64_t h = 0xcbf29ce484222325ull;
   h = fnv(h, &a, sizeof(a));
@@ -1315,13 +1394,18 @@ lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp) {
   a.march_k = ctx->march_k; a.prog_recs = ctx->pairs.prog_recs;
   a.pupil_h = L.pupil_h; a.vz = L.pupil_z - L.z_sensor; a.geom_norm = L.geom_norm;
   a.stop_h = L.stop_h; a.inv_stop_h = 1.0f / L.stop_h;
-  a.sx = L.sun_dir[0]; a.sy = L.sun_dir[1];
-  {
-    // a ray contributes only if d.s > lobe_thr (lfk_march): |d - s|^2 = 2 - 2 d.s < 2 (1 - thr) for unit vectors,
-    // and the (x, y) projection is no longer than the vector; the float march's directions are unit to ~1e-6
-    const double thr = 1.0 - (1.0625 / (double)L.sun_inv_one_minus_cos) * (1.0 + 1e-6) - 4e-7;
-    a.rho = (float)(std::sqrt(2.0 * (1.0 - thr)) * 1.001 + 1e-5);
+  // the lights the table is built for: all of the context's (light 0 = the sun of lf_set_sun) -- a test leaves one out
+  // (lf_test_knob("cull_ignore_light"): a table wrong by construction, which the audit must refute)
+  for (int k = 0; k < std::max(1, L.n_lights); k++) {
+    if (L.n_lights > 1 && k == ctx->cull_ignore_light) continue;
+    const bool sun = L.n_lights <= 1;
+    a.lsx[a.n_lights] = sun ? L.sun_dir[0] : L.light_dir[k][0];
+    a.lsy[a.n_lights] = sun ? L.sun_dir[1] : L.light_dir[k][1];
+    a.lrho[a.n_lights] = lf_cull_lobe_rho(sun ? L.sun_inv_one_minus_cos : L.light_inv_one_minus_cos[k]);
+    a.n_lights++;
   }
+  a.sx = a.lsx[0]; a.sy = a.lsy[0]; a.rho = a.lrho[0];
+  const bool lights = a.n_lights > 1;
   std::memcpy(a.occ, ctx->cull_occ, sizeof(a.occ));
   a.keep_partial = R.keep_partial; a.lost_rel = R.lost_rel; a.lost_abs = R.lost_abs; a.strict = R.strict; a.lobe_k = R.lobe_k;
   a.strict_lost = R.strict_lost; a.slack_mode = R.slack_mode; a.disable = R.disable;
@@ -1409,15 +1493,18 @@ lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp) {
     ra.share_rank = a.share_rank; ra.share_n = a.share_n; ra.share_nb = a.share_nb;
     ra.n_mine = C.n_mine; ra.n_waves = C.n_mine * (unsigned)(ra.patches * ra.patches);
     ra.sx = a.sx; ra.sy = a.sy; ra.rho = a.rho; ra.geo_margin = R.margin;
+    ra.n_lights = a.n_lights;
+    std::memcpy(ra.lsx, a.lsx, sizeof(ra.lsx)); std::memcpy(ra.lsy, a.lsy, sizeof(ra.lsy)); std::memcpy(ra.lrho, a.lrho, sizeof(ra.lrho));
     for (int lv = 0; lv < C.n_levels; lv++) { ra.slots[lv] = C.slots + C.slot_off[lv]; ra.foots[lv] = (const float4*)C.foots[lv]; }
-    hipLaunchKernelGGL(k_cull_resolve, dim3((ra.n_waves + 3u) / 4u), dim3(256), 0, ctx->stream, ra, ctx->cull_dev);
+    if (lights) hipLaunchKernelGGL(k_cull_resolve<true>, dim3((ra.n_waves + 3u) / 4u), dim3(256), 0, ctx->stream, ra, ctx->cull_dev);
+    else hipLaunchKernelGGL(k_cull_resolve<false>, dim3((ra.n_waves + 3u) / 4u), dim3(256), 0, ctx->stream, ra, ctx->cull_dev);
     LF_HIP(ctx, hipGetLastError());
   } else {
     std::chrono::steady_clock::time_point t_lv;      // (stats_dev: experiments only -- why the boxes of a level ended as they did)
     auto launch = [&](CullLevelRun& run) -> lf_status {
       if (stats_dev) LF_HIP(ctx, hipMemsetAsync(stats_dev, 0, 32 * sizeof(unsigned long long), ctx->stream));
       if (stats_dev) { LF_HIP(ctx, hipStreamSynchronize(ctx->stream)); t_lv = std::chrono::steady_clock::now(); }
-      cull_launch_level(ctx, ctx->cull_rules_custom ? k_cull_level_general : k_cull_level, run, ctx->cull_dev, stats_dev);
+      cull_launch_level(ctx, ctx->cull_rules_custom ? k_cull_level_general : lights ? k_cull_level_lights : k_cull_level, run, ctx->cull_dev, stats_dev);
       return LF_OK;
     };
     auto after = [&](CullLevelRun& run) -> lf_status {

@@ -265,7 +265,7 @@ __global__ void k_frame_setup(const LfParaxialLens* __restrict__ plp, LfCamera c
       const double PI_ = 3.14159265358979323;
       double edge_x = tan(0.5 * (cam.hfov_deg * (PI_ / 180.0)));
       double edge_y = tan(0.5 * (cam.vfov_deg * (PI_ / 180.0)));
-      int n = 0;
+      int n = 0, n_in = 0;
       const double* lights = lights_mem ? lights_mem : light_args.v;
       for (int l = 0; l < n_lights; l++) {
         double dx = lights[6 * l] - cam.pos[0], dy = lights[6 * l + 1] - cam.pos[1],
@@ -277,6 +277,7 @@ __global__ void k_frame_setup(const LfParaxialLens* __restrict__ plp, LfCamera c
         double rc = 1.0 / fabs(pz);
         double nx = (((rc * px) / edge_x) + 1) / 2.0;
         double ny = (((rc * py) / edge_y) + 1) / 2.0;
+        if ((nx >= 0 && nx <= 1) && (ny >= 0 && ny <= 1)) n_in++;
         if ((nx >= 0 && nx <= 1) && (ny >= 0 && ny <= 1) && n < LF_MAX_FLARES) {
           fl->origin[n][0] = nx; fl->origin[n][1] = ny;
           fl->radiance[n][0] = lights[6 * l + 3];
@@ -288,6 +289,7 @@ __global__ void k_frame_setup(const LfParaxialLens* __restrict__ plp, LfCamera c
         }
       }
       fl->n_flares = n;
+      fl->n_in_frame = n_in;
     }
     __threadfence_block();
     __syncthreads();

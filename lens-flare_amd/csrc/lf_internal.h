@@ -31,6 +31,8 @@ struct LfFlares {
   double origin[LF_MAX_FLARES][2];
   double radiance[LF_MAX_FLARES][3];
   double axis_ray[2];
+  int n_in_frame;   // in-frame lights find_sun_pos met, those beyond LF_MAX_FLARES (kept by nobody) included
+  int pad;
 };
 
 // One rasterisable ghost triangle, vertices already y-sorted and shifted by -0.5
@@ -117,6 +119,14 @@ struct LfLensDev {
   float lambda_rgb[LF_MAX_LAMBDA][3];
   float n_start[LF_MAX_LAMBDA];  // index of the medium between the last interface and the sensor
   LfSurfaceDev surf[LF_MAX_SURFACES];
+  // Every light of the march (lf_set_lights), light 0 among them: the sun_* fields above ARE light 0, which is all a
+  // single-light kernel reads.  Behind everything else, so that no field a single-light kernel reads has moved.
+  int n_lights;
+  float light_dir[LF_MAX_LIGHTS][3];
+  float light_radiance[LF_MAX_LIGHTS][3];
+  float light_inv_one_minus_cos[LF_MAX_LIGHTS];
+  float light_ss[LF_MAX_LIGHTS];
+  float light_thr[LF_MAX_LIGHTS];   // lf_march_lobe_thr of light k (light 0's also travels as MarchArgs::lobe_thr)
 };
 
 struct LfPairsDev {
@@ -443,6 +453,7 @@ struct lf_ctx {
   // geometric
   LfLensDev lens{};
   bool lens_valid = false, sun_valid = false;
+  float light_radius[LF_MAX_LIGHTS] = {};   // the angular radii as lf_set_lights was given them (lf_get_lights)
   // the sampling specification's two coherence parameters (round 4 defaults, measured on the bench frame:
   // profiles/r04_tile_stride.json): 64 x 64 pupil sub-cells per stratum, shared by the 64 pixels of a wave
   // whose columns are 8 apart -- 108 ms and a tile correlation of 7.4 where rounds 1-3 (4 x 4 sub-cells,
@@ -504,6 +515,7 @@ struct lf_ctx {
   bool cull_rules_custom = false;              // a test installed rules / asked for the general kernel (lf_test_knob)
   bool cull_force = false;                     // lf_test_knob("cull_force"): the culled kernel whatever the table starts
   bool cull_weights_first = false;             // lf_test_knob("cull_weights_first"): k_march_cull<K, true>
+  int cull_ignore_light = -1;                  // lf_test_knob("cull_ignore_light"): the pre-pass / resolve leave this light out (a table wrong by construction)
   bool cull_no_prefix = false;                 // lf_test_knob("cull_no_prefix"): every started path marched alone from the sensor (round 5)
   int scene_compact = -1;                      // lf_test_knob("scene_compact"): -1 = by the tree's size, 0 / 1 forced
   bool comm_force_exchange = false;            // lf_test_knob("comm_force_exchange"): the collectives also with one rank
@@ -570,11 +582,19 @@ void lf_timing_end(lf_ctx* ctx, int kernel, hipEvent_t start, hipStream_t stream
 // 1 - 1.0625 (1 - cos alpha) - 4e-7 MAY lie inside the lobe.  The 1/16 margin is relative, the 4e-7 absolute: the float
 // dot product of two unit vectors is only good to ~2e-7, so a relative margin alone loses part of a sub-milliradian
 // sun's lobe (1 - cos(0.8 mrad) = 3.2e-7).  Rounded down: float(thr) never exceeds thr.
-inline float lf_march_lobe_thr(const LfLensDev& L) {
-  const double thr = 1.0 - (1.0625 / (double)L.sun_inv_one_minus_cos) * (1.0 + 1e-6) - 4e-7;
+inline float lf_march_lobe_thr_of(float inv_one_minus_cos) {
+  const double thr = 1.0 - (1.0625 / (double)inv_one_minus_cos) * (1.0 + 1e-6) - 4e-7;
   float t = (float)thr;
   if ((double)t > thr) t = std::nextafterf(t, -2.0f);
   return t;
+}
+inline float lf_march_lobe_thr(const LfLensDev& L) { return lf_march_lobe_thr_of(L.sun_inv_one_minus_cos); }
+// the radius, in (x, y) direction space, of what the pre-test admits around a light: the cull pre-pass's lobe test
+// (a ray contributes only if d.s > lobe_thr: |d - s|^2 = 2 - 2 d.s < 2 (1 - thr) for unit vectors, and the (x, y)
+// projection is no longer than the vector; the float march's directions are unit to ~1e-6)
+inline float lf_cull_lobe_rho(float inv_one_minus_cos) {
+  const double thr = 1.0 - (1.0625 / (double)inv_one_minus_cos) * (1.0 + 1e-6) - 4e-7;
+  return (float)(std::sqrt(2.0 * (1.0 - thr)) * 1.001 + 1e-5);
 }
 
 inline LfDeal lf_deal_of(const lf_ctx* ctx) {
@@ -592,9 +612,9 @@ inline void lf_install_split(lf_ctx* ctx, const LfSplit& s) {
   }
   ctx->split = s;
 }
-// the kernel variant of the weighted march (lf_march_events.h: kVarBare .. kVarCoatFilt)
+// the kernel variant of the weighted march (lf_march_events.h: kVarBare .. kVarCoatFilt, | kVarLights: several lights)
 inline int lf_march_variant(const lf_ctx* ctx) {
-  return (ctx->coat.n > 0 ? 1 : 0) | (ctx->mask_filter == LF_MASK_BILINEAR ? 2 : 0);
+  return (ctx->coat.n > 0 ? 1 : 0) | (ctx->mask_filter == LF_MASK_BILINEAR ? 2 : 0) | (ctx->lens.n_lights > 1 ? 4 : 0);
 }
 // the cull table is not this context's alone: shared between ranks, or built only in part (the frame dealt by blocks)
 inline bool lf_cull_table_split(const lf_ctx* ctx) {

@@ -123,6 +123,9 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
   __shared__ unsigned long long s_acc[64 * 3];
   __shared__ unsigned long long s_cnt[kMarchCounters];
   __shared__ int s_next;
+  // several lights (VAR & kVarLights): radiance_k[c] * lambda_rgb[l][c] per light (lights_channel_factors); a kernel of one
+  // light never names it
+  __shared__ float s_chan[(VAR & kVarLights) ? kLightChan : 1];
 #ifdef LF_MARCH_LIVE_HIST
   // instrumented build (profiles/r03_march_variants.txt), never shipped: executed wave-ray events by
   // the number of live lanes, bucket = lanes / 8 (8 = all 64)
@@ -164,6 +167,7 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
   if (tid < 64 * 3) s_acc[tid] = 0ull;
   if (tid < kMarchCounters) s_cnt[tid] = 0ull;
   if (tid == 0) s_next = 0;
+  if (VAR & kVarLights) lights_channel_factors(lens, s_chan, tid, 64 * kWgWaves);
   __syncthreads();
 
   // a wave's 64 pixels: 8 rows x 8 columns that are 2^xs apart; 2^xs such waves interleave in a block of
@@ -508,8 +512,10 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
             // with a 1/16 margin computed once on the host; the lobe factor itself is evaluated
             // without cancellation after the weight re-march, see lobe_q, and decides)
             lanemask lit[K], lit_any = 0ull;
+            if (VAR & kVarLights) lit_any = lights_pretest<K, !kW1>(lens, r, alive, lit);
 #pragma unroll
             for (int j = 0; j < K; j++) {
+              if (VAR & kVarLights) break;
               const float cg = fmaf(r[j].dx, sx, fmaf(r[j].dy, sy, r[j].dz * sz));
               lit[j] = alive[j] & __ballot(cg > lobe_thr);
               lit_any |= lit[j];
@@ -531,7 +537,7 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
             }
 #endif
             // (the epilogue's exact test, made before the re-march instead of after it: lobe_gate)
-            if (!kW1 && lit_any != 0ull) lit_any = lobe_gate<K>(r, lit, sx, sy, sz, sun_ss, inv_1mc);
+            if (!(VAR & kVarLights) && !kW1 && lit_any != 0ull) lit_any = lobe_gate<K>(r, lit, sx, sy, sz, sun_ss, inv_1mc);
             if (lit_any != 0ull) {
               // rare (about 1 % of the wave-paths): march this path again, alone and with the
               // weight, along its own row sequence -- once per wavelength that has a lit lane
@@ -580,6 +586,10 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
                 // (selects, not branches: with no divergent branch anywhere in the walk the compiler
                 // keeps its control flow as plain scalar branches)
                 // (the re-march reproduces the first pass bit for bit: rw's direction is r[j]'s)
+                if (VAR & kVarLights) {
+                  lights_epilogue(lens, s_chan, rw, ((lj >> lane) & 1ull) != 0ull, l, &s_acc[lane * 3], n_light);
+                  continue;
+                }
                 const float qq = lobe_q(rw.dx, rw.dy, rw.dz, sx, sy, sz, sun_ss, inv_1mc);
                 const float om = 1.0f - qq;
                 float contrib = __fdiv_rn(rw.wn, rw.wd) * (om * om);
@@ -741,7 +751,11 @@ int lf_march_fix_bits(const LfLensDev& L, int n_paths, int spp) {
   double worst = 0.0;
   for (int c = 0; c < 3; c++) {
     double s = 0.0;
-    for (int l = 0; l < L.n_lambda; l++) s += (double)(L.sun_radiance[c] * L.lambda_rgb[l][c]);
+    // (several lights: a ray may lie in every lobe -- the sum over lights of what each can add)
+    for (int k = 0; k < std::max(1, L.n_lights); k++) {
+      const float rad = L.n_lights > 0 ? L.light_radiance[k][c] : L.sun_radiance[c];
+      for (int l = 0; l < L.n_lambda; l++) s += (double)(rad * L.lambda_rgb[l][c]);
+    }
     worst = std::max(worst, s);
   }
   worst *= (double)spp * (double)n_paths * (double)L.geom_norm;
@@ -769,13 +783,18 @@ void lf_derive_lens(lf_ctx* ctx, int n, int stop, int n_lambda, const float* rad
                     const float* thickness, const float* ior, const float* semi_ap,
                     float sensor_w_mm) {
   LfLensDev& L = ctx->lens;
-  // keep the sun across a lens change
-  float keep_sun_dir[3], keep_sun_rad[3], keep_inv = L.sun_inv_one_minus_cos, keep_ss = L.sun_ss;
-  for (int c = 0; c < 3; c++) { keep_sun_dir[c] = L.sun_dir[c]; keep_sun_rad[c] = L.sun_radiance[c]; }
+  // keep the lights (the sun is light 0) across a lens change
+  const LfLensDev keep = L;
   std::memset(&L, 0, sizeof(L));
-  for (int c = 0; c < 3; c++) { L.sun_dir[c] = keep_sun_dir[c]; L.sun_radiance[c] = keep_sun_rad[c]; }
-  L.sun_inv_one_minus_cos = keep_inv;
-  L.sun_ss = keep_ss;
+  for (int c = 0; c < 3; c++) { L.sun_dir[c] = keep.sun_dir[c]; L.sun_radiance[c] = keep.sun_radiance[c]; }
+  L.sun_inv_one_minus_cos = keep.sun_inv_one_minus_cos;
+  L.sun_ss = keep.sun_ss;
+  L.n_lights = keep.n_lights;
+  std::memcpy(L.light_dir, keep.light_dir, sizeof(L.light_dir));
+  std::memcpy(L.light_radiance, keep.light_radiance, sizeof(L.light_radiance));
+  std::memcpy(L.light_inv_one_minus_cos, keep.light_inv_one_minus_cos, sizeof(L.light_inv_one_minus_cos));
+  std::memcpy(L.light_ss, keep.light_ss, sizeof(L.light_ss));
+  std::memcpy(L.light_thr, keep.light_thr, sizeof(L.light_thr));
   L.n_surf = n; L.stop = stop; L.n_lambda = n_lambda;
   float z = 0.0f;
   for (int k = 0; k < n; k++) {
@@ -1189,6 +1208,8 @@ static lf_status march_upload(lf_ctx* ctx, int spp, int total_paths = 0) {
     ctx->march_fix_bits = bits;
     LfLensDev up = ctx->lens;
     for (int c = 0; c < 3; c++) up.sun_radiance[c] = std::ldexp(ctx->lens.sun_radiance[c], bits - 36);
+    for (int k = 0; k < up.n_lights; k++)
+      for (int c = 0; c < 3; c++) up.light_radiance[k][c] = std::ldexp(ctx->lens.light_radiance[k][c], bits - 36);
     // (pageable source of an asynchronous copy: the runtime stages it before the call returns)
     LF_HIP(ctx, hipMemcpyAsync(ctx->lens_dev, &up, sizeof(LfLensDev), hipMemcpyHostToDevice, ctx->stream));
   }
@@ -1356,7 +1377,11 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
   } else {
   hipEvent_t ev = lf_timing_begin(ctx, LFK_MARCH);
 #define LF_LAUNCH_MARCH(KK)  do { switch (lf_march_variant(ctx)) { case kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarCoatFilt); break; case kVarFilt: LF_LAUNCH_MARCH2(KK, kVarFilt); break; \
-                                   case kVarCoat: LF_LAUNCH_MARCH2(KK, kVarCoat); break; default: LF_LAUNCH_MARCH2(KK, kVarBare); break; } } while (0)
+                                   case kVarCoat: LF_LAUNCH_MARCH2(KK, kVarCoat); break; case kVarBare: LF_LAUNCH_MARCH2(KK, kVarBare); break; \
+                                   case kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarLights | kVarCoatFilt); break; \
+                                   case kVarLights | kVarFilt: LF_LAUNCH_MARCH2(KK, kVarLights | kVarFilt); break; \
+                                   case kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarLights | kVarCoat); break; \
+                                   default: LF_LAUNCH_MARCH2(KK, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_MARCH2(KK, CC)                                                                   \
   hipLaunchKernelGGL((k_march<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                \
@@ -1461,7 +1486,7 @@ lf_status lfk_lens_rays(lf_ctx* ctx, int lambda, int n, const float* d_xy, const
 #define LF_LAUNCH_LENS_RAYS(VV)                                                                         \
   hipLaunchKernelGGL(k_lens_rays<VV>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,     \
                      ctx->lens_dev, ctx->primary_dev, m.texels, m.w, m.h, lambda, n, d_xy, d_uv, d_out)
-  switch (lf_march_variant(ctx)) {
+  switch (lf_march_variant(ctx) & kVarCoatFilt) {      // (a primary path knows no light)
     case kVarCoatFilt: LF_LAUNCH_LENS_RAYS(kVarCoatFilt); break;
     case kVarFilt: LF_LAUNCH_LENS_RAYS(kVarFilt); break;
     case kVarCoat: LF_LAUNCH_LENS_RAYS(kVarCoat); break;

@@ -46,6 +46,85 @@ __device__ __forceinline__ lanemask lobe_gate(const Ray (&r)[K], lanemask (&lit)
   return lit_any;
 }
 
+// ---- several lights (lf_set_lights; the kernels instantiated with kVarLights) ------------------------------------------
+// Light k's lobe is the sun's with LfLensDev::light_*[k] in place of sun_*: the same pre-test against light_thr[k], the same
+// lobe_q.  n_lights and every per-light scalar are wave-uniform and come through the scalar cache (k is a loop counter).
+// ONE definition of each step, for every march kernel and the cull table's audit.
+
+// is the direction d inside light k's lobe, exactly as the single-light march decides it: the pre-test d.s_k > thr_k AND
+// lobe_q_k < 1 (q: lobe_q_k, valid where the pre-test holds)
+__device__ __forceinline__ bool light_admits(const LfLensDev* __restrict__ lens, int k, float dx, float dy, float dz, float& q) {
+  const float sx = lens->light_dir[k][0], sy = lens->light_dir[k][1], sz = lens->light_dir[k][2];
+  const float cg = fmaf(dx, sx, fmaf(dy, sy, dz * sz));
+  q = lobe_q(dx, dy, dz, sx, sy, sz, lens->light_ss[k], lens->light_inv_one_minus_cos[k]);
+  return cg > lens->light_thr[k] && q < 1.0f;
+}
+// The pre-test of a completed path's K rays: lit[j] = the lanes of alive[j] that ANY light's pre-test admits (d.s_k > thr_k)
+// and then -- GATE, the geometry-first kernels: what lobe_gate is to one light -- that lie inside ANY light's lobe, so that
+// a wavelength none of whose lanes will contribute to any light is not marched again.  Returns the union of the masks.
+template <int K, bool GATE>
+__device__ __forceinline__ lanemask lights_pretest(const LfLensDev* __restrict__ lens, const Ray (&r)[K], const lanemask (&alive)[K],
+                                                   lanemask (&lit)[K]) {
+  const int n = lens->n_lights;
+  lanemask lit_any = 0ull;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    bool near = false;
+    for (int k = 0; k < n; k++) {
+      const float cg = fmaf(r[j].dx, lens->light_dir[k][0], fmaf(r[j].dy, lens->light_dir[k][1], r[j].dz * lens->light_dir[k][2]));
+      near = near || cg > lens->light_thr[k];
+    }
+    lit[j] = alive[j] & __ballot(near);
+    lit_any |= lit[j];
+  }
+  if (!GATE || lit_any == 0ull) return lit_any;
+  lit_any = 0ull;
+#pragma unroll
+  for (int j = 0; j < K; j++) {
+    if (lit[j] != 0ull) {
+      bool in = false;
+      for (int k = 0; k < n; k++) { float q; in = light_admits(lens, k, r[j].dx, r[j].dy, r[j].dz, q) || in; }
+      lit[j] &= __ballot(in);
+    }
+    lit_any |= lit[j];
+  }
+  return lit_any;
+}
+// What a lit ray's contribution to light k is multiplied by per channel c, for wavelength l: light_radiance[k][c] *
+// lambda_rgb[l][c] (one float multiply, as the single light's) at s_chan[(k * LF_MAX_LAMBDA + l) * 3 + c]: formed once per
+// workgroup, before the kernel's first barrier.
+constexpr int kLightChan = LF_MAX_LIGHTS * LF_MAX_LAMBDA * 3;
+__device__ __forceinline__ void lights_channel_factors(const LfLensDev* __restrict__ lens, float* __restrict__ s_chan, int tid, int n_threads) {
+  for (int i = tid; i < kLightChan; i += n_threads) {
+    const int k = i / (LF_MAX_LAMBDA * 3), lc = i - k * (LF_MAX_LAMBDA * 3), l = lc / 3, c = lc - 3 * l;
+    s_chan[i] = (k < lens->n_lights && l < lens->n_lambda) ? lens->light_radiance[k][c] * lens->lambda_rgb[l][c] : 0.0f;
+  }
+}
+// The lit epilogue, after the ONE weighted re-march of wavelength l (rw: the re-marched ray; mine: this lane is one the
+// pre-test admitted): per light k the single light's arithmetic -- q_k, (1 - q_k)^2 times the weight, kept where the lane
+// lies inside lobe k -- one fixed-point value per (ray, light, channel), converted separately and added to the pixel's
+// three sums at acc; n_light counts (ray, light) contributions.
+__device__ __forceinline__ void lights_epilogue(const LfLensDev* __restrict__ lens, const float* __restrict__ s_chan, const Ray& rw,
+                                                bool mine, int l, unsigned long long* __restrict__ acc, unsigned& n_light) {
+  const int n = lens->n_lights;
+  const float wq = __fdiv_rn(rw.wn, rw.wd);
+  for (int k = 0; k < n; k++) {
+    float qq;
+    const bool in = light_admits(lens, k, rw.dx, rw.dy, rw.dz, qq);
+    const float om = 1.0f - qq;
+    float contrib = wq * (om * om);
+    contrib = (mine && in && contrib > 0.0f) ? contrib : 0.0f;
+    n_light += contrib > 0.0f ? 1u : 0u;
+    const float* const ch = s_chan + (k * LF_MAX_LAMBDA + l) * 3;
+#pragma unroll
+    for (int c = 0; c < 3; c++) {
+      const float v = contrib * ch[c];
+      const unsigned long long fx = (unsigned long long)(v * 68719476736.0f);
+      if (fx) atomicAdd(&acc[c], fx);
+    }
+  }
+}
+
 struct MarchArgs {
   int mw, mh, W, H, y0, y1;
   int spp, G;          // G x G pupil strata, G = floor(sqrt(spp))

@@ -279,7 +279,8 @@ __device__ __forceinline__ lanemask stop_event(Ray& r, float dzv, float h2, floa
 // What the weight of a ray may have to evaluate beyond bare glass and the nearest texel is chosen at compile
 // time, so that a context without it launches the kernels it always launched: bit 0 = a film somewhere on the
 // lens (lf_set_lens_coatings), bit 1 = the bilinear stop mask (lf_set_mask_filter).
-enum : int { kVarBare = 0, kVarCoat = 1, kVarFilt = 2, kVarCoatFilt = 3 };
+enum : int { kVarBare = 0, kVarCoat = 1, kVarFilt = 2, kVarCoatFilt = 3,
+             kVarLights = 4 };   // | kVarLights: the context holds several lights (lf_set_lights): the lobe pre-test and the lit epilogue loop over them
 // The stop of a kernel instantiated for variant VAR.  Under the filter the geometry-only march (W = false) runs
 // the UNCHANGED nearest lookup on the support texture S (2 mw x 2 mh floats behind the texels, k_mask_support:
 // S > 0 exactly where one of the four texels of the bilinear footprint is open), the weighted march the

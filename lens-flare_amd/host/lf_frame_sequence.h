@@ -38,7 +38,8 @@ typedef struct lf_frame_plan {
   int lens_camera_mode;           // 0 pinhole; 1 / 2: the scene through the prescription (needs the counter RNG)
   double world_per_mm, exposure;
   int ghosts;                     // lf_frame_ghosts
-  int sun_from_flares;            // the march's sun = the in-frame light of the flare state (flare 0)
+  int sun_from_flares;            // the march's lights = EVERY in-frame light of the flare state (lf_set_lights_from_flares;
+                                  // one flare: exactly lf_set_sun_from_flares(0))
   float sun_angular_radius;
   int geo_spp;
   uint64_t geo_key;
@@ -66,7 +67,7 @@ static inline lf_status lf_run_frame(lf_ctx* ctx, const lf_frame_plan* p, const 
   // generate_ghost_buffer (pathtracer.cpp:714-817)
   if (p->ghosts == LF_FRAME_GHOSTS_MARCH) {
     if (p->sun_from_flares)
-      LF_FRAME_STEP(lf_set_sun_from_flares(ctx, 0, 0.0, p->sun_angular_radius));
+      LF_FRAME_STEP(lf_set_lights_from_flares(ctx, 0.0, p->sun_angular_radius, NULL));
     LF_FRAME_STEP(lf_trace_ghosts(ctx, p->geo_spp, p->geo_key));
   } else if (p->ghosts == LF_FRAME_GHOSTS_NONE) {
     LF_FRAME_STEP(lf_clear_ghost_buffer(ctx));

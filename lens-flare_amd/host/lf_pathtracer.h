@@ -125,6 +125,12 @@ class PathTracer {
                             const float* thickness, const float* ior, const float* semi_aperture,
                             float sensor_width_mm, const float sun_dir[3], float sun_angular_radius,
                             int spp);
+  // after use_geometric_ghosts: SEVERAL lights in one pass of the march instead of its one sun (lf_set_lights: n x 3
+  // directions with z < 0, n x 3 radiances, n angular radii; the ghost buffer is the sum of the lights' own frames) ...
+  void set_lights(int n_lights, const float* dir, const float* radiance, const float* angular_radius);
+  // ... or every in-frame light of the flare state (flare_origins / flare_radiance as find_sun_pos or the host left
+  // them), taken over by the frame sequence at every generate_ghost_buffer (lf_set_lights_from_flares)
+  void use_lights_from_flares(float angular_radius);
   // replaces PathTracer::bvh / scene (pathtracer.h:116-124): hand the static scene to the device
   // so that the sample loop of raytrace_pixel (BVH closest hit + direct lighting) runs there too;
   // argument layout as lf_set_scene (include/lensflare.h)
@@ -150,6 +156,8 @@ class PathTracer {
   lf_ctx* ctx_ = nullptr;
   bool frame_ready_ = false, textures_uploaded_ = false, geometric_ = false, device_scene_ = false;
   int geo_spp_ = 0;
+  bool lights_from_flares_ = false;
+  float lights_radius_ = 0.05f;
   std::vector<double> star_;    // host mirror of raytrace_starburst for every pixel
   std::vector<double> sample_;  // host mirror of the composed sensor buffer
   std::mutex mu_;

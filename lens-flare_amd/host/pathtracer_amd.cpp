@@ -25,8 +25,9 @@
 //   * LF_LENS_FILE=<prescription.lens> is set in the environment of the unchanged host application;
 //     LF_GEOMETRIC_SPP (default 64), LF_SUN_ANGULAR_RADIUS (radians, default 0.05) and
 //     LF_GEOMETRIC_KEY (counter-RNG key) tune it.
-// generate_ghost_buffer then fills ghost_buffer with lf_trace_ghosts (sun = the in-frame
-// DirectionalLight find_sun_pos found, lf_set_sun_from_flares) instead of the paraxial quads.
+// generate_ghost_buffer then fills ghost_buffer with lf_trace_ghosts (lights = EVERY in-frame
+// DirectionalLight find_sun_pos found, lf_set_lights_from_flares: one march for all of them;
+// more than LF_MAX_LIGHTS in the frame is refused) instead of the paraxial quads.
 //
 // Built and exercised as test infrastructure by oracle/Makefile (targets `dropin`, `app`: the
 // reference's other objects -- raytraced_renderer.o included -- linked unmodified, pathtracer.o

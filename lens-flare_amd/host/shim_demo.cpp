@@ -99,8 +99,59 @@ static int geo_main(int argc, char** argv) {
   return 0;
 }
 
+// shim_demo geolights <lens.txt> <mask.f32> <mw> <mh> <W> <H> <spp> <angular radius> <outprefix> <n> then n x {ox oy r g b}
+// Several in-frame lights through the mirror's frame sequence: the flare state as a host leaves it in the public fields
+// (normalised screen positions, radiances), PathTracer::use_lights_from_flares, generate_ghost_buffer -- every light gets
+// its lens ghosts in ONE march.
+static int geolights_main(int argc, char** argv) {
+  if (argc < 12) return 1;
+  std::ifstream in(argv[2]);
+  int n, stop, nl;
+  float sensor_w;
+  in >> n >> stop >> nl >> sensor_w;
+  std::vector<float> radius(n), thick(n), semi(n), ior((size_t)n * nl);
+  for (int k = 0; k < n; k++) {
+    in >> radius[k] >> thick[k] >> semi[k];
+    for (int l = 0; l < nl; l++) in >> ior[(size_t)l * n + k];
+  }
+  const size_t mw = atoi(argv[4]), mh = atoi(argv[5]), W = atoi(argv[6]), H = atoi(argv[7]);
+  const int spp = atoi(argv[8]);
+  const float alpha = (float)atof(argv[9]);
+  const std::string out = argv[10];
+  const int n_lights = atoi(argv[11]);
+  if (argc < 12 + 5 * n_lights) return 1;
+  try {
+    PathTracer pt(0);
+    Camera cam;
+    CameraApertureTexture ap;
+    ap.init_from_texels(read_f32(argv[3], mw * mh).data(), mw, mh);
+    cam.aperture_texture = &ap;
+    cam.ghost_aperture_texture = &ap;
+    pt.clear();
+    pt.set_frame_size(W, H);
+    pt.camera = &cam;
+    pt.counter_jitter = true;
+    for (int k = 0; k < n_lights; k++) {
+      char** v = argv + 12 + 5 * k;
+      pt.flare_origins.emplace_back(atof(v[0]), atof(v[1]));
+      pt.flare_radiance.emplace_back(atof(v[2]), atof(v[3]), atof(v[4]));
+    }
+    pt.axis_ray = Vector2D(0.5, 0.5);
+    const float placeholder[3] = {0.0f, 0.0f, -1.0f};      // (replaced by the flare state's lights at the frame)
+    pt.use_geometric_ghosts(n, stop, nl, radius.data(), thick.data(), ior.data(), semi.data(), sensor_w, placeholder, alpha, spp);
+    pt.use_lights_from_flares(alpha);
+    pt.generate_ghost_buffer();
+    dump(out + ".ghost.f64", &pt.ghost_buffer.data[0].x, W * H * 3);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "shim_demo geolights: %s\n", e.what());
+    return 3;
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && std::string(argv[1]) == "geo") return geo_main(argc, argv);
+  if (argc > 1 && std::string(argv[1]) == "geolights") return geolights_main(argc, argv);
   if (argc < 5) return 1;
   std::ifstream in(argv[1]);
   size_t W, H, ns_aa, aw, ah, gw, gh, n_lights;
