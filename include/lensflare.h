@@ -26,6 +26,7 @@ extern "C" {
 #define LF_ABI_VERSION 1
 #define LF_MAX_SURFACES 16   /* interfaces per prescription (incl. the stop) */
 #define LF_MAX_LAMBDA 8      /* wavelengths per prescription */
+#define LF_MAX_COAT_LAYERS 6 /* layers of a coating stack on one interface (lf_set_lens_coating_stacks) */
 #define LF_MAX_FLARES 8      /* in-frame directional lights */
 #define LF_MAX_LIGHTS 8      /* lights one launch of the geometric march follows (lf_set_lights) */
 #define LF_MAX_PAIRS 128     /* ghost pairs per trace call */
@@ -450,9 +451,42 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path);
  * profiles/coating_cost.json); a lens without films runs the kernels it always ran. */
 lf_status lf_set_lens_coatings(lf_ctx* ctx, int n_surfaces, int n_lambda, const float* lambda_nm,
                                const float* thickness_nm, const float* index);
-/* what lf_set_lens_coatings installed (any array may be NULL): zeros and n_coated = 0 for a bare lens */
+/* what lf_set_lens_coatings installed (any array may be NULL): zeros and n_coated = 0 for a bare lens.
+ * LF_ERR_STATE while some interface holds a stack of two or more layers (lf_get_lens_coating_stacks reads those). */
 lf_status lf_get_lens_coatings(lf_ctx* ctx, int n_surfaces, int n_lambda, float* lambda_nm,
                                float* thickness_nm, float* index, int* n_coated);
+/* Multi-layer anti-reflection STACKS: up to LF_MAX_COAT_LAYERS lossless layers per interface.
+ *   n_layers[k]                 layers on interface k, 0 .. LF_MAX_COAT_LAYERS (the stop: 0)
+ *   thickness_nm[j*n + k]       physical thickness of layer j of interface k, nm, in [0, 10000]
+ *   index[(j*L + l)*n + k]      its index at wavelength l (L = n_lambda), finite and >= the smaller of the two indices
+ *                               beside interface k at that wavelength
+ * Layer j = 0 is the one on the SCENE side of the interface: the order is fixed in space, and a ray travelling towards
+ * the scene meets the layers reversed (the library reverses them when it derives each direction's constants).
+ * With cm_j^2 = (n cos t)^2 + m_j^2 - n^2 the rule on the indices keeps the optical cosine cm_j of every layer real
+ * wherever the interface itself does not reflect totally: there is no frustrated total reflection inside a stack.
+ * Layers of thickness 0 are dropped before anything else happens; an interface left with exactly ONE layer is installed
+ * as that single film -- the records, the arithmetic and the kernels of lf_set_lens_coatings, its frames bit for bit --
+ * and only a lens with two or more layers on some interface launches the kernels that evaluate a stack (the
+ * recursive Airy sum of lf_march_events.h stack_fraction: float32, nothing divided, one loop over the layers).
+ * n_layers == NULL clears the stacks.  The two setters replace each other's state; lf_set_lens clears it, lf_focus_lens
+ * keeps it.  Like a film, a stack changes only the weight: the cull table, the counters and the lit pixel set stay those
+ * of the bare lens.  A lens file carries stacks as `layer k thickness_nm m_1 .. m_L` lines (or one m for all
+ * wavelengths), each appending a layer to interface k, scene side first, after a `lambda_nm` line; an interface takes
+ * `layer` lines or a `coating` line, not both.  Not modelled: absorbing layers (complex indices), graded or
+ * dispersive-by-formula films. */
+lf_status lf_set_lens_coating_stacks(lf_ctx* ctx, int n_surfaces, int n_lambda, const float* lambda_nm,
+                                     const int* n_layers, const float* thickness_nm, const float* index);
+/* what is installed, after the drop of zero-thickness layers (a single film of lf_set_lens_coatings reads as one layer);
+ * the arrays are sized as for the setter with LF_MAX_COAT_LAYERS layers (any may be NULL), n_stacked = the interfaces
+ * with two or more layers */
+lf_status lf_get_lens_coating_stacks(lf_ctx* ctx, int n_surfaces, int n_lambda, float* lambda_nm, int* n_layers,
+                                     float* thickness_nm, float* index, int* n_stacked);
+/* host arithmetic, no device (like lf_coating_reflectance): the reflectance of ONE stacked interface in the float32
+ * contract of the march (stack_fraction itself) -- out = {R_s, R_p, R} for a ray arriving in n_in at cosine cos_in; the
+ * layers n_film[i], thickness_nm[i] in the order the RAY meets them; layers of thickness 0 are dropped, one layer left is
+ * lf_coating_reflectance bit for bit, none the bare interface; total reflection gives 1 */
+lf_status lf_coating_stack_reflectance(float n_in, int n_layers, const float* n_film, const float* thickness_nm,
+                                       float n_out, float lambda_nm, float cos_in, float out[3]);
 /* host arithmetic, no device (like lf_paraxial_efl): the coated reflectance of ONE interface in the float32
  * contract of the march -- out = {R_s, R_p, R = (R_s + R_p) / 2} for a ray arriving in n_in at cosine
  * cos_in (in [0, 1]) of its angle of incidence; thickness 0 gives the bare interface, total reflection 1 */

@@ -42,6 +42,7 @@ ABI_SYMBOLS = [
     "lf_clear_ghost_buffer", "lf_draw_ghost", "lf_rasterize_textured_triangle", "lf_fill_textured_pixel",
     "lf_shift_vertex", "lf_compute_phase", "lf_irradiance_falloff", "lf_scene_trace_ray", "lf_scene_shade",
     "lf_load_lens_file", "lf_get_lens_info", "lf_set_lens_coatings", "lf_get_lens_coatings", "lf_coating_reflectance",
+    "lf_set_lens_coating_stacks", "lf_get_lens_coating_stacks", "lf_coating_stack_reflectance",
     "lf_set_mask_filter", "lf_get_mask_filter", "lf_mask_lookup",
     "lf_set_pupil_target", "lf_get_pupil_target", "lf_aim_at_exit_pupil", "lf_paraxial_exit_pupil", "lf_set_ghost_accumulate",
     "lf_set_lens_camera", "lf_get_lens_camera", "lf_set_lens_camera_aim", "lf_paraxial_entrance_pupil", "lf_focus_lens", "lf_focus_lens_from_pupil",
@@ -159,7 +160,7 @@ def load_lens_file(path):
     """Parse a .lens prescription (see data/dgauss11.lens) -> dict of float32 arrays."""
     if not os.path.isabs(path) and not os.path.exists(path):
         path = os.path.join(DATA, path)
-    rows, sensor_w, lambda_nm, coats = [], 36.0, None, []
+    rows, sensor_w, lambda_nm, coats, layers = [], 36.0, None, [], []
     for line in open(path):
         line = line.split("#")[0].strip()
         if not line:
@@ -173,6 +174,9 @@ def load_lens_file(path):
             continue
         if t[0] == "coating":        # coating k thickness_nm m_1 .. m_L | m  (lf_set_lens_coatings)
             coats.append((int(t[1]), float(t[2]), [float(v) for v in t[3:]]))
+            continue
+        if t[0] == "layer":          # layer k thickness_nm m_1 .. m_L | m  (appends to interface k's stack, scene side first)
+            layers.append((int(t[1]), float(t[2]), [float(v) for v in t[3:]]))
             continue
         rows.append([float(v) for v in t])
     rows = np.array(rows, np.float64)
@@ -200,7 +204,49 @@ def load_lens_file(path):
             thick[k] = d
             index[:, k] = m if len(m) == nl else m[0]
         lens["coatings"] = dict(lambda_nm=np.array(lambda_nm, np.float32), thickness_nm=thick, index=index)
+    if layers:
+        if lambda_nm is None:
+            raise ValueError(f"{path}: layer lines need a lambda_nm line (the wavelengths of the index columns)")
+        nl = ior.shape[0]
+        n_layers = np.zeros(n, np.int32)
+        thick = np.zeros((MAX_COAT_LAYERS, n), np.float32)
+        index = np.zeros((MAX_COAT_LAYERS, nl, n), np.float32)
+        coated = {k for k, _, _ in coats}
+        for k, d, m in layers:
+            if not 0 <= k < n or len(m) not in (1, nl):
+                raise ValueError(f"{path}: bad layer line for interface {k}")
+            if k in coated:
+                raise ValueError(f"{path}: interface {k} has a coating line and layer lines")
+            if n_layers[k] >= MAX_COAT_LAYERS:
+                raise ValueError(f"{path}: more than {MAX_COAT_LAYERS} layers on interface {k}")
+            thick[n_layers[k], k] = d
+            index[n_layers[k], :, k] = m if len(m) == nl else m[0]
+            n_layers[k] += 1
+        if coats:                    # a film is a stack of one layer: everything goes through the stacks' setter
+            c = lens.pop("coatings")
+            for k in coated:
+                n_layers[k], thick[0, k], index[0, :, k] = 1, c["thickness_nm"][k], c["index"][:, k]
+        lens["coating_stacks"] = dict(lambda_nm=np.array(lambda_nm, np.float32), n_layers=n_layers, thickness_nm=thick,
+                                      index=index)
     return lens
+
+
+MAX_COAT_LAYERS = 6      # LF_MAX_COAT_LAYERS
+
+
+def coating_stack_reflectance(n_in, n_film, thickness_nm, n_out, lambda_nm, cos_in):
+    """(R_s, R_p, R) of one interface under a stack of layers in the march's float32 arithmetic
+    (lf_coating_stack_reflectance, host only): n_film[i], thickness_nm[i] in the order the ray meets them."""
+    m = np.ascontiguousarray(n_film, np.float32).ravel()
+    d = np.ascontiguousarray(thickness_nm, np.float32).ravel()
+    if len(m) != len(d):
+        raise ValueError("one index and one thickness per layer")
+    out = (C.c_float * 3)()
+    st = load_library().lf_coating_stack_reflectance(C.c_float(n_in), len(m), _fp(m, C.c_float), _fp(d, C.c_float),
+                                                     C.c_float(n_out), C.c_float(lambda_nm), C.c_float(cos_in), out)
+    if st != 0:
+        raise LensFlareError(st, "lf_coating_stack_reflectance")
+    return float(out[0]), float(out[1]), float(out[2])
 
 
 def quarter_wave_thickness(m, lambda_nm):
@@ -659,6 +705,45 @@ class LensFlare:
         if "coatings" in lens:
             c = lens["coatings"]
             self.set_lens_coatings(c["lambda_nm"], c["thickness_nm"], c["index"])
+        if "coating_stacks" in lens:
+            c = lens["coating_stacks"]
+            self.set_lens_coating_stacks(c["lambda_nm"], c["n_layers"], c["thickness_nm"], c["index"])
+
+    def set_lens_coating_stacks(self, lambda_nm, n_layers=None, thickness_nm=None, index=None):
+        """Stacks of layers on the installed lens: lambda_nm[l], n_layers[k] (0 = bare), thickness_nm[j, k] and
+        index[j, l, k] of layer j (0 = the scene side) of interface k; j runs over max(n_layers) layers or more.
+        n_layers None clears every stack."""
+        if n_layers is None:
+            self._ck(self.lib.lf_set_lens_coating_stacks(self.ctx, 0, 0, None, None, None, None))
+            return
+        lam = np.ascontiguousarray(lambda_nm, np.float32).ravel()
+        nl = np.ascontiguousarray(n_layers, np.int32).ravel()
+        d = np.atleast_2d(np.asarray(thickness_nm, np.float32))
+        m = np.asarray(index, np.float32)
+        if m.ndim == 2:              # one index per layer and interface, for every wavelength
+            m = np.repeat(m[:, None, :], len(lam), axis=1)
+        if d.shape[1:] != (len(nl),) or m.shape != (d.shape[0], len(lam), len(nl)):
+            raise ValueError("thickness_nm is (layers, n_surfaces), index (layers, n_lambda, n_surfaces)")
+        # (the arrays always hold MAX_COAT_LAYERS layers: a count beyond that is the library's to refuse)
+        rows = max(MAX_COAT_LAYERS, d.shape[0], int(nl.max()) if len(nl) else 0)
+        d = np.ascontiguousarray(np.concatenate([d, np.zeros((rows - d.shape[0], len(nl)), np.float32)]))
+        m = np.ascontiguousarray(np.concatenate([m, np.zeros((rows - m.shape[0], len(lam), len(nl)), np.float32)]))
+        self._ck(self.lib.lf_set_lens_coating_stacks(self.ctx, len(nl), len(lam), _fp(lam, C.c_float), _fp(nl, C.c_int),
+                                                     _fp(d, C.c_float), _fp(m, C.c_float)))
+
+    def get_lens_coating_stacks(self):
+        """dict(lambda_nm, n_layers, thickness_nm (MAX_COAT_LAYERS x n), index (MAX_COAT_LAYERS x n_lambda x n), n_stacked)
+        of the installed lens, after the drop of zero-thickness layers."""
+        info = self.lens_info()
+        n, nl = info["n"], info["n_lambda"]
+        lam = np.zeros(nl, np.float32)
+        cnt = np.zeros(n, np.int32)
+        d = np.zeros((MAX_COAT_LAYERS, n), np.float32)
+        m = np.zeros((MAX_COAT_LAYERS, nl, n), np.float32)
+        ns = C.c_int()
+        self._ck(self.lib.lf_get_lens_coating_stacks(self.ctx, n, nl, _fp(lam, C.c_float), _fp(cnt, C.c_int),
+                                                     _fp(d, C.c_float), _fp(m, C.c_float), C.byref(ns)))
+        return dict(lambda_nm=lam, n_layers=cnt, thickness_nm=d, index=m, n_stacked=ns.value)
 
     def set_lens_coatings(self, lambda_nm, thickness_nm=None, index=None):
         """Single-layer films on the installed lens: lambda_nm[l] (the index columns' wavelengths), thickness_nm[k]

@@ -219,6 +219,41 @@ void lf_coat_constants(float n, float m, float np, float thickness_nm, float lam
   c->p12a = np2 / q2; c->p12b = m2 / q2;
 }
 
+// host: the record of stack_fraction (lf_march_events.h) for one (interface, direction, wavelength): lf_internal.h
+void lf_stack_constants(float n, float np, int N, const float* m, const float* thickness_nm, float lambda_nm, float* out) {
+  const float n2 = n * n;
+  const int count = N;
+  std::memcpy(&out[0], &count, sizeof(int));
+  float mp = n;   // the medium in front of the layer
+  for (int i = 0; i < N; i++) {
+    const float mi = m[i], mi2 = mi * mi, mp2 = mp * mp;
+    float* o = out + 1 + 5 * i;
+    o[0] = mi2 - n2;
+    o[1] = (2.0f * thickness_nm[i]) / lambda_nm;
+    o[2] = 1.0f / (mp + mi);
+    const float q = std::fmaf(mi2, mp, mp2 * mi);
+    o[3] = mi2 / q; o[4] = mp2 / q;
+    mp = mi;
+  }
+  const float mp2 = mp * mp, np2 = np * np;
+  float* o = out + 1 + 5 * N;
+  o[0] = 1.0f / (mp + np);
+  const float q = std::fmaf(np2, mp, mp2 * np);
+  o[1] = np2 / q; o[2] = mp2 / q;
+}
+
+void lf_stack_constants_of(const LfCoatings& C, int n_surfaces, int n_lambda, int surf, int l, bool plus_z, float n_in,
+                           float n_out, float* out) {
+  const int N = C.n_layers[surf];
+  float m[LF_MAX_COAT_LAYERS], d[LF_MAX_COAT_LAYERS];
+  for (int i = 0; i < N; i++) {
+    const int j = plus_z ? i : N - 1 - i;   // layer 0 lies on the scene side: a ray travelling -z meets it last
+    m[i] = C.layer_index[((size_t)j * n_lambda + l) * n_surfaces + surf];
+    d[i] = C.layer_nm[(size_t)j * n_surfaces + surf];
+  }
+  lf_stack_constants(n_in, n_out, N, m, d, C.lambda_nm[l], out);
+}
+
 extern "C" {
 
 int lf_abi_version(void) { return LF_ABI_VERSION; }
@@ -269,7 +304,7 @@ lf_status lf_create(lf_ctx** out, int device) {
             hipMalloc((void**)&ctx->pairs_dev, sizeof(LfPairsDev)) == hipSuccess &&
             hipMalloc((void**)&ctx->counters_dev, kMarchCounterSlots * sizeof(unsigned long long)) == hipSuccess &&
             hipMalloc((void**)&ctx->scene_counters_dev, kSceneCounters * sizeof(unsigned long long)) == hipSuccess &&
-            hipMalloc((void**)&ctx->primary_dev, sizeof(LfPrimaryDev)) == hipSuccess;
+            hipMalloc((void**)&ctx->primary_dev, sizeof(LfPrimaryDev) + kPrimaryStackBytes) == hipSuccess;
   for (int s = 0; s < 2 && ok; s++)
     ok = hipMalloc((void**)&ctx->ap[s].stats, sizeof(lf_aperture_stats)) == hipSuccess;
   if (!ok) { lf_destroy(ctx); return LF_ERR_OOM; }
@@ -1536,6 +1571,11 @@ lf_status lf_set_lens_coatings(lf_ctx* ctx, int n_surfaces, int n_lambda, const 
     C.thickness_nm[k] = thickness_nm[k];
     for (int l = 0; l < n_lambda; l++)
       C.index[(size_t)l * n_surfaces + k] = thickness_nm[k] > 0.0f ? index[(size_t)l * n_surfaces + k] : 0.0f;
+    if (thickness_nm[k] > 0.0f) {   // (lf_get_lens_coating_stacks reads a film as one layer)
+      C.n_layers[k] = 1;
+      C.layer_nm[k] = thickness_nm[k];
+      for (int l = 0; l < n_lambda; l++) C.layer_index[(size_t)l * n_surfaces + k] = index[(size_t)l * n_surfaces + k];
+    }
   }
   if (C.n == 0) C = LfCoatings{};
   ctx->coat = C;
@@ -1551,10 +1591,120 @@ lf_status lf_get_lens_coatings(lf_ctx* ctx, int n_surfaces, int n_lambda, float*
   if (n_surfaces != ctx->raw_n || n_lambda != ctx->lens.n_lambda)
     return lf_fail(ctx, LF_ERR_INVALID, "lf_get_lens_coatings: sizes differ from the installed lens");
   const LfCoatings& C = ctx->coat;
+  if (C.n_stacked > 0)
+    return lf_fail(ctx, LF_ERR_STATE, "lf_get_lens_coatings: an interface holds a stack of layers (lf_get_lens_coating_stacks)");
   if (lambda_nm) for (int l = 0; l < n_lambda; l++) lambda_nm[l] = C.lambda_nm[l];
   if (thickness_nm) for (int k = 0; k < n_surfaces; k++) thickness_nm[k] = C.thickness_nm[k];
   if (index) for (size_t i = 0; i < (size_t)n_lambda * n_surfaces; i++) index[i] = C.index[i];
   if (n_coated) *n_coated = C.n;
+  return LF_OK;
+}
+
+lf_status lf_set_lens_coating_stacks(lf_ctx* ctx, int n_surfaces, int n_lambda, const float* lambda_nm,
+                                     const int* n_layers, const float* thickness_nm, const float* index) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lens_coating_stacks before lf_set_lens");
+  if (!n_layers) {   // every interface bare
+    ctx->coat = LfCoatings{};
+    ctx->events_dirty = true;
+    ctx->lenscam_dirty = true;
+    return LF_OK;
+  }
+  const LfLensDev& L = ctx->lens;
+  if (n_surfaces != ctx->raw_n || n_lambda != L.n_lambda || !lambda_nm || !thickness_nm || !index)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_coating_stacks: sizes differ from the installed lens (or a NULL array)");
+  for (int l = 0; l < n_lambda; l++)
+    if (!std::isfinite(lambda_nm[l]) || !(lambda_nm[l] > 0.0f))
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_coating_stacks: wavelengths must be finite and > 0 nm");
+  LfCoatings C;
+  for (int l = 0; l < n_lambda; l++) C.lambda_nm[l] = lambda_nm[l];
+  for (int k = 0; k < n_surfaces; k++) {
+    if (n_layers[k] < 0 || n_layers[k] > LF_MAX_COAT_LAYERS)
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_coating_stacks: an interface takes 0 .. LF_MAX_COAT_LAYERS layers");
+    if (n_layers[k] > 0 && k == ctx->raw_stop)
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_coating_stacks: the stop cannot carry a layer");
+    int kept = 0;
+    for (int j = 0; j < n_layers[k]; j++) {
+      const float d = thickness_nm[(size_t)j * n_surfaces + k];
+      if (!std::isfinite(d) || d < 0.0f || d > kCoatMaxThicknessNm)
+        return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_coating_stacks: a thickness must be finite and in [0, 10000] nm");
+      if (d == 0.0f) continue;   // dropped (its index is not read): the layers behind it move up
+      for (int l = 0; l < n_lambda; l++) {
+        const float m = index[((size_t)j * n_lambda + l) * n_surfaces + k];
+        // m >= min(n, n') keeps every layer's cosine real wherever the interface does not reflect totally
+        if (!std::isfinite(m) || !(m >= std::min(L.surf[k].n_before[l], L.surf[k].n_after[l])))
+          return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_coating_stacks: a layer index must be finite and >= the smaller index beside the interface");
+      }
+      C.layer_nm[(size_t)kept * n_surfaces + k] = d;
+      for (int l = 0; l < n_lambda; l++)
+        C.layer_index[((size_t)kept * n_lambda + l) * n_surfaces + k] = index[((size_t)j * n_lambda + l) * n_surfaces + k];
+      kept++;
+    }
+    C.n_layers[k] = kept;
+    if (kept > 0) C.n++;
+    if (kept > 1) C.n_stacked++;
+    if (kept == 1) {   // a single film: lf_set_lens_coatings' state, records and kernels
+      C.thickness_nm[k] = C.layer_nm[k];
+      for (int l = 0; l < n_lambda; l++) C.index[(size_t)l * n_surfaces + k] = C.layer_index[(size_t)l * n_surfaces + k];
+    }
+  }
+  if (C.n == 0) C = LfCoatings{};
+  ctx->coat = C;
+  ctx->events_dirty = true;
+  ctx->lenscam_dirty = true;
+  return LF_OK;
+}
+
+lf_status lf_get_lens_coating_stacks(lf_ctx* ctx, int n_surfaces, int n_lambda, float* lambda_nm, int* n_layers,
+                                     float* thickness_nm, float* index, int* n_stacked) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_get_lens_coating_stacks before lf_set_lens");
+  if (n_surfaces != ctx->raw_n || n_lambda != ctx->lens.n_lambda)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_get_lens_coating_stacks: sizes differ from the installed lens");
+  const LfCoatings& C = ctx->coat;
+  if (lambda_nm) for (int l = 0; l < n_lambda; l++) lambda_nm[l] = C.lambda_nm[l];
+  if (n_layers) for (int k = 0; k < n_surfaces; k++) n_layers[k] = C.n_layers[k];
+  if (thickness_nm) for (size_t i = 0; i < (size_t)LF_MAX_COAT_LAYERS * n_surfaces; i++) thickness_nm[i] = C.layer_nm[i];
+  if (index) for (size_t i = 0; i < (size_t)LF_MAX_COAT_LAYERS * n_lambda * n_surfaces; i++) index[i] = C.layer_index[i];
+  if (n_stacked) *n_stacked = C.n_stacked;
+  return LF_OK;
+}
+
+lf_status lf_coating_stack_reflectance(float n_in, int n_layers, const float* n_film, const float* thickness_nm,
+                                       float n_out, float lambda_nm, float cos_in, float out[3]) {
+  if (!out || n_layers < 0 || n_layers > LF_MAX_COAT_LAYERS || (n_layers > 0 && (!n_film || !thickness_nm)))
+    return LF_ERR_INVALID;
+  if (!std::isfinite(n_in) || !std::isfinite(n_out) || !std::isfinite(lambda_nm) || !std::isfinite(cos_in))
+    return LF_ERR_INVALID;
+  if (!(n_in >= 1.0f) || !(n_out >= 1.0f) || !(lambda_nm > 0.0f) || !(cos_in >= 0.0f) || !(cos_in <= 1.0f))
+    return LF_ERR_INVALID;
+  float m[LF_MAX_COAT_LAYERS], d[LF_MAX_COAT_LAYERS];
+  int N = 0;
+  for (int i = 0; i < n_layers; i++) {
+    if (!std::isfinite(n_film[i]) || !std::isfinite(thickness_nm[i]) || thickness_nm[i] < 0.0f ||
+        thickness_nm[i] > kCoatMaxThicknessNm || !(n_film[i] >= std::min(n_in, n_out)))
+      return LF_ERR_INVALID;
+    if (thickness_nm[i] == 0.0f) continue;
+    m[N] = n_film[i]; d[N] = thickness_nm[i]; N++;
+  }
+  if (N <= 1) return lf_coating_reflectance(n_in, N ? m[0] : n_in, n_out, N ? d[0] : 0.0f, lambda_nm, cos_in, out);
+  // the event's optical cosines, as lf_coating_reflectance
+  const float sq = n_in * cos_in;
+  const float n2 = n_in * n_in, np2 = n_out * n_out;
+  const float k2 = sq * sq + (np2 - n2);
+  if (k2 < 0.0f) { out[0] = out[1] = out[2] = 1.0f; return LF_OK; }   // total reflection
+  const float ct = std::sqrt(k2);
+  float rec[kStackDwords(LF_MAX_COAT_LAYERS)];
+  lf_stack_constants(n_in, n_out, N, m, d, lambda_nm, rec);
+  struct HostLoad {
+    const float* p;
+    int operator()(int i) const { int v; std::memcpy(&v, p + i, sizeof(int)); return v; }
+  };
+  float Rn, Rd, Ns, Ds, Np, Dp;
+  lfm::stack_fraction(sq, ct, HostLoad{rec}, Rn, Rd, &Ns, &Ds, &Np, &Dp);
+  out[0] = Ns / Ds;
+  out[1] = Np / Dp;
+  out[2] = Rn / Rd;
   return LF_OK;
 }
 
@@ -1604,7 +1754,9 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
   // rows: radius thickness n_1 ... n_L semi_aperture; '#' starts a comment; radius 0 with index 0 = the stop
   // optional: `lambda_nm l_1 .. l_L` (the wavelengths of the index columns) and
   // `coating k thickness_nm m_1 .. m_L | m` (a film on interface k: lf_set_lens_coatings; needs lambda_nm)
-  std::vector<std::vector<double>> rows, coats;
+  // `layer k thickness_nm m_1 .. m_L | m` (appends a layer to interface k's stack, scene side first:
+  // lf_set_lens_coating_stacks; needs lambda_nm; not on an interface with a `coating` line)
+  std::vector<std::vector<double>> rows, coats, layers;
   std::vector<double> lambdas;
   bool lambda_line = false, lambda_bad = false;
   double sensor_w = 36.0;
@@ -1614,13 +1766,14 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (char* h = std::strchr(line, '#')) *h = 0;
     std::vector<double> v;
     char* p = line;
-    int keyword = 0;   // 1 sensor_width_mm, 2 lambda_nm, 3 coating
+    int keyword = 0;   // 1 sensor_width_mm, 2 lambda_nm, 3 coating, 4 layer
     while (*p) {
       while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') p++;
       if (!*p) break;
       if (v.empty() && !keyword && std::strncmp(p, "sensor_width_mm", 15) == 0) { keyword = 1; p += 15; continue; }
       if (v.empty() && !keyword && std::strncmp(p, "lambda_nm", 9) == 0) { keyword = 2; p += 9; continue; }
       if (v.empty() && !keyword && std::strncmp(p, "coating", 7) == 0) { keyword = 3; p += 7; continue; }
+      if (v.empty() && !keyword && std::strncmp(p, "layer", 5) == 0) { keyword = 4; p += 5; continue; }
       char* e = nullptr;
       const double d = std::strtod(p, &e);
       if (e == p) {
@@ -1634,6 +1787,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (bad) break;
     if (keyword == 2) { lambda_line = true; lambdas = v; continue; }
     if (keyword == 3) { coats.push_back(v); continue; }
+    if (keyword == 4) { layers.push_back(v); continue; }
     if (keyword == 1) { if (v.size() != 1) { bad = true; break; } sensor_w = v[0]; continue; }
     if (!v.empty()) rows.push_back(v);
   }
@@ -1652,21 +1806,43 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     for (int l = 0; l < nl; l++) ior[l * n + k] = (is_stop && stop == k) ? 1.0f : (float)rows[k][2 + l];
   }
   float lam[LF_MAX_LAMBDA] = {}, cth[LF_MAX_SURFACES] = {}, cidx[LF_MAX_LAMBDA * LF_MAX_SURFACES] = {};
-  if (!coats.empty()) {
+  bool has_coating[LF_MAX_SURFACES] = {};   // interface k has a `coating` line (whatever its thickness)
+  if (!coats.empty() || !layers.empty()) {
     if (!lambda_line || lambda_bad || (int)lambdas.size() != nl)
-      return lf_fail(ctx, LF_ERR_INVALID, "lf_load_lens_file: coating lines need a lambda_nm line with one wavelength per index column");
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_load_lens_file: coating / layer lines need a lambda_nm line with one wavelength per index column");
     for (int l = 0; l < nl; l++) lam[l] = (float)lambdas[l];
     for (const auto& c : coats) {
       const int k = c.size() >= 3 ? (int)c[0] : -1;
       if (k < 0 || k >= n || (double)k != c[0] || ((int)c.size() != 3 && (int)c.size() != nl + 2) || cth[k] != 0.0f)
         return lf_fail(ctx, LF_ERR_INVALID, "lf_load_lens_file: a coating line is `coating k thickness_nm m_1 .. m_L` or `coating k thickness_nm m` (once per interface)");
       cth[k] = (float)c[1];
+      has_coating[k] = true;
       for (int l = 0; l < nl; l++) cidx[l * n + k] = (float)c[(int)c.size() == 3 ? 2 : 2 + l];
     }
   }
+  // the stacks: a `coating` line is a stack of one layer (installed as that film: lf_set_lens_coating_stacks)
+  std::vector<int> nlay((size_t)n, 0);
+  std::vector<float> lth((size_t)LF_MAX_COAT_LAYERS * n, 0.0f), lidx((size_t)LF_MAX_COAT_LAYERS * nl * n, 0.0f);
+  for (const auto& c : layers) {
+    const int k = c.size() >= 3 ? (int)c[0] : -1;
+    if (k < 0 || k >= n || (double)k != c[0] || ((int)c.size() != 3 && (int)c.size() != nl + 2) || has_coating[k] ||
+        nlay[(size_t)k] >= LF_MAX_COAT_LAYERS)
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_load_lens_file: a layer line is `layer k thickness_nm m_1 .. m_L` or `layer k thickness_nm m`, at most LF_MAX_COAT_LAYERS per interface and none beside a coating line");
+    const int j = nlay[(size_t)k]++;
+    lth[(size_t)j * n + k] = (float)c[1];
+    for (int l = 0; l < nl; l++) lidx[((size_t)j * nl + l) * n + k] = (float)c[(int)c.size() == 3 ? 2 : 2 + l];
+  }
+  if (!layers.empty())
+    for (int k = 0; k < n; k++)
+      if (cth[k] != 0.0f) {
+        nlay[(size_t)k] = 1;
+        lth[(size_t)k] = cth[k];
+        for (int l = 0; l < nl; l++) lidx[(size_t)l * n + k] = cidx[l * n + k];
+      }
   lf_status st = lf_set_lens(ctx, n, stop, nl, radius, thick, ior, semi, (float)sensor_w);
-  if (st != LF_OK || coats.empty()) return st;
-  st = lf_set_lens_coatings(ctx, n, nl, lam, cth, cidx);
+  if (st != LF_OK || (coats.empty() && layers.empty())) return st;
+  st = layers.empty() ? lf_set_lens_coatings(ctx, n, nl, lam, cth, cidx)
+                      : lf_set_lens_coating_stacks(ctx, n, nl, lam, nlay.data(), lth.data(), lidx.data());
   if (st != LF_OK) {   // the lens stays, bare
     const std::string why = ctx->err;
     (void)lf_set_lens_coatings(ctx, n, nl, nullptr, nullptr, nullptr);

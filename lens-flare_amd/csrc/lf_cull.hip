@@ -852,6 +852,10 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
                                                       case kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarCoatFilt); break; \
                                                       case kVarLights | kVarFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarFilt); break; \
                                                       case kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarCoat); break; \
+                                                      case kVarStack | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarStack | kVarCoat); break; \
+                                                      case kVarStack | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarStack | kVarCoatFilt); break; \
+                                                      case kVarStack | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarStack | kVarLights | kVarCoat); break; \
+                                                      case kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarStack | kVarLights | kVarCoatFilt); break; \
                                                       default: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_CULL2(KK, WW, SS, CC)                                                                       \
   hipLaunchKernelGGL((k_march_cull<KK, WW, SS, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
@@ -864,6 +868,10 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
                                               case kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarCoatFilt); break; \
                                               case kVarLights | kVarFilt: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarFilt); break; \
                                               case kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarCoat); break; \
+                                              case kVarStack | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarStack | kVarCoat); break; \
+                                              case kVarStack | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarStack | kVarCoatFilt); break; \
+                                              case kVarStack | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarStack | kVarLights | kVarCoat); break; \
+                                              case kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarStack | kVarLights | kVarCoatFilt); break; \
                                               default: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_ITEMS2(KK, CC)                                                                             \
   hipLaunchKernelGGL((k_march_items<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \

@@ -207,15 +207,34 @@ struct alignas(64) LfWeightRow {
 struct alignas(32) LfCoatK {
   float dm, ph, s01, s12, p01a, p01b, p12a, p12b;
 };
-// the film on interface k of the prescription (host): thickness 0 = bare
+// the film or the stack on interface k of the prescription (host): one state, written by lf_set_lens_coatings and by
+// lf_set_lens_coating_stacks.  n_layers[k] = 0: bare; 1: a single film -- thickness_nm[k] / index[] hold it, and the
+// LfCoatK records and coated_fraction evaluate it; >= 2: a stack -- thickness_nm[k] is 0, layer_nm / layer_index hold
+// the layers, scene side first, zero-thickness layers already dropped (a single film is in them too, as layer 0)
 struct LfCoatings {
-  int n = 0;                                   // interfaces with a film (0: none)
+  int n = 0;                                   // interfaces with a film or a stack (0: none)
+  int n_stacked = 0;                           // ... with two or more layers: the kVarStack kernels
   float lambda_nm[LF_MAX_LAMBDA] = {};
   float thickness_nm[LF_MAX_SURFACES] = {};
   float index[LF_MAX_LAMBDA * LF_MAX_SURFACES] = {};   // [l * n_surfaces + k]
+  int n_layers[LF_MAX_SURFACES] = {};
+  float layer_nm[LF_MAX_COAT_LAYERS * LF_MAX_SURFACES] = {};                     // [j * n_surfaces + k]
+  float layer_index[LF_MAX_COAT_LAYERS * LF_MAX_LAMBDA * LF_MAX_SURFACES] = {};   // [(j * n_lambda + l) * n_surfaces + k]
 };
 constexpr float kCoatMaxThicknessNm = 10000.0f;
 void lf_coat_constants(float n_in, float m, float n_out, float thickness_nm, float lambda_nm, LfCoatK* c);
+// One wavelength of a STACKED (interface, direction of travel): the record stack_fraction (lf_march_events.h) reads, float
+// arithmetic where lf_coat_constants derives the single film's.  m[i], thickness_nm[i]: the N layers in the order the ray
+// MEETS them.  out: kStackDwords(N) dwords -- [0] N (an int); [1 + 5 i ..] dm_i = m_i^2 - n^2, ph_i = 2 d_i / lambda and the
+// scales of the interface in front of layer i, 1 / (m' + m_i), m_i^2 / q, m'^2 / q (m' the medium in front, q = m_i^2 m' +
+// m'^2 m_i); [1 + 5 N ..] the last interface's, between layer N - 1 and n'.
+constexpr int kStackDwords(int n_layers) { return 4 + 5 * n_layers; }
+void lf_stack_constants(float n_in, float n_out, int n_layers, const float* m, const float* thickness_nm, float lambda_nm,
+                        float* out);
+// ... of interface `surf` of the installed stacks at wavelength l, for a ray travelling +z (the layers as listed: scene
+// side first) or -z (reversed)
+void lf_stack_constants_of(const LfCoatings& C, int n_surfaces, int n_lambda, int surf, int l, bool plus_z, float n_in,
+                           float n_out, float* out);
 // The march does not walk the per-pair sequences one by one: every path of a (sample, wavelength)
 // starts with the same backward leg from the sensor, and all pairs (i, .) share the forward leg that
 // follows the reflection at i.  The per-wavelength *program* is that tree in depth-first order:
@@ -332,7 +351,8 @@ struct LfCullCache {
 struct LfPrimaryRow {
   float dzv, curv, ch, c2, sc, h2;
   int kind;        // 0 = curved glass, LF_EV_STOP, LF_EV_FLAT
-  int coated;      // the interface carries a film: coat[] holds its constants
+  int coated;      // 0 bare; 1: the interface carries a film, coat[] holds its constants; else 2 | the byte offset, from this
+                   // row, of its stack records behind the table (a multiple of 4; lf_upload_primary_table, StackPrimary)
   float cn22[LF_MAX_LAMBDA], rn2[LF_MAX_LAMBDA], delta[LF_MAX_LAMBDA];
   float fs[LF_MAX_LAMBDA], fo[LF_MAX_LAMBDA], fi[LF_MAX_LAMBDA];
   LfCoatK coat[LF_MAX_LAMBDA];
@@ -344,6 +364,8 @@ struct LfPrimaryDev {
   float n_start[LF_MAX_LAMBDA];
   LfPrimaryRow row[LF_MAX_SURFACES];
 };
+// the device allocation behind the table: every interface's stack records at their largest
+constexpr size_t kPrimaryStackBytes = (size_t)LF_MAX_SURFACES * LF_MAX_LAMBDA * 4 * (4 + 5 * LF_MAX_COAT_LAYERS);
 // what k_scene_term's lens mode needs beside the table (kernel argument, by value)
 struct LfLensCamArgs {
   int mode;              // 1 = one reference wavelength carries R, G and B; 2 = one ray per wavelength
@@ -466,7 +488,7 @@ struct lf_ctx {
   float raw_ior[LF_MAX_LAMBDA * LF_MAX_SURFACES] = {};
   float raw_semi_ap[LF_MAX_SURFACES] = {};
   float pupil_target_h = 0.0f, pupil_target_z = 0.0f;   // lf_set_pupil_target; h <= 0: the rear element
-  LfCoatings coat;                                        // lf_set_lens_coatings (cleared by lf_set_lens)
+  LfCoatings coat;                                        // lf_set_lens_coatings / lf_set_lens_coating_stacks (cleared by lf_set_lens)
   int mask_filter = LF_MASK_NEAREST;                      // lf_set_mask_filter (a setting of the context: nothing clears it)
   std::vector<float> mask_host;                           // the STARBURST slot's texels (occupancy / open radius follow the filter)
   bool ghost_accumulate = false;                          // lf_set_ghost_accumulate
@@ -612,9 +634,10 @@ inline void lf_install_split(lf_ctx* ctx, const LfSplit& s) {
   }
   ctx->split = s;
 }
-// the kernel variant of the weighted march (lf_march_events.h: kVarBare .. kVarCoatFilt, | kVarLights: several lights)
+// the kernel variant of the weighted march (lf_march_events.h: kVarBare .. kVarCoatFilt, | kVarLights: several lights, | kVarStack)
 inline int lf_march_variant(const lf_ctx* ctx) {
-  return (ctx->coat.n > 0 ? 1 : 0) | (ctx->mask_filter == LF_MASK_BILINEAR ? 2 : 0) | (ctx->lens.n_lights > 1 ? 4 : 0);
+  return (ctx->coat.n > 0 ? 1 : 0) | (ctx->mask_filter == LF_MASK_BILINEAR ? 2 : 0) | (ctx->lens.n_lights > 1 ? 4 : 0) |
+         (ctx->coat.n_stacked > 0 ? 8 : 0);   // (kVarStack: only ever with kVarCoat -- a stacked interface counts in coat.n)
 }
 // the cull table is not this context's alone: shared between ranks, or built only in part (the frame dealt by blocks)
 inline bool lf_cull_table_split(const lf_ctx* ctx) {

@@ -19,6 +19,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <vector>
 
 #include "lf_internal.h"
 
@@ -26,8 +27,10 @@
 // derives them for a ray travelling -z (n_in = the medium behind the interface, n_out = in front)
 lf_status lf_upload_primary_table(lf_ctx* ctx) {
   const LfLensDev& L = ctx->lens;
-  LfPrimaryDev P;
-  std::memset(&P, 0, sizeof(P));
+  // (the table, and behind it the stack records of the interfaces that hold two or more layers: one upload)
+  std::vector<unsigned char> buf(sizeof(LfPrimaryDev) + kPrimaryStackBytes, 0);
+  LfPrimaryDev& P = *reinterpret_cast<LfPrimaryDev*>(buf.data());
+  size_t next_stack = sizeof(LfPrimaryDev);
   P.n = L.n_surf; P.n_lambda = L.n_lambda;
   P.inv_stop_h = 1.0f / L.stop_h;
   P.front_zv = L.surf[0].zv;
@@ -56,11 +59,22 @@ lf_status lf_upload_primary_table(lf_ctx* ctx) {
       for (int l = 0; l < L.n_lambda; l++)
         lf_coat_constants(s.n_after[l], C.index[(size_t)l * L.n_surf + k], s.n_before[l], C.thickness_nm[k], C.lambda_nm[l],
                           &w.coat[l]);
+    if (C.n_stacked > 0 && C.n_layers[k] >= 2) {
+      // the ray travels -z: it meets the layers reversed.  Wavelength l at + 4 l kStackDwords(N) bytes (StackPrimary)
+      const size_t sub = sizeof(float) * kStackDwords(C.n_layers[k]);
+      if (next_stack + (size_t)L.n_lambda * sub > buf.size())
+        return lf_fail(ctx, LF_ERR_STATE, "primary table: the stack records exceed their allocation");
+      w.coated = 2 | (int)(next_stack - (size_t)((const unsigned char*)&w - buf.data()));
+      for (int l = 0; l < L.n_lambda; l++)
+        lf_stack_constants_of(C, L.n_surf, L.n_lambda, k, l, false, s.n_after[l], s.n_before[l],
+                              reinterpret_cast<float*>(buf.data() + next_stack + (size_t)l * sub));
+      next_stack += (size_t)L.n_lambda * sub;
+    }
   }
-  if (!ctx->primary_dev) LF_HIP(ctx, hipMalloc((void**)&ctx->primary_dev, sizeof(LfPrimaryDev)));
+  if (!ctx->primary_dev) LF_HIP(ctx, hipMalloc((void**)&ctx->primary_dev, buf.size()));
   // (the context's stream is non-blocking: a kernel that still reads the previous table must finish first)
   LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  LF_HIP(ctx, hipMemcpy(ctx->primary_dev, &P, sizeof(P), hipMemcpyHostToDevice));
+  LF_HIP(ctx, hipMemcpy(ctx->primary_dev, buf.data(), buf.size(), hipMemcpyHostToDevice));
   return LF_OK;
 }
 

@@ -1085,8 +1085,18 @@ static void pack_program(lf_ctx* ctx, const std::vector<LfEventRow>& rows, const
   int n_coated = 0;
   for (int k = 0; k < n_recs; k++) n_coated += coated(k) ? 1 : 0;
   const size_t coat_off = (*seq_off + ((size_t)P.total_events + 1) * sizeof(int) + 63) & ~(size_t)63;
-  out.assign(n_coated ? coat_off + (size_t)n_groups * n_coated * 3 * sizeof(LfCoatK)
-                      : *seq_off + ((size_t)P.total_events + 1) * sizeof(int), 0);
+  // ... and behind them the records of the STACKED ones (lf_set_lens_coating_stacks): per (group, stacked record) three
+  // records of kStackDwords(N) dwords (lf_stack_constants), wavelength j of the group at + 4 j kStackDwords(N); the weight
+  // row's offset carries bit 0 to tell them from a film's (StackRec, lf_march_events.h)
+  auto surf_of = [&](int k) { return row_at(0, first_row[(size_t)k]).surf_dir & 0xff; };
+  auto stacked = [&](int k) { return C.n_stacked > 0 && C.n_layers[surf_of(k)] >= 2; };
+  size_t stack_bytes = 0;
+  for (int k = 0; k < n_recs; k++)
+    if (stacked(k)) stack_bytes += (size_t)n_groups * 3 * sizeof(float) * kStackDwords(C.n_layers[surf_of(k)]);
+  const size_t stack_off = coat_off + (size_t)n_groups * n_coated * 3 * sizeof(LfCoatK);
+  out.assign(n_coated || stack_bytes ? stack_off + stack_bytes
+                                     : *seq_off + ((size_t)P.total_events + 1) * sizeof(int), 0);
+  size_t next_stack = stack_off;
   // the per-pair sequences (read by the weight re-march): one dword per event, record | kind << 16;
   // every (interface, direction) a pair crosses is in the program, so its record exists
   {
@@ -1145,6 +1155,19 @@ static void pack_program(lf_ctx* ctx, const std::vector<LfEventRow>& rows, const
           const LfEventRow& r = row_at(l, first_row[k]);
           lf_coat_constants(r.n_in, C.index[(size_t)l * ctx->raw_n + surf], r.n_out, C.thickness_nm[surf], C.lambda_nm[l], &ck[j]);
         }
+      } else if (stacked(k)) {
+        const int surf = surf_of(k);
+        const size_t sub = sizeof(float) * kStackDwords(C.n_layers[surf]);
+        // every offset is checked against the buffer before anything is written through it
+        if (next_stack + 3 * sub > out.size() || next_stack - *wrec_off > 0x7ffffff0u) { *ok = false; return; }
+        w.coat = (int)(next_stack - *wrec_off) | 1;
+        for (int j = 0; j < 3; j++) {
+          const int l = std::min(g * K + (j < K ? j : K - 1), n_lambda - 1);
+          const LfEventRow& r = row_at(l, first_row[k]);
+          lf_stack_constants_of(C, ctx->raw_n, n_lambda, surf, l, r.sgn > 0.0f, r.n_in, r.n_out,
+                                reinterpret_cast<float*>(out.data() + next_stack + (size_t)j * sub));
+        }
+        next_stack += 3 * sub;
       }
     }
   }
@@ -1381,6 +1404,10 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
                                    case kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarLights | kVarCoatFilt); break; \
                                    case kVarLights | kVarFilt: LF_LAUNCH_MARCH2(KK, kVarLights | kVarFilt); break; \
                                    case kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarLights | kVarCoat); break; \
+                                   case kVarStack | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarStack | kVarCoat); break; \
+                                   case kVarStack | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarStack | kVarCoatFilt); break; \
+                                   case kVarStack | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarStack | kVarLights | kVarCoat); break; \
+                                   case kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarStack | kVarLights | kVarCoatFilt); break; \
                                    default: LF_LAUNCH_MARCH2(KK, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_MARCH2(KK, CC)                                                                   \
   hipLaunchKernelGGL((k_march<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
@@ -1416,7 +1443,7 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
 
 lf_status lfk_march(lf_ctx* ctx, int spp, uint64_t key) {
 #ifdef LF_MARCH_ALL_WEIGHTS
-  if (ctx->coat.n > 0 || ctx->mask_filter != LF_MASK_NEAREST)
+  if (ctx->coat.n > 0 || ctx->mask_filter != LF_MASK_NEAREST)   // (coat.n counts stacked interfaces too)
     return lf_fail(ctx, LF_ERR_INVALID, "LF_MARCH_ALL_WEIGHTS (timing ablation): a coated lens / a filtered mask is not supported");
 #endif
   const int n = ctx->pairs.n;
@@ -1486,7 +1513,9 @@ lf_status lfk_lens_rays(lf_ctx* ctx, int lambda, int n, const float* d_xy, const
 #define LF_LAUNCH_LENS_RAYS(VV)                                                                         \
   hipLaunchKernelGGL(k_lens_rays<VV>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,     \
                      ctx->lens_dev, ctx->primary_dev, m.texels, m.w, m.h, lambda, n, d_xy, d_uv, d_out)
-  switch (lf_march_variant(ctx) & kVarCoatFilt) {      // (a primary path knows no light)
+  switch (lf_march_variant(ctx) & (kVarCoatFilt | kVarStack)) {      // (a primary path knows no light)
+    case kVarStack | kVarCoatFilt: LF_LAUNCH_LENS_RAYS(kVarStack | kVarCoatFilt); break;
+    case kVarStack | kVarCoat: LF_LAUNCH_LENS_RAYS(kVarStack | kVarCoat); break;
     case kVarCoatFilt: LF_LAUNCH_LENS_RAYS(kVarCoatFilt); break;
     case kVarFilt: LF_LAUNCH_LENS_RAYS(kVarFilt); break;
     case kVarCoat: LF_LAUNCH_LENS_RAYS(kVarCoat); break;

@@ -59,6 +59,18 @@ __host__ __device__ inline float lf_cos2pi(float x) {
                                -19.7392082f), 1.0f);
   return far ? -c : c;
 }
+// sin(2 pi x), the same way: the exact reduction y = x - rint(x), |y| folded into [0, 1/4] (sin 2 pi (1/2 - b) = sin 2 pi b:
+// no sign change in the fold, the sign is y's), then a fixed odd polynomial b q(b^2) (max error 2.0e-7 on [0, 1/4] in
+// float; 6.5e-8 of it is the polynomial's own, the rest the rounding of the Horner steps near sin = 1).  Never v_sin_f32.
+__host__ __device__ inline float lf_sin2pi(float x) {
+  const float y = x - rintf(x);
+  const float a = fabsf(y);
+  const float b = a > 0.25f ? 0.5f - a : a;
+  const float z = b * b;
+  const float s = b * fmaf(z, fmaf(z, fmaf(z, fmaf(z, fmaf(z, -14.3368559f, 41.9999619f), -76.7036667f), 81.6052094f),
+                                -41.3417015f), 6.28318548f);
+  return y < 0.0f ? -s : s;
+}
 __host__ __device__ inline float lf_coat_sqrt(float x) {
 #ifdef __HIP_DEVICE_COMPILE__
   return __builtin_amdgcn_sqrtf(x);
@@ -98,6 +110,63 @@ __host__ __device__ inline void coated_fraction(float sq, float ct, const LfCoat
   Rn = fmaf(N[0], D[1], N[1] * D[0]);
   Rd = 2.0f * (D[0] * D[1]);
   if (Ns_) { *Ns_ = N[0]; *Ds_ = D[0]; *Np_ = N[1]; *Dp_ = D[1]; }
+}
+
+// The unpolarised reflectance of a STACK of N lossless layers between the media n and n' (lf_set_lens_coating_stacks), as
+// one fraction Rn / Rd like the single film's, from the same optical cosines sq and ct.  Layer i (i = 0 the one the ray
+// meets first) has cm_i = sqrt(sq^2 + dm_i), dm_i = m_i^2 - n^2, and the round-trip phase delta_i = 2 pi ph_i cm_i,
+// ph_i = 2 d_i / lambda.  The recursive Airy (Rouard) form, from the interface FARTHEST from the arriving ray: the complex
+// amplitude reflected by what lies behind a layer is carried as numerator and denominator (P, Q) -- nothing is divided --
+// starting at the last interface's a / b; crossing layer i and the interface in front of it (amplitude a / b, real)
+//   P' = a Q + b P e^{i delta_i},   Q' = b Q + a P e^{i delta_i}
+// per polarisation; |r|^2 = |P|^2 / |Q|^2, then Rn = Ns Dp + Np Ds, Rd = 2 Ds Dp.  The amplitudes are scaled by the
+// record's constants so that every b is 1 at normal incidence (|Q| stays near 1), as coated_fraction's are.
+// The record (lf_stack_constants, dwords): [0] N; [1 + 5 i ..] dm_i, ph_i and the scales s, pa, pb of the interface in
+// FRONT of layer i; [1 + 5 N ..] the last interface's s, pa, pb.  ld(i) loads dword i -- a wave-uniform scalar load in
+// the re-march, a plain load where the wavelength differs between lanes, an array on the host -- INSIDE the loop: its trip
+// count is wave-uniform, and the live vector state is P and Q (complex, s and p: eight floats) and the previous cm,
+// whatever N is.  Host and device: lf_coating_stack_reflectance runs it too.
+__host__ __device__ inline float lf_bits_float(int v) { return __builtin_bit_cast(float, v); }
+template <class LD>
+__host__ __device__ inline void stack_fraction(float sq, float ct, const LD& ld, float& Rn, float& Rd,
+                                               float* Ns_ = nullptr, float* Ds_ = nullptr, float* Np_ = nullptr,
+                                               float* Dp_ = nullptr) {
+  const int N = ld(0);
+  const int last = 1 + 5 * N;
+  float cm = lf_coat_sqrt(fmaxf(fmaf(sq, sq, lf_bits_float(ld(last - 5))), 0.0f));   // the farthest layer's
+  float Psr, Psi = 0.0f, Qsr, Qsi = 0.0f, Ppr, Ppi = 0.0f, Qpr, Qpi = 0.0f;
+  {
+    const float s = lf_bits_float(ld(last)), pa = lf_bits_float(ld(last + 1)), pb = lf_bits_float(ld(last + 2));
+    Psr = (cm - ct) * s; Qsr = (cm + ct) * s;
+    const float v = pb * ct;
+    Ppr = fmaf(pa, cm, -v); Qpr = fmaf(pa, cm, v);
+  }
+  for (int i = N - 1; i >= 0; --i) {   // wave-uniform
+    const int o = 1 + 5 * i;
+    const float ph = lf_bits_float(ld(o + 1)), s = lf_bits_float(ld(o + 2));
+    const float pa = lf_bits_float(ld(o + 3)), pb = lf_bits_float(ld(o + 4));
+    const float dprev = lf_bits_float(ld(i > 0 ? o - 5 : o));   // (layer i - 1's dm; unused in front of the first layer)
+    const float x = ph * cm;
+    const float C = lf_cos2pi(x), S = lf_sin2pi(x);
+    // the optical cosine in front of the layer: the previous layer's, or the event's own in the medium of arrival
+    const float cp = i > 0 ? lf_coat_sqrt(fmaxf(fmaf(sq, sq, dprev), 0.0f)) : sq;
+    const float as = (cp - cm) * s, bs = (cp + cm) * s;
+    const float u = pb * cm;
+    const float ap = fmaf(pa, cp, -u), bp = fmaf(pa, cp, u);
+    const float Esr = fmaf(Psr, C, -(Psi * S)), Esi = fmaf(Psr, S, Psi * C);
+    const float Epr = fmaf(Ppr, C, -(Ppi * S)), Epi = fmaf(Ppr, S, Ppi * C);
+    Psr = fmaf(as, Qsr, bs * Esr); Psi = fmaf(as, Qsi, bs * Esi);
+    const float qsr = fmaf(bs, Qsr, as * Esr), qsi = fmaf(bs, Qsi, as * Esi);
+    Ppr = fmaf(ap, Qpr, bp * Epr); Ppi = fmaf(ap, Qpi, bp * Epi);
+    const float qpr = fmaf(bp, Qpr, ap * Epr), qpi = fmaf(bp, Qpi, ap * Epi);
+    Qsr = qsr; Qsi = qsi; Qpr = qpr; Qpi = qpi;
+    cm = cp;
+  }
+  const float Ns = fmaf(Psr, Psr, Psi * Psi), Ds = fmaf(Qsr, Qsr, Qsi * Qsi);
+  const float Np = fmaf(Ppr, Ppr, Ppi * Ppi), Dp = fmaf(Qpr, Qpr, Qpi * Qpi);
+  Rn = fmaf(Ns, Dp, Np * Ds);
+  Rd = 2.0f * (Ds * Dp);
+  if (Ns_) { *Ns_ = Ns; *Ds_ = Ds; *Np_ = Np; *Dp_ = Dp; }
 }
 
 // ---- the filtered stop mask ("mask filter") -------------------------------------
@@ -169,11 +238,20 @@ typedef unsigned long long lanemask;
 // fraction as it always has.  NoCoat compiles to the bare event alone: the kernels are instantiated twice,
 // and only a lens with a film launches the variant that can evaluate one (its temporaries, inlined in the
 // re-march, would raise the register pressure of the shared-leg kernel for every frame: DESIGN.md section 4).
+// A kernel whose variant has bit kVarStack as well (launched only for a lens with a STACK of two or more layers on some
+// interface: lf_set_lens_coating_stacks) passes StackRec / StackPrimary: stacked() tells, wave-uniformly and from the dword
+// the row has loaded anyway, a stack record from a film's LfCoatK, and a stacked row takes stack_fraction behind a second
+// wave-uniform branch.  For every other CT stacked() is a constant false and the branch is not compiled.
+struct NoStack {
+  __device__ __forceinline__ int operator()(int) const { return 0; }
+};
 struct NoCoat {
   NoCoat() = default;
   __device__ __forceinline__ NoCoat(const void*, int, int) {}
   __device__ __forceinline__ bool on() const { return false; }
   __device__ __forceinline__ LfCoatK get() const { return LfCoatK{}; }
+  __device__ __forceinline__ bool stacked() const { return false; }
+  __device__ __forceinline__ NoStack stack() const { return NoStack{}; }
 };
 template <bool W, class CT = NoCoat>
 __device__ __forceinline__ lanemask surface_event(Ray& r, float dzv, float c, float ch, float c2, float sc,
@@ -204,7 +282,8 @@ __device__ __forceinline__ lanemask surface_event(Ray& r, float dzv, float c, fl
     // (a totally reflected ray only survives a mirror event, and only W = true reads ct there)
     ct = lf_sqrt(reflect ? fmaxf(k2, 0.0f) : k2);
     if (W && coat.on()) {   // wave-uniform: a film on this interface
-      coated_fraction(sq, ct, coat.get(), Rn, D);
+      if (coat.stacked()) stack_fraction(sq, ct, coat.stack(), Rn, D);   // wave-uniform: ... a stack of them
+      else coated_fraction(sq, ct, coat.get(), Rn, D);
       // a refraction transmits Rd - Rn: clamped at 0, a rounding-negative factor must not reach the unsigned sums
       if (!reflect) Rn = fminf(Rn, D);
     } else if (W) {
@@ -280,7 +359,8 @@ __device__ __forceinline__ lanemask stop_event(Ray& r, float dzv, float h2, floa
 // time, so that a context without it launches the kernels it always launched: bit 0 = a film somewhere on the
 // lens (lf_set_lens_coatings), bit 1 = the bilinear stop mask (lf_set_mask_filter).
 enum : int { kVarBare = 0, kVarCoat = 1, kVarFilt = 2, kVarCoatFilt = 3,
-             kVarLights = 4 };   // | kVarLights: the context holds several lights (lf_set_lights): the lobe pre-test and the lit epilogue loop over them
+             kVarLights = 4,    // | kVarLights: the context holds several lights (lf_set_lights): the lobe pre-test and the lit epilogue loop over them
+             kVarStack = 8 };   // | kVarStack (only with kVarCoat): some interface holds a stack of layers (lf_set_lens_coating_stacks)
 // The stop of a kernel instantiated for variant VAR.  Under the filter the geometry-only march (W = false) runs
 // the UNCHANGED nearest lookup on the support texture S (2 mw x 2 mh floats behind the texels, k_mask_support:
 // S > 0 exactly where one of the four texels of the bilinear footprint is open), the weighted march the
@@ -387,6 +467,8 @@ struct CoatRec {
   const void* base;
   int off, j;
   __device__ __forceinline__ bool on() const { return off != 0; }
+  __device__ __forceinline__ bool stacked() const { return false; }
+  __device__ __forceinline__ NoStack stack() const { return NoStack{}; }
   __device__ __forceinline__ LfCoatK get() const {
     typedef const char __attribute__((address_space(4))) * cptr;
     const lf_i8 v = *(const lf_i8 __attribute__((address_space(4)))*)((cptr)(base) + (off + 32 * j));
@@ -394,14 +476,54 @@ struct CoatRec {
                    __int_as_float(v[4]), __int_as_float(v[5]), __int_as_float(v[6]), __int_as_float(v[7])};
   }
 };
-// what a kernel instantiated with / without film support (bit kVarCoat of its variant) passes to surface_event
-template <int VAR> using CoatSel = typename std::conditional<(VAR & kVarCoat) != 0, CoatRec, NoCoat>::type;
+// ... of a kernel that can evaluate a stack too: bit 0 of the (wave-uniform) offset marks a stack record -- its N in the
+// first dword, wavelength j of the group at + j (16 + 20 N) bytes (pack_program) -- every dword a scalar load
+struct StackLoad {
+  const char __attribute__((address_space(4))) * p;
+  __device__ __forceinline__ int operator()(int i) const { return *(const int __attribute__((address_space(4)))*)(p + 4 * i); }
+};
+struct StackRec {
+  const void* base;
+  int off, j;
+  __device__ __forceinline__ bool on() const { return off != 0; }
+  __device__ __forceinline__ bool stacked() const { return (off & 1) != 0; }
+  __device__ __forceinline__ LfCoatK get() const { return CoatRec{base, off, j}.get(); }
+  __device__ __forceinline__ StackLoad stack() const {
+    typedef const char __attribute__((address_space(4))) * cptr;
+    const cptr q = (cptr)(base) + (off & ~1);
+    const int N = *(const int __attribute__((address_space(4)))*)(q);
+    return StackLoad{q + j * (16 + 20 * N)};
+  }
+};
+// what a kernel instantiated with / without film support (bits kVarCoat, kVarStack of its variant) passes to surface_event
+template <int VAR> using CoatSel = typename std::conditional<(VAR & kVarStack) != 0, StackRec,
+                                   typename std::conditional<(VAR & kVarCoat) != 0, CoatRec, NoCoat>::type>::type;
 // ... and of a row of the primary table (the wavelength may differ between lanes: a plain load)
 struct CoatPrimary {
   const LfPrimaryRow* row;
   int lambda;
   __device__ __forceinline__ bool on() const { return row->coated != 0; }
+  __device__ __forceinline__ bool stacked() const { return false; }
+  __device__ __forceinline__ NoStack stack() const { return NoStack{}; }
   __device__ __forceinline__ LfCoatK get() const { return row->coat[lambda]; }
+};
+// ... of a kernel that can evaluate a stack too: coated = 1 a film, else 2 | the byte offset FROM THE ROW of the interface's
+// stack records behind the table (lf_upload_primary_table), wavelength l at + l (16 + 20 N) bytes
+struct StackPlain {
+  const int* p;
+  __device__ __forceinline__ int operator()(int i) const { return p[i]; }
+};
+struct StackPrimary {
+  const LfPrimaryRow* row;
+  int lambda;
+  __device__ __forceinline__ bool on() const { return row->coated != 0; }
+  __device__ __forceinline__ bool stacked() const { return (row->coated & 2) != 0; }
+  __device__ __forceinline__ LfCoatK get() const { return row->coat[lambda]; }
+  __device__ __forceinline__ StackPlain stack() const {
+    const char* q = (const char*)row + (row->coated & ~3);
+    const int N = *(const int*)q;
+    return StackPlain{(const int*)(q + lambda * (16 + 20 * N))};
+  }
 };
 
 // ---- the primary path N-1 .. 0 with its weight (LensCamera::generate_ray) ---------------------------
@@ -421,7 +543,11 @@ __device__ __forceinline__ bool primary_path(const LfPrimaryDev* __restrict__ P,
     if (w.kind & LF_EV_STOP) {
       ok = stop_event<true, (VAR & kVarFilt) != 0>(r, w.dzv, w.h2, P->inv_stop_h, mask, mw, mh);
     } else {
-      if (VAR & kVarCoat)
+      if (VAR & kVarStack)
+        ok = surface_event<true>(r, w.dzv, w.curv, w.ch, w.c2, w.sc, w.cn22[lambda], w.rn2[lambda],
+                                 w.delta[lambda], w.h2, false, (w.kind & LF_EV_FLAT) != 0, -1.0f, geom_ok,
+                                 w.fs[lambda], w.fo[lambda], w.fi[lambda], StackPrimary{&w, lambda});
+      else if (VAR & kVarCoat)
         ok = surface_event<true>(r, w.dzv, w.curv, w.ch, w.c2, w.sc, w.cn22[lambda], w.rn2[lambda],
                                  w.delta[lambda], w.h2, false, (w.kind & LF_EV_FLAT) != 0, -1.0f, geom_ok,
                                  w.fs[lambda], w.fo[lambda], w.fi[lambda], CoatPrimary{&w, lambda});

@@ -448,8 +448,10 @@ struct ScenePixelArgs {
   uint64_t key;
 };
 // FILT: the lens camera reads the stop mask bilinearly (lf_set_mask_filter) -- its own instantiations, so that a
-// context under LF_MASK_NEAREST launches the kernels it always launched
-template <bool SOFT, bool LENS, bool FILT>
+// context under LF_MASK_NEAREST launches the kernels it always launched.  STACK: the primary path can evaluate a stack of
+// coating layers (lf_set_lens_coating_stacks) -- again its own instantiations, launched only for a lens that holds one (the
+// branch compiled into the others moved their spills: profiles/coating_stack_resources.txt)
+template <bool SOFT, bool LENS, bool FILT, bool STACK>
 __device__ __forceinline__ void scene_pixel(const LfSceneDev& sc, const LfEnvDev& ev, const LfCamera& cam,
                                             const ScenePixelArgs& a, const uint32_t* __restrict__ aa_raw,
                                             const LfLensCamArgs& lc, const LfPrimaryDev* __restrict__ prim,
@@ -480,7 +482,7 @@ __device__ __forceinline__ void scene_pixel(const LfSceneDev& sc, const LfEnvDev
       for (int li = 0; li < n_rays; li++) {
         const int l = lc.mode == 2 ? li : lc.lambda_ref;
         lfm::Ray r{st.X, st.Y, 0.0f, fmaf(st.X, st.X, st.Y * st.Y), st.dx, st.dy, st.dz, st.w0, 1.0f};
-        const bool left = lfm::primary_path<FILT ? lfm::kVarCoatFilt : lfm::kVarCoat>(prim, l, r, mask, lc.mw, lc.mh, lane);
+        const bool left = lfm::primary_path<(STACK ? lfm::kVarStack : 0) | (FILT ? lfm::kVarCoatFilt : lfm::kVarCoat)>(prim, l, r, mask, lc.mw, lc.mh, lane);
         lens_started++;
         if (!left) continue;
         lens_left++;
@@ -546,7 +548,7 @@ __device__ __forceinline__ void scene_pixel(const LfSceneDev& sc, const LfEnvDev
   scene[3 * p + 2] = total.z * rc;
 }
 
-template <bool SOFT, bool LENS, bool FILT = false>
+template <bool SOFT, bool LENS, bool FILT = false, bool STACK = false>
 __global__ __launch_bounds__(256, LF_SCENE_WAVES) void k_scene_term(LfSceneDev sc, LfEnvDev ev, LfCamera cam,
                                                     ScenePixelArgs a, int y0, int y1, LfDeal deal,
                                                     const uint32_t* __restrict__ aa_raw,
@@ -573,7 +575,7 @@ __global__ __launch_bounds__(256, LF_SCENE_WAVES) void k_scene_term(LfSceneDev s
   SceneTally tally{0u, 0u};
   unsigned lens_started = 0u, lens_left = 0u;
   if (mine)
-    scene_pixel<SOFT, LENS, FILT>(sc, ev, cam, a, aa_raw, lc, prim, mask, x, y, lane, stack, tally, lens_started,
+    scene_pixel<SOFT, LENS, FILT, STACK>(sc, ev, cam, a, aa_raw, lc, prim, mask, x, y, lane, stack, tally, lens_started,
                             lens_left, scene);
   // the frame's counters (every lane arrives here): LDS adds, then one global add per counter
   if (tally.rays) atomicAdd(&s_cnt[0], (unsigned long long)tally.rays);
@@ -603,7 +605,7 @@ constexpr int kLensStridedMaxPrims = 1024;
 #ifndef LF_SCENE_LENS_WAVES
 #define LF_SCENE_LENS_WAVES 3     // (2 / 3 / 4 / 5 waves per SIMD: 10.0 / 8.2 / 10.3 / 14.2 ms on the c4 bench frame -- spills beyond 3)
 #endif
-template <bool SOFT, bool FILT = false>   // FILT: as scene_pixel's
+template <bool SOFT, bool FILT = false, bool STACK = false>   // FILT, STACK: as scene_pixel's
 __global__ __launch_bounds__(256, LF_SCENE_LENS_WAVES) void k_scene_lens(LfSceneDev sc, LfEnvDev ev, LfCamera cam, ScenePixelArgs a,
                                                        int y0, int y1, LfDeal deal, int mxs, LfLensCamArgs lc,
                                                        const LfPrimaryDev* __restrict__ prim,
@@ -742,7 +744,7 @@ __global__ __launch_bounds__(256, LF_SCENE_LENS_WAVES) void k_scene_lens(LfScene
       bool left = false;
       lfm::Ray r{st.X, st.Y, 0.0f, fmaf(st.X, st.X, st.Y * st.Y), st.dx, st.dy, st.dz, st.w0, 1.0f};
       if (active) {
-        left = lfm::primary_path<FILT ? lfm::kVarCoatFilt : lfm::kVarCoat>(prim, l, r, mask, lc.mw, lc.mh, lane);
+        left = lfm::primary_path<(STACK ? lfm::kVarStack : 0) | (FILT ? lfm::kVarCoatFilt : lfm::kVarCoat)>(prim, l, r, mask, lc.mw, lc.mh, lane);
         lens_started++;
         if (left) lens_left++;
       }
@@ -1291,9 +1293,10 @@ lf_status lf_render_scene_term(lf_ctx* ctx) {
   const size_t px = (size_t)(ctx->y1 - ctx->y0) * ctx->W;
   if (px == 0) return LF_OK;
   const bool soft = ctx->scene_dev.n_soft_lights > 0 || ctx->env_dev.w > 0 || ctx->hemisphere_sample;
-#define LF_LAUNCH_SCENE(SOFT, LENS)  do { if ((LENS) && filt) LF_LAUNCH_SCENE2(SOFT, LENS, true); else LF_LAUNCH_SCENE2(SOFT, LENS, false); } while (0)
-#define LF_LAUNCH_SCENE2(SOFT, LENS, FILT)                                                               \
-  hipLaunchKernelGGL((k_scene_term<SOFT, LENS, (LENS) && (FILT)>), dim3((unsigned)((ctx->W + 31) / 32), (unsigned)(((ctx->y1 + 7) >> 3) - (ctx->y0 >> 3))), \
+#define LF_LAUNCH_SCENE(SOFT, LENS)  do { if ((LENS) && filt && stacks) LF_LAUNCH_SCENE2(SOFT, LENS, true, true); else if ((LENS) && stacks) LF_LAUNCH_SCENE2(SOFT, LENS, false, true); \
+                                          else if ((LENS) && filt) LF_LAUNCH_SCENE2(SOFT, LENS, true, false); else LF_LAUNCH_SCENE2(SOFT, LENS, false, false); } while (0)
+#define LF_LAUNCH_SCENE2(SOFT, LENS, FILT, STACK)                                                        \
+  hipLaunchKernelGGL((k_scene_term<SOFT, LENS, (LENS) && (FILT), (LENS) && (STACK)>), dim3((unsigned)((ctx->W + 31) / 32), (unsigned)(((ctx->y1 + 7) >> 3) - (ctx->y0 >> 3))), \
                      dim3(256), 0, ctx->stream, ctx->scene_dev, ctx->env_dev, ctx->cam, pa, ctx->y0, ctx->y1, \
                      lf_deal_of(ctx), ctx->jitter_aa_raw, lc, ctx->primary_dev,                           \
                      ctx->ap[LF_APERTURE_STARBURST].texels, ctx->scene_counters_dev, ctx->scene)
@@ -1304,9 +1307,10 @@ lf_status lf_render_scene_term(lf_ctx* ctx) {
   LfLensCamArgs lc;
   lf_fill_lenscam_args(ctx, &lc);
   hipEvent_t ev = lf_timing_begin(ctx, LFK_SCENE);
-#define LF_LAUNCH_SCENE_LENS(SOFT)  do { if (filt) LF_LAUNCH_SCENE_LENS2(SOFT, true); else LF_LAUNCH_SCENE_LENS2(SOFT, false); } while (0)
-#define LF_LAUNCH_SCENE_LENS2(SOFT, FILT)                                                                  \
-  hipLaunchKernelGGL((k_scene_lens<SOFT, FILT>), dim3((unsigned)((lens_tiles_x + 3) / 4), (unsigned)(((ctx->y1 + 7) >> 3) - (ctx->y0 >> 3))), \
+#define LF_LAUNCH_SCENE_LENS(SOFT)  do { if (filt && stacks) LF_LAUNCH_SCENE_LENS2(SOFT, true, true); else if (stacks) LF_LAUNCH_SCENE_LENS2(SOFT, false, true); \
+                                         else if (filt) LF_LAUNCH_SCENE_LENS2(SOFT, true, false); else LF_LAUNCH_SCENE_LENS2(SOFT, false, false); } while (0)
+#define LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK)                                                           \
+  hipLaunchKernelGGL((k_scene_lens<SOFT, FILT, STACK>), dim3((unsigned)((lens_tiles_x + 3) / 4), (unsigned)(((ctx->y1 + 7) >> 3) - (ctx->y0 >> 3))), \
                      dim3(256), (size_t)std::min(kStackDepth, std::max(1, ctx->scene_tree_depth + 1)) * 256 * sizeof(int), \
                      ctx->stream, ctx->scene_dev, ctx->env_dev, ctx->cam, pa, ctx->y0, ctx->y1,           \
                      lf_deal_of(ctx), lens_mxs, lc, ctx->primary_dev,                                      \
@@ -1319,6 +1323,7 @@ lf_status lf_render_scene_term(lf_ctx* ctx) {
   // (lf_test_knob("scene_compact", 0): the round-4 kernel, one traversal per lane's own sample -- kept as the A/B of the tests)
   const bool compact = ctx->scene_compact != 0;
   const bool filt = ctx->mask_filter == LF_MASK_BILINEAR;   // (lf_set_mask_filter: the lens camera's stop)
+  const bool stacks = ctx->coat.n_stacked > 0;              // (lf_set_lens_coating_stacks: an interface of two or more layers)
   if (lens && compact) { if (soft) LF_LAUNCH_SCENE_LENS(true); else LF_LAUNCH_SCENE_LENS(false); }
   else if (lens) { if (soft) LF_LAUNCH_SCENE(true, true); else LF_LAUNCH_SCENE(false, true); }
   else { if (soft) LF_LAUNCH_SCENE(true, false); else LF_LAUNCH_SCENE(false, false); }
