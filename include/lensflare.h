@@ -543,6 +543,39 @@ lf_status lf_set_lights(lf_ctx* ctx, int n_lights, const float* dir, const float
 /* what lf_set_lights / lf_set_sun installed (any pointer may be NULL; arrays of LF_MAX_LIGHTS lights): the unit
  * directions and radiances as stored, the angular radii as given; *n_lights = 0 before any light */
 lf_status lf_get_lights(lf_ctx* ctx, int* n_lights, float* dir, float* radiance, float* angular_radius);
+/* GHOST OCCLUSION: hide a light's lens ghosts behind the scene.  Off by default (on = 0); a context with occlusion off
+ * launches exactly the kernels it launched before this call existed.  on = 1 needs world_per_mm > 0 and finite (scene
+ * units per lens millimetre, lf_set_lens_camera's), else LF_ERR_INVALID and the previous state stays.  A setting of the
+ * context: it survives lf_set_lens, lf_set_lights, lf_focus_lens and lf_set_frame.  The contract, occlusion on:
+ *   - lf_trace_ghosts needs a lens, lf_set_camera and a scene of at least one primitive (lf_set_scene / lf_load_collada),
+ *     else LF_ERR_STATE with a message that names what is missing; a later lf_set_scene / lf_set_camera is picked up by
+ *     the next launch;
+ *   - everything before the lit epilogue is unchanged: the samples, the events and the fates, the cull table with its
+ *     cache, resolve and audit, the weighted re-march, lf_get_march_fix_bits;
+ *   - per (ray, light k) contrib_k is computed exactly as without occlusion and added, as the same u64 values, if and
+ *     only if the ray's SHADOW RAY finds no primitive: the ray's own exit point on the front element along its own exit
+ *     direction, from min_t = 0 to max_t = +inf (the camera's clip planes do not apply, as they do not clip a
+ *     directional light's shadow ray in the scene term).  A ray walks once for all its lights: the ray is the same;
+ *   - the mapping is the lens camera's, in double: with the re-marched ray's (px, py, z) in lens millimetres (z absolute
+ *     in the prescription's coordinates, the front vertex at 0) and z_ref the paraxial entrance pupil's z at the
+ *     reference wavelength (what lf_get_lens_camera reports), oc = (px wpm, py wpm, (z - z_ref) wpm), origin = pos +
+ *     c2w oc, direction = c2w unit(dx, dy, dz) -- in a lens-camera frame a ghost's shadow ray and the scene image agree;
+ *   - the primitive tests and the tree are the scene term's (the reference's double-precision sphere / triangle tests);
+ *   - a frame of K lights stays the sum of the K single-light frames under the same occlusion setting, bit for bit;
+ *   - lf_counters::rays_hit_light counts what was added; lf_get_ghost_occlusion_stats = {shadow tests made = (ray,
+ *     light) pairs with contrib_k > 0, of those blocked}, reset by lf_reset_counters; every other counter,
+ *     lf_get_executed_events, lf_get_cull_table and lf_get_cull_audit are those of the same launch with occlusion off.
+ * Not covered: the starburst and the paraxial ghost quads of an occluded light stay; occluders are opaque.
+ * lf_get_ghost_occlusion (any pointer may be NULL): the setting, and *march_variant = the kernel variant the next launch
+ * takes (bit 4, value 16, set exactly when occlusion is on). */
+lf_status lf_set_ghost_occlusion(lf_ctx* ctx, int on, double world_per_mm);
+lf_status lf_get_ghost_occlusion(lf_ctx* ctx, int* on, double* world_per_mm, int* march_variant);
+lf_status lf_get_ghost_occlusion_stats(lf_ctx* ctx, uint64_t out[2]);
+/* "would this exit ray see the sky": n rays, each {origin xyz in lens millimetres, direction xyz} (6 floats), through the
+ * same mapping and the same any-hit walk as the march's shadow rays, on the state installed; visible[i] = 1 if ray i
+ * meets no primitive, else 0.  Preconditions as lf_trace_ghosts' with occlusion on (which must be on: it carries
+ * world_per_mm), except that no light is needed. */
+lf_status lf_ghost_ray_visibility(lf_ctx* ctx, size_t n, const float* rays, unsigned char* visible);
 /* Sun hand-over from the scene to the march: turn in-frame flare `flare` of lf_find_sun_pos /
  * lf_set_flares (normalised screen position flare_origins[flare], radiance flare_radiance[flare];
  * src/pathtracer/pathtracer.cpp:32-64, camera.cpp:245-273) into the lens-space light of

@@ -37,6 +37,7 @@ ABI_SYMBOLS = [
     "lf_generate_ghost_buffer", "lf_render_flare_layer", "lf_read_tile", "lf_read_pixel",
     "lf_write_to_framebuffer", "lf_save_image_rgba", "lf_device_buffer", "lf_set_lens", "lf_set_lambda_rgb", "lf_set_sun",
     "lf_set_lights", "lf_get_lights", "lf_set_lights_from_flares",
+    "lf_set_ghost_occlusion", "lf_get_ghost_occlusion", "lf_get_ghost_occlusion_stats", "lf_ghost_ray_visibility",
     "lf_set_sun_from_flares", "lf_paraxial_efl", "lf_paraxial_image_scale", "lf_set_ghost_pairs", "lf_set_pupil_subcells", "lf_set_tile_stride", "lf_trace_ghosts", "lf_set_march_culling", "lf_get_cull_info", "lf_get_cull_table", "lf_get_cull_started_fraction", "lf_get_cull_reason", "lf_set_cull_audit", "lf_get_cull_audit", "lf_test_knob", "lf_comm_share_cull", "lf_set_cull_share", "lf_cull_prepare", "lf_cull_table_view", "lf_cull_commit", "lf_get_march_fix_bits", "lf_generate_lens_rays", "lf_get_counters", "lf_reset_counters", "lf_get_executed_events", "lf_get_march_stats", "lf_native_sqrt", "lf_native_rcp", "lf_set_starburst_spectrum", "lf_load_collada", "lf_march_tables",
     "lf_timing_enable", "lf_timing_reset", "lf_timing_get",
     "lf_clear_ghost_buffer", "lf_draw_ghost", "lf_rasterize_textured_triangle", "lf_fill_textured_pixel",
@@ -809,6 +810,45 @@ class LensFlare:
         n = C.c_int(0)
         self._ck(self.lib.lf_set_lights_from_flares(self.ctx, C.c_double(efl_mm), C.c_float(angular_radius), C.byref(n)))
         return n.value
+
+    # ---- ghost occlusion (lf_set_ghost_occlusion): a light's ghosts hidden behind the scene
+    def set_ghost_occlusion(self, on=True, world_per_mm=0.001):
+        """On: a lit ghost ray adds only what the scene does not block -- its own exit point on the front element along
+        its own exit direction, mapped to the world as the lens camera maps it (world_per_mm scene units per lens
+        millimetre, > 0 and finite).  Off (the default): the launch is the one it always was.  trace_ghosts then needs
+        a lens, set_camera and a scene."""
+        on = bool(on)
+        w = float(world_per_mm)
+        if on and not (w > 0.0 and np.isfinite(w)):
+            raise ValueError("set_ghost_occlusion: world_per_mm must be > 0 and finite")
+        self._ck(self.lib.lf_set_ghost_occlusion(self.ctx, int(on), C.c_double(w)))
+
+    def get_ghost_occlusion(self):
+        """dict(on, world_per_mm, march_variant): the setting, and the kernel variant the next launch takes (bit value
+        16 = the occlusion kernels)"""
+        on, w, v = C.c_int(0), C.c_double(0.0), C.c_int(0)
+        self._ck(self.lib.lf_get_ghost_occlusion(self.ctx, C.byref(on), C.byref(w), C.byref(v)))
+        return dict(on=bool(on.value), world_per_mm=w.value, march_variant=v.value)
+
+    def ghost_occlusion_stats(self):
+        """dict(tested, blocked): (ray, light) shadow tests made since reset_counters, and how many of them were blocked"""
+        out = (C.c_uint64 * 2)()
+        self._ck(self.lib.lf_get_ghost_occlusion_stats(self.ctx, out))
+        return dict(tested=int(out[0]), blocked=int(out[1]))
+
+    def ghost_ray_visibility(self, rays):
+        """rays: n x 6 (origin xyz in lens millimetres, direction xyz).  Returns n bools: would the exit ray see the sky
+        (the mapping and the any-hit walk of the march's shadow rays, on the state installed)."""
+        r = np.asarray(rays)
+        if r.ndim != 2 or r.shape[1] != 6:
+            raise ValueError("ghost_ray_visibility: rays must be n x 6 (origin xyz in lens mm, direction xyz)")
+        r = np.ascontiguousarray(r, np.float32)
+        if not np.isfinite(r).all() or not (np.abs(r[:, 3:]).max(axis=1) > 0.0).all():
+            raise ValueError("ghost_ray_visibility: rays must be finite, directions non-zero")
+        vis = np.zeros(len(r), np.uint8)
+        self._ck(self.lib.lf_ghost_ray_visibility(self.ctx, C.c_size_t(len(r)), _fp(r, C.c_float),
+                                                  vis.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return vis.astype(bool)
 
     def set_ghost_pairs(self, pairs=None, include_primary=True):
         if pairs is None or len(pairs) == 0:

@@ -254,6 +254,37 @@ void lf_stack_constants_of(const LfCoatings& C, int n_surfaces, int n_lambda, in
   lf_stack_constants(n_in, n_out, N, m, d, C.lambda_nm[l], out);
 }
 
+// ---- ghost occlusion: the state a shadow ray needs, and its device record (lf_set_ghost_occlusion below) -------------
+// what a shadow ray needs installed: the prescription (the mapping's z_ref is its entrance pupil), the camera, a scene
+lf_status lf_occlusion_ready(const lf_ctx* ctx, const char* who) {
+  std::string missing;
+  if (!ctx->lens_valid) missing += " a lens (lf_set_lens)";
+  if (!ctx->cam_valid) missing += std::string(missing.empty() ? "" : ",") + " a camera (lf_set_camera)";
+  if (!ctx->scene_valid || ctx->scene_dev.n_prims < 1)
+    missing += std::string(missing.empty() ? "" : ",") + " a scene of at least one primitive (lf_set_scene / lf_load_collada)";
+  if (missing.empty()) return LF_OK;
+  return lf_fail(ctx, LF_ERR_STATE, std::string(who) + ": ghost occlusion needs" + missing);
+}
+
+lf_status lf_fill_occlusion(const lf_ctx* ctx, double world_per_mm, LfOcclDev* o) {
+  std::memset(o, 0, sizeof(*o));
+  // the camera position is the centre of the paraxial entrance pupil at the reference wavelength, as the lens camera
+  // has it (lf_lenscam_prepare: the same call on the same prescription)
+  double z = 0.0, m = 1.0;
+  if (ctx->raw_stop >= 0 &&
+      lf_paraxial_entrance_pupil(ctx->raw_n, ctx->raw_stop, ctx->raw_radius, ctx->raw_thickness,
+                                 ctx->raw_ior + (size_t)(ctx->lens.n_lambda / 2) * ctx->raw_n, &z, &m) != LF_OK)
+    return lf_fail(ctx, LF_ERR_INVALID, "ghost occlusion: the stop has no finite paraxial image through the front group");
+  o->nodes = ctx->scene_dev.nodes; o->prims = ctx->scene_dev.prims;
+  o->stats = ctx->counters_dev + kMarchOcclSlot;
+  std::memcpy(o->c2w, ctx->cam.c2w, sizeof(o->c2w));
+  std::memcpy(o->pos, ctx->cam.pos, sizeof(o->pos));
+  o->wpm = world_per_mm;
+  o->z_ref = z;
+  o->front_zv = ctx->lens.surf[0].zv;
+  return LF_OK;
+}
+
 extern "C" {
 
 int lf_abi_version(void) { return LF_ABI_VERSION; }
@@ -300,7 +331,7 @@ lf_status lf_create(lf_ctx** out, int device) {
   bool ok = hipMalloc((void**)&ctx->flares, sizeof(LfFlares)) == hipSuccess &&
             hipMalloc((void**)&ctx->ghosts, sizeof(LfGhostList)) == hipSuccess &&
             hipMalloc((void**)&ctx->pl_dev, sizeof(LfParaxialLens)) == hipSuccess &&
-            hipMalloc((void**)&ctx->lens_dev, sizeof(LfLensDev)) == hipSuccess &&
+            hipMalloc((void**)&ctx->lens_dev, kLensDevBytes) == hipSuccess &&
             hipMalloc((void**)&ctx->pairs_dev, sizeof(LfPairsDev)) == hipSuccess &&
             hipMalloc((void**)&ctx->counters_dev, kMarchCounterSlots * sizeof(unsigned long long)) == hipSuccess &&
             hipMalloc((void**)&ctx->scene_counters_dev, kSceneCounters * sizeof(unsigned long long)) == hipSuccess &&
@@ -1081,6 +1112,10 @@ lf_status lf_trace_ghosts(lf_ctx* ctx, int spp, uint64_t key) {
                        "a pupil target is set and the pair selection holds a pair with both mirrors behind the stop: "
                        "such pairs need the default disc (march them in a second launch, lf_set_ghost_accumulate)");
   }
+  if (ctx->ghost_occlusion) {
+    const lf_status ready = lf_occlusion_ready(ctx, "lf_trace_ghosts");
+    if (ready != LF_OK) return ready;
+  }
   LF_HIP(ctx, hipSetDevice(ctx->device));
   lf_status st = lfk_march(ctx, spp, key);
   if (st != LF_OK) return st;
@@ -1251,6 +1286,60 @@ lf_status lf_get_cull_table(lf_ctx* ctx, uint64_t* out, size_t n_entries) {
 lf_status lf_get_march_fix_bits(lf_ctx* ctx, int* bits) {
   if (!ctx || !bits) return LF_ERR_INVALID;
   *bits = ctx->march_fix_bits;
+  return LF_OK;
+}
+
+// ---- ghost occlusion ("ghost occlusion") ---------------------------------------------------------
+lf_status lf_set_ghost_occlusion(lf_ctx* ctx, int on, double world_per_mm) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (on != 0 && (!(world_per_mm > 0.0) || !std::isfinite(world_per_mm)))
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_ghost_occlusion: world_per_mm must be > 0 and finite");
+  ctx->ghost_occlusion = on != 0;
+  if (on != 0) ctx->ghost_occl_wpm = world_per_mm;
+  return LF_OK;
+}
+
+lf_status lf_get_ghost_occlusion(lf_ctx* ctx, int* on, double* world_per_mm, int* march_variant) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (on) *on = ctx->ghost_occlusion ? 1 : 0;
+  if (world_per_mm) *world_per_mm = ctx->ghost_occl_wpm;
+  if (march_variant) *march_variant = lf_march_variant(ctx);
+  return LF_OK;
+}
+
+lf_status lf_get_ghost_occlusion_stats(lf_ctx* ctx, uint64_t out[2]) {
+  if (!ctx || !out) return LF_ERR_INVALID;
+  unsigned long long c[2];
+  LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  LF_HIP(ctx, hipMemcpy(c, ctx->counters_dev + kMarchOcclSlot, sizeof(c), hipMemcpyDeviceToHost));
+  out[0] = c[0]; out[1] = c[1];
+  return LF_OK;
+}
+
+lf_status lf_ghost_ray_visibility(lf_ctx* ctx, size_t n, const float* rays, unsigned char* visible) {
+  if (!ctx || (n > 0 && (!rays || !visible))) return LF_ERR_INVALID;
+  if (n > 0x7fffffffull) return lf_fail(ctx, LF_ERR_INVALID, "lf_ghost_ray_visibility: too many rays for one call");
+  if (!ctx->ghost_occlusion)
+    return lf_fail(ctx, LF_ERR_STATE, "lf_ghost_ray_visibility: ghost occlusion is off (lf_set_ghost_occlusion gives the mapping its scale)");
+  lf_status st = lf_occlusion_ready(ctx, "lf_ghost_ray_visibility");
+  if (st != LF_OK) return st;
+  if (n == 0) return LF_OK;
+  LfOcclDev o;
+  st = lf_fill_occlusion(ctx, ctx->ghost_occl_wpm, &o);
+  if (st != LF_OK) return st;
+  LF_HIP(ctx, hipSetDevice(ctx->device));
+  float* d_rays = nullptr;
+  unsigned char* d_vis = nullptr;
+  hipError_t e = hipMalloc((void**)&d_rays, n * 6 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_vis, n);
+  if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * 6 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) st = lfk_ghost_ray_visibility(ctx, o, n, d_rays, d_vis);
+  if (e == hipSuccess && st == LF_OK) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && st == LF_OK) e = hipMemcpy(visible, d_vis, n, hipMemcpyDeviceToHost);
+  if (d_rays) (void)hipFree(d_rays);
+  if (d_vis) (void)hipFree(d_vis);
+  if (st != LF_OK) return st;
+  LF_HIP(ctx, e);
   return LF_OK;
 }
 

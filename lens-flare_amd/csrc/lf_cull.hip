@@ -195,7 +195,7 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
         weighted_remarch<VAR>(rw, seq, n_ev, j, recs, wrecs, wrec_table, mask, inv_stop_h, a.mw, a.mh);
       }
       if (VAR & kVarLights) {
-        lights_epilogue(lens, s_chan, rw, ((lj >> lane) & 1ull) != 0ull, l, &s_acc[acc_slot * 3], T.n_light);
+        lights_epilogue<VAR>(lens, s_chan, rw, ((lj >> lane) & 1ull) != 0ull, l, &s_acc[acc_slot * 3], T.n_light);
         continue;
       }
       const float qq = lobe_q(rw.dx, rw.dy, rw.dz, sx, sy, sz, sun_ss, inv_1mc);
@@ -372,7 +372,7 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
             T.n_rm_rows += (unsigned)n_ev;
             weighted_remarch<VAR>(rw, seq, n_ev, j, recs, wrecs, wrec_table, mask, inv_stop_h, a.mw, a.mh);
             if (VAR & kVarLights) {
-              lights_epilogue(lens, s_chan, rw, ((lj >> lane) & 1ull) != 0ull, l, &s_acc[lane * 3], T.n_light);
+              lights_epilogue<VAR>(lens, s_chan, rw, ((lj >> lane) & 1ull) != 0ull, l, &s_acc[lane * 3], T.n_light);
               continue;
             }
             const float qq = lobe_q(rw.dx, rw.dy, rw.dz, sx, sy, sz, sun_ss, inv_1mc);
@@ -415,7 +415,7 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
 // VAR (lf_march_events.h): what the weighted march can evaluate -- kVarCoat: the lens has a film somewhere
 // (lf_set_lens_coatings); kVarFilt: the stop mask is read bilinearly (lf_set_mask_filter)
 template <int K, bool W1, int MODE, int VAR>
-__global__ __launch_bounds__(64 * kWgWaves, (K == 1 ? 8 : MODE == 1 ? LF_SHARED_WAVES : 6))
+__global__ __launch_bounds__(64 * kWgWaves, ((VAR & kVarOccl) ? 4 : K == 1 ? 8 : MODE == 1 ? LF_SHARED_WAVES : 6))   // (kVarOccl: as k_march)
 void k_march_cull(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                   const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
                   const LfWeightRow* __restrict__ wrec_table, const float* __restrict__ mask, MarchArgs a,
@@ -634,7 +634,7 @@ constexpr int kItemChunk = 256;      // samples per chunk at most (8 bits of an 
 constexpr int kItemCellCache = 64;   // chunks of up to this many samples keep each (sample, pixel)'s table cell between the two listing passes
 
 template <int K, int VAR>
-__global__ __launch_bounds__(64 * kWgWaves, 6)      // (42 KB of LDS lists: three workgroups per CU)
+__global__ __launch_bounds__(64 * kWgWaves, (VAR & kVarOccl) ? 4 : 6)      // (kVarOccl: as k_march; 42 KB of LDS lists: three workgroups per CU)
 void k_march_items(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                    const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
                    const LfWeightRow* __restrict__ wrec_table, const float* __restrict__ mask, MarchArgs a,
@@ -856,7 +856,13 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
                                                       case kVarStack | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarStack | kVarCoatFilt); break; \
                                                       case kVarStack | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarStack | kVarLights | kVarCoat); break; \
                                                       case kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarStack | kVarLights | kVarCoatFilt); break; \
-                                                      default: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarBare); break; } } while (0)
+                                                      case kVarOccl | kVarLights | kVarBare: LF_LAUNCH_CULL2(KK, WW, SS, kVarOccl | kVarLights | kVarBare); break; \
+                                                  case kVarOccl | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarOccl | kVarLights | kVarCoat); break; \
+                                                  case kVarOccl | kVarLights | kVarFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarOccl | kVarLights | kVarFilt); break; \
+                                                  case kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarOccl | kVarLights | kVarCoatFilt); break; \
+                                                  case kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
+                                                  case kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                                  default: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_CULL2(KK, WW, SS, CC)                                                                       \
   hipLaunchKernelGGL((k_march_cull<KK, WW, SS, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                         \
@@ -872,7 +878,13 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
                                               case kVarStack | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarStack | kVarCoatFilt); break; \
                                               case kVarStack | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarStack | kVarLights | kVarCoat); break; \
                                               case kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarStack | kVarLights | kVarCoatFilt); break; \
-                                              default: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarBare); break; } } while (0)
+                                              case kVarOccl | kVarLights | kVarBare: LF_LAUNCH_ITEMS2(KK, kVarOccl | kVarLights | kVarBare); break; \
+                                                  case kVarOccl | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarOccl | kVarLights | kVarCoat); break; \
+                                                  case kVarOccl | kVarLights | kVarFilt: LF_LAUNCH_ITEMS2(KK, kVarOccl | kVarLights | kVarFilt); break; \
+                                                  case kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarOccl | kVarLights | kVarCoatFilt); break; \
+                                                  case kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
+                                                  case kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                                  default: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_ITEMS2(KK, CC)                                                                             \
   hipLaunchKernelGGL((k_march_items<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                         \

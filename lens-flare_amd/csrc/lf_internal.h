@@ -16,6 +16,7 @@
 // ---- limits -------------------------------------------------------------------------------
 // k_march's counters: the seven of lf_counters, executed events, re-march lane events, re-march rows
 constexpr int kMarchCounters = 10;
+constexpr int kMarchOcclSlot = 10;       // lf_get_ghost_occlusion_stats: shadow tests made, of those blocked (two slots)
 constexpr int kMarchCounterSlots = 256;  // allocated (instrumented experiment builds append their tallies)
 constexpr int kMarchHistSlot = 16;       // -DLF_MARCH_LIVE_HIST: 3 row kinds x 9 live-lane buckets
 constexpr int kMarchPairSlot = 64;       // -DLF_MARCH_PAIR_STATS: 3 x 64 per-path tallies
@@ -104,6 +105,18 @@ struct LfSurfaceDev {
   float n_after[LF_MAX_LAMBDA];  // ... on the sensor side (the stop leaves the medium unchanged)
 };
 
+// the ghost march's occlusion test (lf_march_common.h ghost_ray_visible; DESIGN.md section 4, "ghost occlusion")
+struct LfOcclDev {
+  LfBvhNode* nodes;              // the scene's tree and primitives (LfSceneDev's)
+  LfPrim* prims;
+  unsigned long long* stats;     // {shadow tests made, of those blocked}: the march counters' slots kMarchOcclSlot, + 1
+  double c2w[9], pos[3];         // the camera (lf_set_camera), row-major
+  double wpm;                    // world units per lens millimetre
+  double z_ref;                  // lens-space z that sits at the camera position: the paraxial entrance pupil (lf_get_lens_camera)
+  float front_zv;                // vertex z of interface 0: a completed ghost ray's hz is relative to it
+  int pad;
+};
+
 struct LfLensDev {
   int n_surf, stop, n_lambda, pad;
   float z_sensor;      // sensor plane z
@@ -128,6 +141,12 @@ struct LfLensDev {
   float light_ss[LF_MAX_LIGHTS];
   float light_thr[LF_MAX_LIGHTS];   // lf_march_lobe_thr of light k (light 0's also travels as MarchArgs::lobe_thr)
 };
+// Ghost occlusion (lf_set_ghost_occlusion): the LfOcclDev record of a launch lies BEHIND the device's LfLensDev, in the same
+// allocation, at kLensOcclOffset -- not inside it: LfLensDev keeps its size and its 4-byte alignment, so the kernels a context
+// without occlusion launches compile to what they were, and nothing keyed on the lens (the cull table's hash) sees it.
+// Written by the launch's upload (lf_fill_occlusion), read by the kVarOccl kernels' lit epilogue alone.
+constexpr size_t kLensOcclOffset = (sizeof(LfLensDev) + 15) & ~(size_t)15;
+constexpr size_t kLensDevBytes = kLensOcclOffset + sizeof(LfOcclDev);
 
 struct LfPairsDev {
   int n;
@@ -492,6 +511,8 @@ struct lf_ctx {
   int mask_filter = LF_MASK_NEAREST;                      // lf_set_mask_filter (a setting of the context: nothing clears it)
   std::vector<float> mask_host;                           // the STARBURST slot's texels (occupancy / open radius follow the filter)
   bool ghost_accumulate = false;                          // lf_set_ghost_accumulate
+  bool ghost_occlusion = false;                           // lf_set_ghost_occlusion (a setting of the context: nothing clears it)
+  double ghost_occl_wpm = 0.001;                          // ... its world units per lens millimetre
   LfLensDev* lens_dev = nullptr;
   LfPairsDev pairs{};
   LfPairsDev* pairs_dev = nullptr;
@@ -634,10 +655,13 @@ inline void lf_install_split(lf_ctx* ctx, const LfSplit& s) {
   }
   ctx->split = s;
 }
-// the kernel variant of the weighted march (lf_march_events.h: kVarBare .. kVarCoatFilt, | kVarLights: several lights, | kVarStack)
+// the kernel variant of the weighted march (lf_march_events.h: kVarBare .. kVarCoatFilt, | kVarLights: several lights, | kVarStack,
+// | kVarOccl: ghost occlusion -- always with kVarLights, whose epilogue it extends: one light is a list of one)
 inline int lf_march_variant(const lf_ctx* ctx) {
-  return (ctx->coat.n > 0 ? 1 : 0) | (ctx->mask_filter == LF_MASK_BILINEAR ? 2 : 0) | (ctx->lens.n_lights > 1 ? 4 : 0) |
-         (ctx->coat.n_stacked > 0 ? 8 : 0);   // (kVarStack: only ever with kVarCoat -- a stacked interface counts in coat.n)
+  return (ctx->coat.n > 0 ? 1 : 0) | (ctx->mask_filter == LF_MASK_BILINEAR ? 2 : 0) |
+         ((ctx->lens.n_lights > 1 || ctx->ghost_occlusion) ? 4 : 0) |
+         (ctx->coat.n_stacked > 0 ? 8 : 0) |   // (kVarStack: only ever with kVarCoat -- a stacked interface counts in coat.n)
+         (ctx->ghost_occlusion ? 16 : 0);
 }
 // the cull table is not this context's alone: shared between ranks, or built only in part (the frame dealt by blocks)
 inline bool lf_cull_table_split(const lf_ctx* ctx) {
@@ -667,6 +691,11 @@ lf_status lfk_flip_rows(lf_ctx* ctx, uint32_t* out_dev);
 lf_status lfk_march(lf_ctx* ctx, int spp, uint64_t key);
 lf_status lfk_lens_rays(lf_ctx* ctx, int lambda, int n, const float* d_xy, const float* d_uv,
                         float* d_out);
+// ghost occlusion: what a launch / a query needs installed (`who` names the caller in the refusal), the device record of the
+// state installed, and the batched per-ray query (d_rays: n x 6 floats, d_vis: n bytes)
+lf_status lf_occlusion_ready(const lf_ctx* ctx, const char* who);
+lf_status lf_fill_occlusion(const lf_ctx* ctx, double world_per_mm, LfOcclDev* o);
+lf_status lfk_ghost_ray_visibility(lf_ctx* ctx, const LfOcclDev& o, size_t n, const float* d_rays, unsigned char* d_vis);
 // lf_lens_camera.hip
 lf_status lf_lenscam_prepare(lf_ctx* ctx);            // table + calibration up to date (no-op when clean)
 lf_status lf_upload_primary_table(lf_ctx* ctx);       // LfPrimaryDev from ctx->lens (k_lens_rays needs it too)

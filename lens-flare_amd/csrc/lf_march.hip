@@ -97,7 +97,7 @@ __device__ unsigned long long* g_lit_map[8];
 #define LF_SKIP_DEAD_LAMBDA 1   // experiments (profiles/r04_march_variants.txt): 0 = no per-wavelength liveness branch
 #endif
 template <int K, int VAR>   // VAR (lf_march_events.h): kVarCoat = the lens has a film somewhere, kVarFilt = bilinear stop mask
-__global__ __launch_bounds__(64 * kWgWaves, (K == 1 ? 8 : 6))
+__global__ __launch_bounds__(64 * kWgWaves, ((VAR & kVarOccl) ? 4 : K == 1 ? 8 : 6))   // (kVarOccl: 128 VGPRs for the walk in the lit epilogue)
 void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
              const int* __restrict__ seq_table, const LfProgHdr* __restrict__ hdr_table,
              const LfProgRow* __restrict__ rec_table, const LfWeightRow* __restrict__ wrec_table,
@@ -587,7 +587,7 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
                 // keeps its control flow as plain scalar branches)
                 // (the re-march reproduces the first pass bit for bit: rw's direction is r[j]'s)
                 if (VAR & kVarLights) {
-                  lights_epilogue(lens, s_chan, rw, ((lj >> lane) & 1ull) != 0ull, l, &s_acc[lane * 3], n_light);
+                  lights_epilogue<VAR>(lens, s_chan, rw, ((lj >> lane) & 1ull) != 0ull, l, &s_acc[lane * 3], n_light);
                   continue;
                 }
                 const float qq = lobe_q(rw.dx, rw.dy, rw.dz, sx, sy, sz, sun_ss, inv_1mc);
@@ -686,6 +686,16 @@ __global__ __launch_bounds__(256) void k_lens_rays(const LfLensDev* __restrict__
     o[6] = alive ? __fdiv_rn(r.wn, r.wd) : 0.0f;
     o[7] = alive ? 1.0f : 0.0f;
   }
+}
+
+// lf_ghost_ray_visibility: would an exit ray (origin xyz on / in front of the front element in lens millimetres, direction
+// xyz) see the sky?  One lane per ray: the lit epilogue's own mapping and walk (lf_march_common.h ghost_ray_visible).
+__global__ __launch_bounds__(256) void k_ghost_ray_visibility(LfOcclDev o, int n, const float* __restrict__ rays,
+                                                              unsigned char* __restrict__ visible) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rays + 6 * (size_t)i;
+  visible[i] = ghost_ray_visible(o, r[0], r[1], r[2], r[3], r[4], r[5]) ? 1 : 0;
 }
 
 // The support texture of the bilinear stop mask (lf_set_mask_filter; DESIGN.md section 5, "the support texture"):
@@ -1235,6 +1245,14 @@ static lf_status march_upload(lf_ctx* ctx, int spp, int total_paths = 0) {
       for (int c = 0; c < 3; c++) up.light_radiance[k][c] = std::ldexp(ctx->lens.light_radiance[k][c], bits - 36);
     // (pageable source of an asynchronous copy: the runtime stages it before the call returns)
     LF_HIP(ctx, hipMemcpyAsync(ctx->lens_dev, &up, sizeof(LfLensDev), hipMemcpyHostToDevice, ctx->stream));
+    // ghost occlusion: the scene, the camera and the mapping as they stand at THIS launch (a later lf_set_scene / lf_set_camera
+    // is picked up by the next one), behind the lens; off: no kernel launched reads the record
+    if (ctx->ghost_occlusion) {
+      LfOcclDev occl;
+      const lf_status st = lf_fill_occlusion(ctx, ctx->ghost_occl_wpm, &occl);
+      if (st != LF_OK) return st;
+      LF_HIP(ctx, hipMemcpyAsync((char*)ctx->lens_dev + kLensOcclOffset, &occl, sizeof(occl), hipMemcpyHostToDevice, ctx->stream));
+    }
   }
   LF_HIP(ctx, hipMemcpyAsync(ctx->pairs_dev, &ctx->pairs, sizeof(LfPairsDev), hipMemcpyHostToDevice,
                              ctx->stream));
@@ -1408,7 +1426,13 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
                                    case kVarStack | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarStack | kVarCoatFilt); break; \
                                    case kVarStack | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarStack | kVarLights | kVarCoat); break; \
                                    case kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarStack | kVarLights | kVarCoatFilt); break; \
-                                   default: LF_LAUNCH_MARCH2(KK, kVarLights | kVarBare); break; } } while (0)
+                                   case kVarOccl | kVarLights | kVarBare: LF_LAUNCH_MARCH2(KK, kVarOccl | kVarLights | kVarBare); break; \
+                                                  case kVarOccl | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarOccl | kVarLights | kVarCoat); break; \
+                                                  case kVarOccl | kVarLights | kVarFilt: LF_LAUNCH_MARCH2(KK, kVarOccl | kVarLights | kVarFilt); break; \
+                                                  case kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarOccl | kVarLights | kVarCoatFilt); break; \
+                                                  case kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
+                                                  case kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                                  default: LF_LAUNCH_MARCH2(KK, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_MARCH2(KK, CC)                                                                   \
   hipLaunchKernelGGL((k_march<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                \
@@ -1498,6 +1522,14 @@ lf_status lfk_mask_support(lf_ctx* ctx) {
   const LfApertureDev& m = ctx->ap[LF_APERTURE_STARBURST];
   hipLaunchKernelGGL(k_mask_support, dim3((unsigned)((2 * m.w + 255) / 256), (unsigned)(2 * m.h)), dim3(256), 0, ctx->stream,
                      m.texels, m.w, m.h, m.texels + (size_t)m.w * m.h);
+  LF_HIP(ctx, hipGetLastError());
+  return LF_OK;
+}
+
+lf_status lfk_ghost_ray_visibility(lf_ctx* ctx, const LfOcclDev& o, size_t n, const float* d_rays, unsigned char* d_vis) {
+  if (n == 0) return LF_OK;
+  hipLaunchKernelGGL(k_ghost_ray_visibility, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, o, (int)n, d_rays,
+                     d_vis);
   LF_HIP(ctx, hipGetLastError());
   return LF_OK;
 }

@@ -7,6 +7,7 @@
 
 #include "lf_internal.h"
 #include "lf_march_events.h"
+#include "lf_scene_walk.h"
 
 namespace lfm {
 
@@ -44,6 +45,37 @@ __device__ __forceinline__ lanemask lobe_gate(const Ray (&r)[K], lanemask (&lit)
     lit_any |= lit[j];
   }
   return lit_any;
+}
+
+// ---- ghost occlusion (lf_set_ghost_occlusion; the kernels instantiated with kVarOccl, k_ghost_ray_visibility) ------------
+// A ray that has left the front element at (px, py, z) lens millimetres (z absolute in the prescription's coordinates)
+// along (dx, dy, dz) goes to the world exactly as the lens camera's primary ray does (lf_scene.hip scene_pixel, the same
+// expressions in the same order, in double): oc = (px wpm, py wpm, (z - z_ref) wpm), origin = pos + c2w oc, direction =
+// c2w unit(d) -- in a lens-camera frame the ghost's shadow ray and the scene image agree.  The shadow ray runs from
+// min_t = 0 to max_t = +inf: the camera's clip planes belong to the image, not to what stands between the lens and a light.
+__device__ __forceinline__ lfw::DRay ghost_shadow_ray(const LfOcclDev& o, float px, float py, float z, float dx, float dy, float dz) {
+  using namespace lfw;
+  const double wpm = o.wpm;
+  const V3 oc = v3((double)px * wpm, (double)py * wpm, ((double)z - o.z_ref) * wpm);
+  const V3 dc = unit(v3((double)dx, (double)dy, (double)dz));
+  const V3 ow = v3(o.pos[0] + ((oc.x * o.c2w[0] + oc.y * o.c2w[1]) + oc.z * o.c2w[2]),
+                   o.pos[1] + ((oc.x * o.c2w[3] + oc.y * o.c2w[4]) + oc.z * o.c2w[5]),
+                   o.pos[2] + ((oc.x * o.c2w[6] + oc.y * o.c2w[7]) + oc.z * o.c2w[8]));
+  return make_ray(ow,
+                  v3((dc.x * o.c2w[0] + dc.y * o.c2w[1]) + dc.z * o.c2w[2],
+                     (dc.x * o.c2w[3] + dc.y * o.c2w[4]) + dc.z * o.c2w[5],
+                     (dc.x * o.c2w[6] + dc.y * o.c2w[7]) + dc.z * o.c2w[8]),
+                  0.0, (double)INFINITY);
+}
+// ... and whether it sees the sky: the scene kernels' any-hit walk (lf_scene_walk.h closest_hit, h == nullptr) over the
+// resident tree, the stack of deferred children in the lane's own array
+__device__ inline bool ghost_ray_visible(const LfOcclDev& o, float px, float py, float z, float dx, float dy, float dz) {
+  lfw::DRay ray = ghost_shadow_ray(o, px, py, z, dx, dy, dz);
+  LfSceneDev sc{};
+  sc.nodes = o.nodes; sc.prims = o.prims;
+  int stack[lfw::kStackDepth];
+  lfw::SceneTally tally{0u, 0u};
+  return !lfw::closest_hit<1>(sc, ray, nullptr, stack, tally);
 }
 
 // ---- several lights (lf_set_lights; the kernels instantiated with kVarLights) ------------------------------------------
@@ -104,16 +136,39 @@ __device__ __forceinline__ void lights_channel_factors(const LfLensDev* __restri
 // pre-test admitted): per light k the single light's arithmetic -- q_k, (1 - q_k)^2 times the weight, kept where the lane
 // lies inside lobe k -- one fixed-point value per (ray, light, channel), converted separately and added to the pixel's
 // three sums at acc; n_light counts (ray, light) contributions.
+//
+// VAR & kVarOccl (lf_set_ghost_occlusion): contrib_k, computed as ever, is added only if the scene does not block the ray --
+// its own exit point on the front element along its own exit direction (ghost_ray_visible above).  The ray is the same for
+// every light, so a lane walks ONCE, at the first light it would contribute to; the tallies count (ray, light) pairs: those
+// with contrib_k > 0 are the shadow tests made, those dropped the blocked ones -- wave-wide ballots, one pair of global
+// adds per epilogue that tested anything.  Only the lanes with something to add walk (a few per wave), each with its own
+// stack of deferred children (a lane's own array, kStackDepth ints of scratch): no LDS beside the kernel's own, so the
+// workgroups per CU stay what the kVarLights twin's LDS allows.
+template <int VAR = kVarLights>
 __device__ __forceinline__ void lights_epilogue(const LfLensDev* __restrict__ lens, const float* __restrict__ s_chan, const Ray& rw,
                                                 bool mine, int l, unsigned long long* __restrict__ acc, unsigned& n_light) {
   const int n = lens->n_lights;
   const float wq = __fdiv_rn(rw.wn, rw.wd);
+  // kVarOccl: the launch's occlusion record behind the lens (wave-uniform: scalar loads), this lane's walk once made
+  const LfOcclDev& occl = *(const LfOcclDev*)((const char*)lens + kLensOcclOffset);
+  int vis = -1;                      // (1 = the ray sees the sky)
+  unsigned w_tested = 0u, w_blocked = 0u;   // ... the wave's tallies (wave-uniform)
   for (int k = 0; k < n; k++) {
     float qq;
     const bool in = light_admits(lens, k, rw.dx, rw.dy, rw.dz, qq);
     const float om = 1.0f - qq;
     float contrib = wq * (om * om);
     contrib = (mine && in && contrib > 0.0f) ? contrib : 0.0f;
+    if (VAR & kVarOccl) {
+      const bool test = contrib > 0.0f;
+      if (test) {
+        if (vis < 0)
+          vis = ghost_ray_visible(occl, rw.px, rw.py, occl.front_zv + rw.hz, rw.dx, rw.dy, rw.dz) ? 1 : 0;
+        if (vis == 0) contrib = 0.0f;
+      }
+      w_tested += (unsigned)__popcll(__ballot(test));
+      w_blocked += (unsigned)__popcll(__ballot(test && contrib == 0.0f));
+    }
     n_light += contrib > 0.0f ? 1u : 0u;
     const float* const ch = s_chan + (k * LF_MAX_LAMBDA + l) * 3;
 #pragma unroll
@@ -121,6 +176,13 @@ __device__ __forceinline__ void lights_epilogue(const LfLensDev* __restrict__ le
       const float v = contrib * ch[c];
       const unsigned long long fx = (unsigned long long)(v * 68719476736.0f);
       if (fx) atomicAdd(&acc[c], fx);
+    }
+  }
+  if ((VAR & kVarOccl) && w_tested != 0u) {   // wave-uniform; the first active lane adds for the wave
+    const lanemask act = __ballot(true);
+    if (__lane_id() == (unsigned)(__ffsll((long long)act) - 1)) {
+      atomicAdd(&occl.stats[0], (unsigned long long)w_tested);
+      if (w_blocked) atomicAdd(&occl.stats[1], (unsigned long long)w_blocked);
     }
   }
 }

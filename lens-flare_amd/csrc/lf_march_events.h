@@ -360,7 +360,9 @@ __device__ __forceinline__ lanemask stop_event(Ray& r, float dzv, float h2, floa
 // lens (lf_set_lens_coatings), bit 1 = the bilinear stop mask (lf_set_mask_filter).
 enum : int { kVarBare = 0, kVarCoat = 1, kVarFilt = 2, kVarCoatFilt = 3,
              kVarLights = 4,    // | kVarLights: the context holds several lights (lf_set_lights): the lobe pre-test and the lit epilogue loop over them
-             kVarStack = 8 };   // | kVarStack (only with kVarCoat): some interface holds a stack of layers (lf_set_lens_coating_stacks)
+             kVarStack = 8,     // | kVarStack (only with kVarCoat): some interface holds a stack of layers (lf_set_lens_coating_stacks)
+             kVarOccl = 16 };   // | kVarOccl (only with kVarLights): a lit ray adds only what the scene does not block (lf_set_ghost_occlusion);
+                                //   differs from its kVarLights twin in lights_epilogue alone (lf_march_common.h)
 // The stop of a kernel instantiated for variant VAR.  Under the filter the geometry-only march (W = false) runs
 // the UNCHANGED nearest lookup on the support texture S (2 mw x 2 mh floats behind the texels, k_mask_support:
 // S > 0 exactly where one of the four texels of the bilinear footprint is open), the weighted march the

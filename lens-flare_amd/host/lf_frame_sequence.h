@@ -43,6 +43,8 @@ typedef struct lf_frame_plan {
   float sun_angular_radius;
   int geo_spp;
   uint64_t geo_key;
+  int ghost_occlusion;            // 0 = off.  Else, with LF_FRAME_GHOSTS_MARCH: the scene hides the march's ghosts
+                                  // (lf_set_ghost_occlusion(1, world_per_mm): needs a camera and a resident scene)
 } lf_frame_plan;
 
 // runs the frame; on failure *failed names the call that failed (a string literal)
@@ -65,6 +67,8 @@ static inline lf_status lf_run_frame(lf_ctx* ctx, const lf_frame_plan* p, const 
   if (p->scene == LF_FRAME_SCENE_DEVICE) LF_FRAME_STEP(lf_render_scene_term(ctx));
   else if (p->scene == LF_FRAME_SCENE_NONE) LF_FRAME_STEP(lf_set_scene_term(ctx, NULL));
   // generate_ghost_buffer (pathtracer.cpp:714-817)
+  LF_FRAME_STEP(lf_set_ghost_occlusion(ctx, (p->ghost_occlusion && p->ghosts == LF_FRAME_GHOSTS_MARCH) ? 1 : 0,
+                                       p->world_per_mm));
   if (p->ghosts == LF_FRAME_GHOSTS_MARCH) {
     if (p->sun_from_flares)
       LF_FRAME_STEP(lf_set_lights_from_flares(ctx, 0.0, p->sun_angular_radius, NULL));

@@ -201,6 +201,12 @@ void PathTracer::use_lights_from_flares(float angular_radius) {
   frame_ready_ = false;
 }
 
+void PathTracer::use_ghost_occlusion(bool on) {
+  if (on && !geometric_) throw std::runtime_error("use_ghost_occlusion: use_geometric_ghosts comes first (only the march's ghosts can be occluded)");
+  ghost_occlusion_ = on;
+  frame_ready_ = false;
+}
+
 void PathTracer::set_scene(int n_spheres, const double* spheres, const int* sphere_material,
                            int n_triangles, const double* tri_positions, const double* tri_normals,
                            const int* tri_material, int n_materials, const double* materials,
@@ -232,6 +238,11 @@ void PathTracer::generate_ghost_buffer() {
   // (same place in the frame: main thread, before the workers start) and raytrace_pixel reads it.
   if (!camera) throw std::runtime_error("generate_ghost_buffer: camera not set");
   upload_textures();
+  if (ghost_occlusion_) {
+    // the ghosts' shadow rays leave from the camera's pose as it stands at this frame (find_sun_pos may never have run)
+    double pos[3] = {camera->pos.x, camera->pos.y, camera->pos.z};
+    check(lf_set_camera(ctx_, camera->c2w, pos, camera->hFov, camera->vFov), "lf_set_camera");
+  }
   // push the public fields (the host may have edited them after find_sun_pos)
   std::vector<double> o, r;
   for (auto& f : flare_origins) { o.push_back(f.x); o.push_back(f.y); }
@@ -260,6 +271,7 @@ void PathTracer::generate_ghost_buffer() {
   plan.geo_spp = geo_spp_; plan.geo_key = 0x1e45f1a4eULL;
   plan.lens_camera_mode = geometric_ ? lens_camera_mode : 0;
   plan.world_per_mm = lens_world_per_mm; plan.exposure = 0.0;
+  plan.ghost_occlusion = ghost_occlusion_ ? 1 : 0;   // (use_ghost_occlusion; its scale is lens_world_per_mm)
   if (plan.lens_camera_mode) plan.jitter = LF_FRAME_JITTER_COUNTER;   // the lens camera's samples are the march's
   if (scene_radiance) {
     // a scene term the HOST evaluates (est_radiance_global_illumination on the CPU, a callback): handed

@@ -131,6 +131,10 @@ class PathTracer {
   // ... or every in-frame light of the flare state (flare_origins / flare_radiance as find_sun_pos or the host left
   // them), taken over by the frame sequence at every generate_ghost_buffer (lf_set_lights_from_flares)
   void use_lights_from_flares(float angular_radius);
+  // after use_geometric_ghosts: the scene hides the march's ghosts (lf_set_ghost_occlusion, scale lens_world_per_mm): a lit
+  // ghost ray adds only what no primitive between the front element and the sky blocks.  Needs a device scene (set_scene /
+  // load_collada) and the camera at the frame.  Off by default: the frames are those of a mirror without this call.
+  void use_ghost_occlusion(bool on);
   // replaces PathTracer::bvh / scene (pathtracer.h:116-124): hand the static scene to the device
   // so that the sample loop of raytrace_pixel (BVH closest hit + direct lighting) runs there too;
   // argument layout as lf_set_scene (include/lensflare.h)
@@ -157,6 +161,7 @@ class PathTracer {
   bool frame_ready_ = false, textures_uploaded_ = false, geometric_ = false, device_scene_ = false;
   int geo_spp_ = 0;
   bool lights_from_flares_ = false;
+  bool ghost_occlusion_ = false;
   float lights_radius_ = 0.05f;
   std::vector<double> star_;    // host mirror of raytrace_starburst for every pixel
   std::vector<double> sample_;  // host mirror of the composed sensor buffer

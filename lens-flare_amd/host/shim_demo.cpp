@@ -6,8 +6,10 @@
 //   shim_demo <case.txt> <aperture.f32> <ghost.f32> <outprefix> [n_threads]
 // case.txt: W H ns_aa flare_radius flare_intensity hFov vFov  pos(3)  c2w(9)  aw ah gw gh
 //           n_lights  then n_lights x (posLight xyz, radiance rgb)
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
+#include <stdexcept>
 #include <string>
 #include <fstream>
 #include <thread>
@@ -149,8 +151,79 @@ static int geolights_main(int argc, char** argv) {
   return 0;
 }
 
+// shim_demo geowall <lens.txt> <mask.f32> <mw> <mh> <W> <H> <spp> <sun x y z> <angular radius> <outprefix> <wall: 0 none, 1 hides the sun, 2 its left half>
+// A wall in front of the sun: the march's ghosts under PathTracer::use_ghost_occlusion.  The wall is a 2 m x 2 m quad 5 m
+// from the camera (identity pose at the origin, 1 scene unit = 1 m), square to the sun's direction and centred on it (1),
+// or shifted so that its edge crosses the sun (2).  Dumps the ghost buffer and prints the shadow tests made / blocked.
+static int geowall_main(int argc, char** argv) {
+  if (argc < 15) return 1;
+  std::ifstream in(argv[2]);
+  int n, stop, nl;
+  float sensor_w;
+  in >> n >> stop >> nl >> sensor_w;
+  std::vector<float> radius(n), thick(n), semi(n), ior((size_t)n * nl);
+  for (int k = 0; k < n; k++) {
+    in >> radius[k] >> thick[k] >> semi[k];
+    for (int l = 0; l < nl; l++) in >> ior[(size_t)l * n + k];
+  }
+  const size_t mw = atoi(argv[4]), mh = atoi(argv[5]), W = atoi(argv[6]), H = atoi(argv[7]);
+  const int spp = atoi(argv[8]);
+  const float sun[3] = {(float)atof(argv[9]), (float)atof(argv[10]), (float)atof(argv[11])};
+  const float alpha = (float)atof(argv[12]);
+  const std::string out = argv[13];
+  const int wall = atoi(argv[14]);
+  try {
+    PathTracer pt(0);
+    Camera cam;
+    CameraApertureTexture ap;
+    ap.init_from_texels(read_f32(argv[3], mw * mh).data(), mw, mh);
+    cam.aperture_texture = &ap;
+    cam.ghost_aperture_texture = &ap;
+    pt.clear();
+    pt.set_frame_size(W, H);
+    pt.camera = &cam;
+    pt.counter_jitter = true;
+    pt.flare_radiance.emplace_back(1.0, 0.9, 0.5);
+    pt.flare_origins.emplace_back(0.5, 0.5);
+    pt.axis_ray = Vector2D(0.5, 0.5);
+    pt.use_geometric_ghosts(n, stop, nl, radius.data(), thick.data(), ior.data(), semi.data(), sensor_w, sun, alpha, spp);
+    if (wall) {
+      // the sun's direction s (lens space = camera space here), two unit vectors u, v square to it
+      const double sl = std::sqrt((double)sun[0] * sun[0] + (double)sun[1] * sun[1] + (double)sun[2] * sun[2]);
+      const double s[3] = {sun[0] / sl, sun[1] / sl, sun[2] / sl};
+      double u[3] = {-s[2], 0.0, s[0]};                              // (s x y: the sun is never along y here, z < 0)
+      const double ul = std::sqrt(u[0] * u[0] + u[2] * u[2]);
+      u[0] /= ul; u[2] /= ul;
+      const double v[3] = {s[1] * u[2] - s[2] * u[1], s[2] * u[0] - s[0] * u[2], s[0] * u[1] - s[1] * u[0]};
+      const double shift = wall == 2 ? -1.0 : 0.0, dist = 5.0;
+      double c[4][3];
+      const double cu[4] = {-1.0 + shift, 1.0 + shift, 1.0 + shift, -1.0 + shift}, cv[4] = {-1.0, -1.0, 1.0, 1.0};
+      for (int i = 0; i < 4; i++)
+        for (int a = 0; a < 3; a++) c[i][a] = dist * s[a] + cu[i] * u[a] + cv[i] * v[a];
+      double pos[18], nrm[18];
+      const int idx[6] = {0, 1, 2, 0, 2, 3};
+      for (int i = 0; i < 6; i++)
+        for (int a = 0; a < 3; a++) { pos[3 * i + a] = c[idx[i]][a]; nrm[3 * i + a] = -s[a]; }
+      const int tri_mat[2] = {0, 0};
+      const double mats[4] = {0.0, 0.5, 0.5, 0.5};                   // diffuse grey
+      pt.set_scene(0, nullptr, nullptr, 2, pos, nrm, tri_mat, 1, mats, 0, nullptr);
+      pt.use_ghost_occlusion(true);
+    }
+    pt.generate_ghost_buffer();
+    dump(out + ".ghost.f64", &pt.ghost_buffer.data[0].x, W * H * 3);
+    uint64_t st[2] = {0, 0};
+    if (lf_get_ghost_occlusion_stats(pt.context(), st) != LF_OK) throw std::runtime_error(pt.last_error());
+    printf("shadow tests %llu blocked %llu\n", (unsigned long long)st[0], (unsigned long long)st[1]);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "shim_demo geowall: %s\n", e.what());
+    return 3;
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && std::string(argv[1]) == "geo") return geo_main(argc, argv);
+  if (argc > 1 && std::string(argv[1]) == "geowall") return geowall_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "geolights") return geolights_main(argc, argv);
   if (argc < 5) return 1;
   std::ifstream in(argv[1]);
