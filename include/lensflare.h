@@ -543,6 +543,60 @@ lf_status lf_set_lights(lf_ctx* ctx, int n_lights, const float* dir, const float
 /* what lf_set_lights / lf_set_sun installed (any pointer may be NULL; arrays of LF_MAX_LIGHTS lights): the unit
  * directions and radiances as stored, the angular radii as given; *n_lights = 0 before any light */
 lf_status lf_get_lights(lf_ctx* ctx, int* n_lights, float* dir, float* radiance, float* angular_radius);
+/* LIGHTS AT A FINITE DISTANCE (point lights).  lf_set_lights_ex is lf_set_lights with a kind per light:
+ *   kind[k] == LF_LIGHT_DIRECTIONAL  vec[3 k ..] is the direction, validated and stored exactly as lf_set_lights does;
+ *   kind[k] == LF_LIGHT_POINT        vec[3 k ..] is the light's POSITION in lens millimetres, the prescription's coordinates:
+ *                                    front vertex at z = 0, the scene at z < 0.
+ * angular_radius[k] is the lobe's angular radius as seen from EVERY exit point (one 1 / (1 - cos) per light, as ever).
+ * With r_f = sqrt(h0^2 + sag(h0)^2), the largest distance from the front vertex to a point of the front element's clear
+ * aperture (h0 its semi-aperture), a point light must be finite and have z <= -2 r_f and |L| >= 4 r_f: otherwise
+ * LF_ERR_INVALID with a message that names the limit (before lf_set_lens: LF_ERR_STATE, the limits are the lens's).  The
+ * call replaces ALL lights; a refusal leaves the previous ones installed.  lf_set_lights and lf_set_sun ARE lf_set_lights_ex
+ * with every kind 0: the same state, the same kernels as before this call existed.
+ * The per-ray contract (float32, every multiply-add an explicit fmaf): a ray has left the front element at
+ * (px, py, z = front_zv + hz) along d; for a point light at L
+ *     s = (Lx - px, Ly - py, Lz - z)   three float subtractions,     ss = |s|^2,
+ *     q = the sun's lobe expression on (d, s, ss) -- |d x s|^2 / (|d|^2 ss + sqrt(|d|^2 ss) d.s) / (1 - cos alpha) -- with
+ *         the correctly rounded root and division,
+ *     inside iff d.s > 0 and q < 1,     contrib = (wn / wd) (1 - q)^2 as ever.
+ * Everything else of the multi-light contract above holds with lights of mixed kinds: one fixed-point value per (ray,
+ * light, channel); the frame of K lights is the sum of the K single-light frames, bit for bit; rays_hit_light counts
+ * (ray, light) contributions; the range contract takes the sum of the radiances.  A point light has no distance falloff
+ * (neither has the scene term's: the reference's PointLight::sample_L).
+ * THE CULL TABLE takes a point light as the direction unit(L) from the front vertex, its radius widened by
+ * r_f / (|L| - r_f): for P on the front cap |unit(L - P) - unit(L)| <= |P| / min(|L - P|, |L|).  The
+ * audit decides "lit" by the exact per-ray test above.  A light so close that the widened table starts more than the
+ * launch's limit takes the path tree (lf_get_cull_reason: LF_CULL_TABLE_TOO_FULL), as a very wide sun does.
+ * KERNELS: a context with a point light -- also as its only light -- launches the kVarNear variants (march variant bits
+ * 4 | 32, lf_get_ghost_occlusion's *march_variant); a context without one launches exactly what it launched before.
+ * lf_set_lens KEEPS the installed lights; if the new front element is too close to an installed point light,
+ * lf_trace_ghosts (and lf_cull_prepare, lf_ghost_ray_light_factors) refuse with LF_ERR_STATE until the lights or the lens
+ * change.  NOT SUPPORTED: ghost occlusion together with a point light -- lf_trace_ghosts refuses with LF_ERR_STATE (the
+ * shadow ray of a point light ends at the light; no kernel is built for it).
+ * lf_get_lights reports a point light as the unit vector from the front vertex to its position; lf_get_lights_ex its kind
+ * and its position as stored (any pointer may be NULL; arrays of LF_MAX_LIGHTS lights).
+ * COST, as measured (the bench frame, 1080p x 256 spp, table rebuilt and audited inside every frame; profiles/near_light_cost.json):
+ * the sun 34.96 ms, through the parent commit's library 35.01 (the kernels are the parent's); the sun replaced by a lamp of the
+ * same 0.05 rad in the same direction 40.44 ms at 1 m, 46.36 ms at 300 mm (the table starts 8.2 / 9.9 % against the sun's 7.7 %),
+ * 121.19 ms at 100 mm (16.5 %: the path tree); {sun, lamp at 1 m} 56.12 ms against 53.55 for two suns, four mixed lights 92.75
+ * against 87.43 for four suns. */
+typedef enum { LF_LIGHT_DIRECTIONAL = 0, LF_LIGHT_POINT = 1 } lf_light_kind;
+lf_status lf_set_lights_ex(lf_ctx* ctx, int n_lights, const int* kind, const float* vec, const float* radiance,
+                           const float* angular_radius);
+lf_status lf_get_lights_ex(lf_ctx* ctx, int* n_lights, int* kind, float* vec, float* radiance, float* angular_radius);
+/* Host arithmetic, no device: one light as lf_set_lights_ex validates it against a front element of the given radius
+ * (0: flat) and semi-aperture -- LF_OK, or LF_ERR_INVALID with the refusal's text in message (may be NULL). */
+lf_status lf_validate_light(int kind, const float vec[3], const float radiance[3], float angular_radius, float front_radius,
+                            float front_semi_aperture, char* message, size_t message_size);
+/* Host arithmetic, no device: the lobe factor of ONE exit ray {origin xyz in lens millimetres (z absolute), direction xyz}
+ * for ONE light (vec, angular_radius as lf_set_lights_ex takes them): *q, and *inside = the ray contributes (either may
+ * be NULL).  For a point light this is the definition the kernels call, bit for bit; for a directional light the device
+ * takes the root with v_sqrt_f32 (1 ulp) where the host's is correctly rounded: q agrees to 2 ulp. */
+lf_status lf_light_lobe_factor(int kind, const float vec[3], float angular_radius, const float ray[6], float* q, int* inside);
+/* ... and on the device, for the lights INSTALLED: out[i n_lights + k] = (1 - q_k)^2 where exit ray i lies inside light k,
+ * 0 elsewhere -- the lit epilogue's own test and factor, without a weight (as lf_ghost_ray_visibility is to occlusion).
+ * Needs a lens and a light. */
+lf_status lf_ghost_ray_light_factors(lf_ctx* ctx, size_t n, const float* rays, float* out);
 /* GHOST OCCLUSION: hide a light's lens ghosts behind the scene.  Off by default (on = 0); a context with occlusion off
  * launches exactly the kernels it launched before this call existed.  on = 1 needs world_per_mm > 0 and finite (scene
  * units per lens millimetre, lf_set_lens_camera's), else LF_ERR_INVALID and the previous state stays.  A setting of the
@@ -595,6 +649,18 @@ lf_status lf_set_sun_from_flares(lf_ctx* ctx, int flare, double efl_mm, float an
  * names the limit; nothing is installed) -- such a host composes launches itself: lf_set_sun_from_flares /
  * lf_set_lights per group of lights under lf_set_ghost_accumulate. */
 lf_status lf_set_lights_from_flares(lf_ctx* ctx, double efl_mm, float angular_radius, int* n_taken);
+/* ... and the scene's POINT lights with them: first the in-frame flares of the flare state, exactly as
+ * lf_set_lights_from_flares takes them (no flare state, or no flare in the frame: none), then every PointLight of the
+ * installed scene lights (type 1 of lf_set_scene_lights / lf_set_scene) as an LF_LIGHT_POINT of lf_set_lights_ex: its world
+ * position through the INVERSE of the lens camera's mapping, in double, then narrowed,
+ *     p_lens = c2w^T (p_world - pos) / world_per_mm + (0, 0, z_ref),
+ * z_ref the paraxial entrance pupil's z (what lf_get_lens_camera reports), its rgb as the lobe's radiance (no distance
+ * falloff: the reference's point light has none either), all with the same angular radius.  A point light behind
+ * lf_set_lights_ex's distance limits (behind the camera, or too close to the front element) is skipped and not counted.
+ * *n_directional / *n_point (may be NULL) = the lights installed.  More than LF_MAX_LIGHTS in all: LF_ERR_INVALID, nothing is
+ * installed; no light at all: LF_ERR_INVALID.  Needs lf_set_frame, lf_set_lens and lf_set_camera. */
+lf_status lf_set_lights_from_scene(lf_ctx* ctx, double efl_mm, float angular_radius, double world_per_mm, int* n_directional,
+                                   int* n_point);
 /* Paraxial effective focal length of a prescription at one wavelength (host arithmetic, no
  * device): the system matrix from the reference's own T / R operators (pathtracer.cpp:527-533);
  * ior_row = the n indices of that wavelength (media BEHIND each interface).  Arguments as
@@ -726,6 +792,8 @@ lf_status lf_get_cull_audit(lf_ctx* ctx, uint64_t* rays, uint64_t* lit, int* lau
  *   "cull_no_prefix" 0/1        every started path marched alone from the sensor (round 5's culled march), same pixels
  *   "cull_ignore_light" k       -1 (default): off; k: the cull pre-pass and the resolve leave light k of lf_set_lights out -- a
  *                               table wrong by construction; the march and the audit still see light k (the audit's test)
+ *   "cull_no_widening" 0/1      1: a point light (lf_set_lights_ex) enters the cull table with a directional light's radius, not
+ *                               widened by r_f / (|L| - r_f) -- a table wrong by construction for a light close to the lens
  *   "cull_cache" 0/1            0: no cached tree -- every pre-pass marches its boxes (the tree a context holds is kept), same table
  *   "cull_cache_max_mb" MiB     the cached tree's byte budget (default 8192)
  *   "cull_general_kernel" 0/1   build the table with the kernel that takes its rules as arguments (must give the shipped one's table)

@@ -37,6 +37,8 @@ ABI_SYMBOLS = [
     "lf_generate_ghost_buffer", "lf_render_flare_layer", "lf_read_tile", "lf_read_pixel",
     "lf_write_to_framebuffer", "lf_save_image_rgba", "lf_device_buffer", "lf_set_lens", "lf_set_lambda_rgb", "lf_set_sun",
     "lf_set_lights", "lf_get_lights", "lf_set_lights_from_flares",
+    "lf_set_lights_ex", "lf_get_lights_ex", "lf_validate_light", "lf_light_lobe_factor", "lf_ghost_ray_light_factors",
+    "lf_set_lights_from_scene",
     "lf_set_ghost_occlusion", "lf_get_ghost_occlusion", "lf_get_ghost_occlusion_stats", "lf_ghost_ray_visibility",
     "lf_set_sun_from_flares", "lf_paraxial_efl", "lf_paraxial_image_scale", "lf_set_ghost_pairs", "lf_set_pupil_subcells", "lf_set_tile_stride", "lf_trace_ghosts", "lf_set_march_culling", "lf_get_cull_info", "lf_get_cull_table", "lf_get_cull_started_fraction", "lf_get_cull_reason", "lf_set_cull_audit", "lf_get_cull_audit", "lf_test_knob", "lf_comm_share_cull", "lf_set_cull_share", "lf_cull_prepare", "lf_cull_table_view", "lf_cull_commit", "lf_get_march_fix_bits", "lf_generate_lens_rays", "lf_get_counters", "lf_reset_counters", "lf_get_executed_events", "lf_get_march_stats", "lf_native_sqrt", "lf_native_rcp", "lf_set_starburst_spectrum", "lf_load_collada", "lf_march_tables",
     "lf_timing_enable", "lf_timing_reset", "lf_timing_get",
@@ -264,6 +266,50 @@ def coating_reflectance(n_in, n_film, n_out, thickness_nm, lambda_nm, cos_in):
     if st != 0:
         raise LensFlareError(st, "lf_coating_reflectance")
     return float(out[0]), float(out[1]), float(out[2])
+
+
+# the kinds of lf_set_lights_ex: a direction, or a position in lens millimetres (front vertex at z = 0, the scene at z < 0)
+LIGHT_DIRECTIONAL, LIGHT_POINT = 0, 1
+
+
+def validate_light(kind, vec, radiance, angular_radius, front_radius, front_semi_aperture):
+    """(status, message) of one light as lf_set_lights_ex validates it against a front element of the given radius
+    (0: flat) and semi-aperture (lf_validate_light, host only): status 0 = accepted."""
+    v = np.ascontiguousarray(vec, np.float32).reshape(3)
+    r = np.ascontiguousarray(radiance, np.float32).reshape(3)
+    msg = C.create_string_buffer(512)
+    st = load_library().lf_validate_light(int(kind), _fp(v, C.c_float), _fp(r, C.c_float), C.c_float(angular_radius),
+                                          C.c_float(front_radius), C.c_float(front_semi_aperture), msg, C.c_size_t(512))
+    return int(st), msg.value.decode()
+
+
+def light_lobe_factor(kind, vec, angular_radius, ray):
+    """(q, inside) of one exit ray {origin xyz in lens mm (z absolute), direction xyz} for one light in the march's float32
+    arithmetic (lf_light_lobe_factor, host only): a point light's is the definition the kernels call."""
+    v = np.ascontiguousarray(vec, np.float32).reshape(3)
+    r = np.ascontiguousarray(ray, np.float32).reshape(6)
+    q, inside = C.c_float(), C.c_int()
+    st = load_library().lf_light_lobe_factor(int(kind), _fp(v, C.c_float), C.c_float(angular_radius), _fp(r, C.c_float),
+                                             C.byref(q), C.byref(inside))
+    if st != 0:
+        raise LensFlareError(st, "lf_light_lobe_factor")
+    return float(q.value), int(inside.value)
+
+
+def light_lobe_factors(kind, vec, angular_radius, rays):
+    """light_lobe_factor over n x 6 rays -> (q float32 array, inside bool array)"""
+    lib = load_library()
+    v = np.ascontiguousarray(vec, np.float32).reshape(3)
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    qs, ins = np.zeros(len(r), np.float32), np.zeros(len(r), bool)
+    q, inside = C.c_float(), C.c_int()
+    fn, vp, ar, base = lib.lf_light_lobe_factor, _fp(v, C.c_float), C.c_float(angular_radius), r.ctypes.data
+    for i in range(len(r)):
+        st = fn(int(kind), vp, ar, C.cast(base + 24 * i, C.POINTER(C.c_float)), C.byref(q), C.byref(inside))
+        if st != 0:
+            raise LensFlareError(st, "lf_light_lobe_factor")
+        qs[i], ins[i] = q.value, bool(inside.value)
+    return qs, ins
 
 
 # how the march and the lens camera read the stop mask (lf_set_mask_filter)
@@ -810,6 +856,54 @@ class LensFlare:
         n = C.c_int(0)
         self._ck(self.lib.lf_set_lights_from_flares(self.ctx, C.c_double(efl_mm), C.c_float(angular_radius), C.byref(n)))
         return n.value
+
+    # ---- lights at a finite distance (lf_set_lights_ex)
+    def set_lights_ex(self, kinds, vecs, radiances, angular_radii):
+        """Lights of mixed kinds in one pass of the march (lf_set_lights_ex): per light LIGHT_DIRECTIONAL with a direction
+        (z < 0) or LIGHT_POINT with a position in lens millimetres (front vertex at z = 0, the scene at z < 0; not closer
+        than the front element's limits).  Replaces all lights; a refusal leaves the previous ones."""
+        k = np.ascontiguousarray(kinds, np.int32).reshape(-1)
+        v = np.ascontiguousarray(vecs, np.float32).reshape(-1, 3)
+        r = np.ascontiguousarray(radiances, np.float32).reshape(-1, 3)
+        a = np.ascontiguousarray(angular_radii, np.float32).reshape(-1)
+        if not (len(k) == len(v) == len(r) == len(a)):
+            raise ValueError("set_lights_ex: one kind, one vector, one radiance and one angular radius per light")
+        self._ck(self.lib.lf_set_lights_ex(self.ctx, len(k), _fp(k, C.c_int), _fp(v, C.c_float), _fp(r, C.c_float),
+                                           _fp(a, C.c_float)))
+
+    def lights_ex(self):
+        """(kinds n, vectors n x 3 -- direction or position as stored --, radiances n x 3, angular radii n) (lf_get_lights_ex)"""
+        n = C.c_int(0)
+        k = np.zeros(MAX_LIGHTS, np.int32)
+        v = np.zeros((MAX_LIGHTS, 3), np.float32)
+        r = np.zeros((MAX_LIGHTS, 3), np.float32)
+        a = np.zeros(MAX_LIGHTS, np.float32)
+        self._ck(self.lib.lf_get_lights_ex(self.ctx, C.byref(n), _fp(k, C.c_int), _fp(v, C.c_float), _fp(r, C.c_float),
+                                           _fp(a, C.c_float)))
+        return k[:n.value].copy(), v[:n.value].copy(), r[:n.value].copy(), a[:n.value].copy()
+
+    def set_lights_from_scene(self, efl_mm=0.0, angular_radius=0.05, world_per_mm=0.001):
+        """the in-frame flares and the scene's PointLights become the lights of the march (lf_set_lights_from_scene);
+        returns (directional, point) lights installed"""
+        nd, npt = C.c_int(0), C.c_int(0)
+        self._ck(self.lib.lf_set_lights_from_scene(self.ctx, C.c_double(efl_mm), C.c_float(angular_radius),
+                                                   C.c_double(world_per_mm), C.byref(nd), C.byref(npt)))
+        return nd.value, npt.value
+
+    def ghost_ray_light_factors(self, rays):
+        """rays: n x 6 (origin xyz in lens millimetres, z absolute; direction xyz).  Returns n x n_lights float32: (1 - q_k)^2
+        where ray i lies inside installed light k, 0 elsewhere (the lit epilogue's own test, lf_ghost_ray_light_factors)."""
+        r = np.asarray(rays)
+        if r.ndim != 2 or r.shape[1] != 6:
+            raise ValueError("ghost_ray_light_factors: rays must be n x 6 (origin xyz in lens mm, direction xyz)")
+        r = np.ascontiguousarray(r, np.float32)
+        if not np.isfinite(r).all():
+            raise ValueError("ghost_ray_light_factors: rays must be finite")
+        n = C.c_int(0)
+        self._ck(self.lib.lf_get_lights(self.ctx, C.byref(n), None, None, None))
+        out = np.zeros((len(r), max(1, n.value)), np.float32)
+        self._ck(self.lib.lf_ghost_ray_light_factors(self.ctx, C.c_size_t(len(r)), _fp(r, C.c_float), _fp(out, C.c_float)))
+        return out[:, :n.value]
 
     # ---- ghost occlusion (lf_set_ghost_occlusion): a light's ghosts hidden behind the scene
     def set_ghost_occlusion(self, on=True, world_per_mm=0.001):

@@ -285,6 +285,52 @@ lf_status lf_fill_occlusion(const lf_ctx* ctx, double world_per_mm, LfOcclDev* o
   return LF_OK;
 }
 
+// ---- the lights of the march ("several lights", "point lights") ----------------------------------
+// One light as lf_set_lights_ex validates it, host arithmetic only (lf_validate_light is this, exported): why = the
+// refusal's message.  front_radius / front_semi_aperture: interface 0 of the prescription (a point light's limits are
+// its r_f; have_front = false: no lens yet, a point light cannot be judged)
+static lf_status validate_light(int kind, const float* v, const float* rad, float ar, bool have_front, float front_radius,
+                                float front_semi_aperture, std::string* why) {
+  if (kind != LF_LIGHT_DIRECTIONAL && kind != LF_LIGHT_POINT) {
+    *why = "light: kind must be LF_LIGHT_DIRECTIONAL (0) or LF_LIGHT_POINT (1)";
+    return LF_ERR_INVALID;
+  }
+  if (kind == LF_LIGHT_DIRECTIONAL) {
+    const double n = std::sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]);
+    if (!(n > 0) || !(v[2] < 0) || !(ar > 0) || ar > 1.5f) { *why = "sun: direction must have z < 0, 0 < angular radius <= 1.5"; return LF_ERR_INVALID; }
+    for (int c = 0; c < 3; c++)   // unsigned fixed-point sums: see lf_set_lambda_rgb; any finite magnitude is fine (lf_march_fix_bits)
+      if (!std::isfinite(rad[c]) || rad[c] < 0.0f || !std::isfinite(v[c])) { *why = "sun: radiance must be finite and >= 0, the direction finite"; return LF_ERR_INVALID; }
+    return LF_OK;
+  }
+  if (!(ar > 0) || ar > 1.5f) { *why = "point light: 0 < angular radius <= 1.5"; return LF_ERR_INVALID; }
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(rad[c]) || rad[c] < 0.0f || !std::isfinite(v[c])) { *why = "point light: radiance must be finite and >= 0, the position finite"; return LF_ERR_INVALID; }
+  if (!have_front) { *why = "point light: its distance limits are the front element's -- lf_set_lens comes first"; return LF_ERR_STATE; }
+  const double r_f = lf_front_reach(front_radius, front_semi_aperture);
+  const double dist = std::sqrt((double)v[0] * v[0] + (double)v[1] * v[1] + (double)v[2] * v[2]);
+  if (!((double)v[2] <= -2.0 * r_f) || !(dist >= 4.0 * r_f)) {
+    char buf[256];
+    std::snprintf(buf, sizeof(buf), "point light too close to the front element: position (%g, %g, %g) mm needs z <= -2 r_f = %g and "
+                  "|L| >= 4 r_f = %g (r_f = %g mm, the front element's reach from its vertex)", v[0], v[1], v[2], -2.0 * r_f, 4.0 * r_f, r_f);
+    *why = buf;
+    return LF_ERR_INVALID;
+  }
+  return LF_OK;
+}
+
+// the installed point lights against the front element of the lens as it is now (a launch's precondition: lf_march.hip)
+lf_status lf_point_lights_fit(const lf_ctx* ctx, const char* who) {
+  const LfLensDev& L = ctx->lens;
+  for (int k = 0; k < L.n_lights; k++) {
+    if (L.light_kind[k] == LF_LIGHT_DIRECTIONAL) continue;
+    std::string why;
+    if (validate_light(LF_LIGHT_POINT, L.light_pos[k], L.light_radiance[k], ctx->light_radius[k], ctx->lens_valid, ctx->raw_radius[0],
+                       ctx->raw_semi_ap[0], &why) != LF_OK)
+      return lf_fail(ctx, LF_ERR_STATE, std::string(who) + ": light " + std::to_string(k) + " no longer fits the lens installed since -- " + why);
+  }
+  return LF_OK;
+}
+
 extern "C" {
 
 int lf_abi_version(void) { return LF_ABI_VERSION; }
@@ -869,26 +915,39 @@ lf_status lf_set_lambda_rgb(lf_ctx* ctx, const float* weights) {
   return LF_OK;
 }
 
-lf_status lf_set_lights(lf_ctx* ctx, int n_lights, const float* dir, const float* radiance, const float* angular_radius) {
-  if (!ctx || !dir || !radiance || !angular_radius) return LF_ERR_INVALID;
+lf_status lf_validate_light(int kind, const float vec[3], const float radiance[3], float angular_radius, float front_radius,
+                            float front_semi_aperture, char* message, size_t message_size) {
+  if (message && message_size) message[0] = 0;
+  if (!vec || !radiance) return LF_ERR_INVALID;
+  if (!(front_semi_aperture > 0.0f) || !std::isfinite(front_semi_aperture) || !std::isfinite(front_radius)) return LF_ERR_INVALID;
+  std::string why;
+  const lf_status st = validate_light(kind, vec, radiance, angular_radius, true, front_radius, front_semi_aperture, &why);
+  if (message && message_size) std::snprintf(message, message_size, "%s", why.c_str());
+  return st;
+}
+
+static lf_status set_lights(lf_ctx* ctx, const char* who, int n_lights, const int* kind, const float* vec, const float* radiance,
+                            const float* angular_radius) {
   if (n_lights < 1 || n_lights > LF_MAX_LIGHTS)
-    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lights: 1 .. LF_MAX_LIGHTS (" + std::to_string(LF_MAX_LIGHTS) + ") lights per launch");
+    return lf_fail(ctx, LF_ERR_INVALID, std::string(who) + ": 1 .. LF_MAX_LIGHTS (" + std::to_string(LF_MAX_LIGHTS) + ") lights per launch");
   // every light is validated before any is installed: a refusal leaves the previous lights in place
   LfLensDev L = ctx->lens;
   for (int k = 0; k < n_lights; k++) {
-    const float* d = dir + 3 * k;
+    const float* d = vec + 3 * k;
     const float* rad = radiance + 3 * k;
     const float ar = angular_radius[k];
-    double n = std::sqrt((double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2]);
-    if (!(n > 0) || !(d[2] < 0) || !(ar > 0) || ar > 1.5f)
-      return lf_fail(ctx, LF_ERR_INVALID, "sun: direction must have z < 0, 0 < angular radius <= 1.5");
-    for (int c = 0; c < 3; c++)   // unsigned fixed-point sums: see lf_set_lambda_rgb; any finite magnitude is fine (lf_march_fix_bits)
-      if (!std::isfinite(rad[c]) || rad[c] < 0.0f || !std::isfinite(d[c]))
-        return lf_fail(ctx, LF_ERR_INVALID, "sun: radiance must be finite and >= 0, the direction finite");
+    const int kd = kind ? kind[k] : LF_LIGHT_DIRECTIONAL;
+    std::string why;
+    const lf_status st = validate_light(kd, d, rad, ar, ctx->lens_valid, ctx->raw_radius[0], ctx->raw_semi_ap[0], &why);
+    if (st != LF_OK) return lf_fail(ctx, st, why);
+    // a point light's direction: from the front vertex (z = 0 in the prescription's coordinates) to its position
+    const double n = std::sqrt((double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2]);
     for (int c = 0; c < 3; c++) {
       L.light_dir[k][c] = (float)(d[c] / n);
       L.light_radiance[k][c] = rad[c];
+      L.light_pos[k][c] = kd == LF_LIGHT_POINT ? d[c] : 0.0f;
     }
+    L.light_kind[k] = kd;
     L.light_inv_one_minus_cos[k] = (float)(1.0 / (1.0 - std::cos((double)ar)));
     L.light_ss[k] = (float)((double)L.light_dir[k][0] * L.light_dir[k][0] +
                             (double)L.light_dir[k][1] * L.light_dir[k][1] +
@@ -896,8 +955,9 @@ lf_status lf_set_lights(lf_ctx* ctx, int n_lights, const float* dir, const float
     L.light_thr[k] = lf_march_lobe_thr_of(L.light_inv_one_minus_cos[k]);
   }
   for (int k = n_lights; k < LF_MAX_LIGHTS; k++) {
-    for (int c = 0; c < 3; c++) L.light_dir[k][c] = L.light_radiance[k][c] = 0.0f;
+    for (int c = 0; c < 3; c++) L.light_dir[k][c] = L.light_radiance[k][c] = L.light_pos[k][c] = 0.0f;
     L.light_inv_one_minus_cos[k] = L.light_ss[k] = L.light_thr[k] = 0.0f;
+    L.light_kind[k] = LF_LIGHT_DIRECTIONAL;
   }
   L.n_lights = n_lights;
   // light 0 is the sun of the single-light kernels
@@ -910,12 +970,40 @@ lf_status lf_set_lights(lf_ctx* ctx, int n_lights, const float* dir, const float
   return LF_OK;
 }
 
+lf_status lf_set_lights_ex(lf_ctx* ctx, int n_lights, const int* kind, const float* vec, const float* radiance,
+                           const float* angular_radius) {
+  if (!ctx || !kind || !vec || !radiance || !angular_radius) return LF_ERR_INVALID;
+  return set_lights(ctx, "lf_set_lights_ex", n_lights, kind, vec, radiance, angular_radius);
+}
+
+lf_status lf_set_lights(lf_ctx* ctx, int n_lights, const float* dir, const float* radiance, const float* angular_radius) {
+  if (!ctx || !dir || !radiance || !angular_radius) return LF_ERR_INVALID;
+  return set_lights(ctx, "lf_set_lights", n_lights, nullptr, dir, radiance, angular_radius);
+}
+
 lf_status lf_set_sun(lf_ctx* ctx, const float dir[3], const float radiance[3],
                      float angular_radius) {
   if (!ctx || !dir || !radiance) return LF_ERR_INVALID;
   return lf_set_lights(ctx, 1, dir, radiance, &angular_radius);
 }
 
+lf_status lf_get_lights_ex(lf_ctx* ctx, int* n_lights, int* kind, float* vec, float* radiance, float* angular_radius) {
+  if (!ctx) return LF_ERR_INVALID;
+  const int n = ctx->sun_valid ? ctx->lens.n_lights : 0;
+  if (n_lights) *n_lights = n;
+  for (int k = 0; k < n; k++) {
+    const bool point = ctx->lens.light_kind[k] != LF_LIGHT_DIRECTIONAL;
+    if (kind) kind[k] = ctx->lens.light_kind[k];
+    for (int c = 0; c < 3; c++) {
+      if (vec) vec[3 * k + c] = point ? ctx->lens.light_pos[k][c] : ctx->lens.light_dir[k][c];
+      if (radiance) radiance[3 * k + c] = ctx->lens.light_radiance[k][c];
+    }
+    if (angular_radius) angular_radius[k] = ctx->light_radius[k];
+  }
+  return LF_OK;
+}
+
+// (a point light: the unit vector from the front vertex to its position, which is what light_dir[k] holds)
 lf_status lf_get_lights(lf_ctx* ctx, int* n_lights, float* dir, float* radiance, float* angular_radius) {
   if (!ctx) return LF_ERR_INVALID;
   const int n = ctx->sun_valid ? ctx->lens.n_lights : 0;
@@ -927,6 +1015,68 @@ lf_status lf_get_lights(lf_ctx* ctx, int* n_lights, float* dir, float* radiance,
     }
     if (angular_radius) angular_radius[k] = ctx->light_radius[k];
   }
+  return LF_OK;
+}
+
+// The lobe factor of ONE exit ray for ONE light, host arithmetic: the definitions the kernels call (lf_march_events.h
+// lf_point_lobe_q for a point light; for a directional light the sun's expression, whose root the device takes with
+// v_sqrt_f32 -- 1 ulp -- where the host's is correctly rounded: q agrees to 2 ulp there, bit for bit for a point light).
+// The light is normalised / stored exactly as lf_set_lights_ex stores it.
+lf_status lf_light_lobe_factor(int kind, const float vec[3], float angular_radius, const float ray[6], float* q, int* inside) {
+  if (!vec || !ray || (kind != LF_LIGHT_DIRECTIONAL && kind != LF_LIGHT_POINT)) return LF_ERR_INVALID;
+  if (!(angular_radius > 0) || angular_radius > 1.5f) return LF_ERR_INVALID;
+  for (int c = 0; c < 3; c++) if (!std::isfinite(vec[c])) return LF_ERR_INVALID;
+  for (int c = 0; c < 6; c++) if (!std::isfinite(ray[c])) return LF_ERR_INVALID;
+  const float inv_1mc = (float)(1.0 / (1.0 - std::cos((double)angular_radius)));
+  float qq, cg;
+  bool in;
+  if (kind == LF_LIGHT_POINT) {
+    qq = lfm::lf_point_lobe_q(ray[3], ray[4], ray[5], ray[0], ray[1], ray[2], vec[0], vec[1], vec[2], inv_1mc, cg);
+    in = cg > 0.0f && qq < 1.0f;
+  } else {
+    const double n = std::sqrt((double)vec[0] * vec[0] + (double)vec[1] * vec[1] + (double)vec[2] * vec[2]);
+    if (!(n > 0)) return LF_ERR_INVALID;
+    const float s[3] = {(float)(vec[0] / n), (float)(vec[1] / n), (float)(vec[2] / n)};
+    const float ss = (float)((double)s[0] * s[0] + (double)s[1] * s[1] + (double)s[2] * s[2]);
+    // (a light at s - 0 with |s|^2 handed in: lf_point_lobe_q's arithmetic IS lobe_q's once s and ss are given)
+    const float dx = ray[3], dy = ray[4], dz = ray[5];
+    cg = fmaf(dx, s[0], fmaf(dy, s[1], dz * s[2]));
+    const float cx = fmaf(dy, s[2], -(dz * s[1])), cy = fmaf(dz, s[0], -(dx * s[2])), cz = fmaf(dx, s[1], -(dy * s[0]));
+    const float c2 = fmaf(cx, cx, fmaf(cy, cy, cz * cz));
+    const float dd = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+    const float ds = dd * ss;
+    qq = (c2 / fmaf(sqrtf(ds), cg, ds)) * inv_1mc;
+    in = cg > lf_march_lobe_thr_of(inv_1mc) && qq < 1.0f;
+  }
+  if (q) *q = qq;
+  if (inside) *inside = in ? 1 : 0;
+  return LF_OK;
+}
+
+// (1 - q_k)^2 of n exit rays {origin xyz in lens millimetres, z absolute; direction xyz} for every installed light k where
+// the ray lies inside it, 0 elsewhere: k_ghost_ray_light_factors calls what the lit epilogue calls (light_admits_at)
+lf_status lf_ghost_ray_light_factors(lf_ctx* ctx, size_t n, const float* rays, float* out) {
+  if (!ctx || (n > 0 && (!rays || !out))) return LF_ERR_INVALID;
+  if (n > 0x7fffffffull / LF_MAX_LIGHTS) return lf_fail(ctx, LF_ERR_INVALID, "lf_ghost_ray_light_factors: too many rays for one call");
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_ghost_ray_light_factors before lf_set_lens");
+  if (!ctx->sun_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_ghost_ray_light_factors: no light installed (lf_set_sun / lf_set_lights / lf_set_lights_ex)");
+  lf_status st = lf_point_lights_fit(ctx, "lf_ghost_ray_light_factors");
+  if (st != LF_OK) return st;
+  if (n == 0) return LF_OK;
+  LF_HIP(ctx, hipSetDevice(ctx->device));
+  const int nl = ctx->lens.n_lights;
+  float *d_rays = nullptr, *d_out = nullptr;
+  hipError_t e = hipMalloc((void**)&d_rays, n * 6 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, n * (size_t)nl * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * 6 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpyAsync(ctx->lens_dev, &ctx->lens, sizeof(LfLensDev), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) st = lfk_ghost_ray_light_factors(ctx, n, d_rays, d_out);
+  if (e == hipSuccess && st == LF_OK) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && st == LF_OK) e = hipMemcpy(out, d_out, n * (size_t)nl * sizeof(float), hipMemcpyDeviceToHost);
+  if (d_rays) (void)hipFree(d_rays);
+  if (d_out) (void)hipFree(d_out);
+  if (st != LF_OK) return st;
+  LF_HIP(ctx, e);
   return LF_OK;
 }
 
@@ -1042,6 +1192,71 @@ lf_status lf_set_lights_from_flares(lf_ctx* ctx, double efl_mm, float angular_ra
   const lf_status st = lf_set_lights(ctx, f.n_flares, dir, rad, ar);
   if (st == LF_OK && n_taken) *n_taken = f.n_flares;
   return st;
+}
+
+// The scene's lights as the lights of the march: the in-frame flares (DirectionalLights) as lf_set_lights_from_flares takes
+// them, then every PointLight of the installed scene lights (type 1 of lf_set_scene_lights, LfLight::v its position) through
+// the INVERSE of the lens camera's mapping, in double: p_lens = c2w^T (p_world - pos) / wpm + (0, 0, z_ref), z_ref the
+// paraxial entrance pupil's z (lf_fill_occlusion's, lf_get_lens_camera's).  A point light the front element's limits
+// refuse (behind the camera, or closer than lf_set_lights_ex allows) is skipped and not counted.
+lf_status lf_set_lights_from_scene(lf_ctx* ctx, double efl_mm, float angular_radius, double world_per_mm, int* n_directional,
+                                   int* n_point) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (n_directional) *n_directional = 0;
+  if (n_point) *n_point = 0;
+  if (ctx->W == 0) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lights_from_scene before lf_set_frame");
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lights_from_scene before lf_set_lens");
+  if (!ctx->cam_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lights_from_scene before lf_set_camera");
+  if (!(world_per_mm > 0.0) || !std::isfinite(world_per_mm))
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lights_from_scene: world_per_mm must be > 0 and finite");
+  LF_HIP(ctx, hipSetDevice(ctx->device));
+  LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  int kind[LF_MAX_LIGHTS];
+  float vec[3 * LF_MAX_LIGHTS], rad[3 * LF_MAX_LIGHTS], ar[LF_MAX_LIGHTS];
+  int n = 0, n_dir = 0, n_pt = 0;
+  const std::string too_many = "lf_set_lights_from_scene: more lights than one launch marches (LF_MAX_LIGHTS = " + std::to_string(LF_MAX_LIGHTS) +
+                               "; compose launches with lf_set_ghost_accumulate)";
+  if (ctx->flares_valid) {
+    LfFlares f;
+    LF_HIP(ctx, hipMemcpy(&f, ctx->flares, sizeof(f), hipMemcpyDeviceToHost));
+    if (f.n_flares > LF_MAX_LIGHTS || f.n_in_frame > LF_MAX_LIGHTS) return lf_fail(ctx, LF_ERR_INVALID, too_many);
+    for (int k = 0; k < f.n_flares; k++) {
+      const lf_status st = light_of_flare(ctx, "lf_set_lights_from_scene", f, k, &efl_mm, vec + 3 * n, rad + 3 * n);
+      if (st != LF_OK) return st;
+      kind[n] = LF_LIGHT_DIRECTIONAL; ar[n] = angular_radius;
+      n++; n_dir++;
+    }
+  }
+  if (ctx->scene_valid && ctx->scene_dev.n_lights > 0) {
+    std::vector<LfLight> lts((size_t)ctx->scene_dev.n_lights);
+    LF_HIP(ctx, hipMemcpy(lts.data(), ctx->scene_dev.lights, lts.size() * sizeof(LfLight), hipMemcpyDeviceToHost));
+    double z_ref = 0.0, mag = 1.0;
+    if (ctx->raw_stop >= 0 &&
+        lf_paraxial_entrance_pupil(ctx->raw_n, ctx->raw_stop, ctx->raw_radius, ctx->raw_thickness,
+                                   ctx->raw_ior + (size_t)(ctx->lens.n_lambda / 2) * ctx->raw_n, &z_ref, &mag) != LF_OK)
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lights_from_scene: the stop has no finite paraxial image through the front group");
+    const double r_f = lf_front_reach(ctx->raw_radius[0], ctx->raw_semi_ap[0]);
+    const double* M = ctx->cam.c2w;
+    for (const LfLight& l : lts) {
+      if (l.type != 1) continue;
+      const double w[3] = {l.v[0] - ctx->cam.pos[0], l.v[1] - ctx->cam.pos[1], l.v[2] - ctx->cam.pos[2]};
+      const float p[3] = {(float)(((M[0] * w[0] + M[3] * w[1]) + M[6] * w[2]) / world_per_mm),
+                          (float)(((M[1] * w[0] + M[4] * w[1]) + M[7] * w[2]) / world_per_mm),
+                          (float)(((M[2] * w[0] + M[5] * w[1]) + M[8] * w[2]) / world_per_mm + z_ref)};
+      const double dist = std::sqrt((double)p[0] * p[0] + (double)p[1] * p[1] + (double)p[2] * p[2]);
+      if (!std::isfinite(dist) || !((double)p[2] <= -2.0 * r_f) || !(dist >= 4.0 * r_f)) continue;   // (behind the limit: skipped)
+      if (n >= LF_MAX_LIGHTS) return lf_fail(ctx, LF_ERR_INVALID, too_many);
+      for (int c = 0; c < 3; c++) { vec[3 * n + c] = p[c]; rad[3 * n + c] = (float)l.rgb[c]; }
+      kind[n] = LF_LIGHT_POINT; ar[n] = angular_radius;
+      n++; n_pt++;
+    }
+  }
+  if (n < 1) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lights_from_scene: no flare in the frame and no point light in front of the lens");
+  const lf_status st = set_lights(ctx, "lf_set_lights_from_scene", n, kind, vec, rad, ar);
+  if (st != LF_OK) return st;
+  if (n_directional) *n_directional = n_dir;
+  if (n_point) *n_point = n_pt;
+  return LF_OK;
 }
 
 lf_status lf_set_ghost_pairs(lf_ctx* ctx, const int* pairs, int n_pairs, int include_primary) {
@@ -1227,6 +1442,7 @@ lf_status lf_test_knob(lf_ctx* ctx, const char* name, double value) {
   if (n == "cull_weights_first") { ctx->cull_weights_first = iv != 0; return LF_OK; }
   if (n == "cull_no_prefix") { ctx->cull_no_prefix = iv != 0; return LF_OK; }
   if (n == "cull_ignore_light") { ctx->cull_ignore_light = iv; return LF_OK; }      // (-1: off; k: the cull table is built WITHOUT light k -- the audit's test)
+  if (n == "cull_no_widening") { ctx->cull_no_widening = iv != 0; return LF_OK; }    // (1: a point light enters the cull table with a directional light's radius -- wrong by construction)
   if (n == "cull_cache") { ctx->cull_cache_on = iv != 0; return LF_OK; }            // (0: the pre-pass marches its boxes at every build)
   if (n == "cull_cache_max_mb") { ctx->cull_cache_max_mb = value; return LF_OK; }   // (the cached tree's byte budget, MiB)
   if (n == "scene_compact") { ctx->scene_compact = iv < 0 ? -1 : iv != 0; return LF_OK; }

@@ -164,7 +164,7 @@ __device__ __forceinline__ void march_started_path(const LfLensDev* __restrict__
     T.n_scene += nlive;
     lanemask lit[K], lit_any = 0ull;
     if (VAR & kVarLights) {
-      lit_any = lights_pretest<K, !W1>(lens, r, alive, lit);
+      lit_any = lights_pretest<K, !W1, VAR>(lens, r, alive, lit);
       if (lit_any == 0ull) continue;
     } else {
 #pragma unroll
@@ -348,7 +348,7 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
         T.n_scene += nlive;
         lanemask lit[K], lit_any = 0ull;
         if (VAR & kVarLights) {
-          lit_any = lights_pretest<K, true>(lens, r, alive, lit);
+          lit_any = lights_pretest<K, true, VAR>(lens, r, alive, lit);
         } else {
 #pragma unroll
         for (int j = 0; j < K; j++) {
@@ -862,6 +862,12 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
                                                   case kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarOccl | kVarLights | kVarCoatFilt); break; \
                                                   case kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
                                                   case kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                                      case kVarNear | kVarLights | kVarBare: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarLights | kVarBare); break; \
+                                                      case kVarNear | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarLights | kVarCoat); break; \
+                                                      case kVarNear | kVarLights | kVarFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarLights | kVarFilt); break; \
+                                                      case kVarNear | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarLights | kVarCoatFilt); break; \
+                                                      case kVarNear | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarStack | kVarLights | kVarCoat); break; \
+                                                      case kVarNear | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarStack | kVarLights | kVarCoatFilt); break; \
                                                   default: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_CULL2(KK, WW, SS, CC)                                                                       \
   hipLaunchKernelGGL((k_march_cull<KK, WW, SS, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
@@ -884,6 +890,12 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
                                                   case kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarOccl | kVarLights | kVarCoatFilt); break; \
                                                   case kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
                                                   case kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                              case kVarNear | kVarLights | kVarBare: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarLights | kVarBare); break; \
+                                              case kVarNear | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarLights | kVarCoat); break; \
+                                              case kVarNear | kVarLights | kVarFilt: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarLights | kVarFilt); break; \
+                                              case kVarNear | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarLights | kVarCoatFilt); break; \
+                                              case kVarNear | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarStack | kVarLights | kVarCoat); break; \
+                                              case kVarNear | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarStack | kVarLights | kVarCoatFilt); break; \
                                                   default: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_ITEMS2(KK, CC)                                                                             \
   hipLaunchKernelGGL((k_march_items<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \

@@ -1024,12 +1024,15 @@ struct CullAuditArgs {
 };
 // LIGHTS (several lights): a marched ray of a dropped box refutes the table if it ends inside ANY light's lobe (light_admits:
 // the march's own per-light test)
-template <bool LIGHTS>
-__global__ __launch_bounds__(256) void k_cull_audit(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
-                                                    const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
-                                                    const float* __restrict__ mask, CullAuditArgs a,
-                                                    const unsigned long long* __restrict__ table,
-                                                    unsigned long long* __restrict__ out) {
+// VAR: 0 = the sun alone; kVarLights = several lights; kVarLights | kVarNear = a point light among them (k_cull_audit_near): the
+// EXACT per-ray test on the audit ray's own exit point (light_admits_at), never the widened direction the table was built with
+template <int VAR>
+__device__ __forceinline__ void cull_audit_body(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
+                                                const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
+                                                const float* __restrict__ mask, const CullAuditArgs& a,
+                                                const unsigned long long* __restrict__ table,
+                                                unsigned long long* __restrict__ out) {
+  constexpr bool LIGHTS = (VAR & kVarLights) != 0;
   const int blk = a.blk_first + (int)blockIdx.y * a.blk_step;
   const int cells = a.P * a.P;
   const int cell = (int)(blockIdx.x * blockDim.x + threadIdx.x);
@@ -1085,7 +1088,7 @@ __global__ __launch_bounds__(256) void k_cull_audit(const LfLensDev* __restrict_
       bool lit;
       if (LIGHTS) {
         lit = false;
-        for (int k = 0; k < lens->n_lights; k++) { float qk; lit = light_admits(lens, k, r.dx, r.dy, r.dz, qk) || lit; }
+        for (int k = 0; k < lens->n_lights; k++) { float qk; lit = light_admits_at<VAR>(lens, k, r.px, r.py, r.hz, r.dx, r.dy, r.dz, qk) || lit; }
         lit = lit && ((alive >> lane) & 1ull) != 0ull;
       } else {
         const float cg = fmaf(r.dx, sx, fmaf(r.dy, sy, r.dz * sz));
@@ -1100,6 +1103,21 @@ __global__ __launch_bounds__(256) void k_cull_audit(const LfLensDev* __restrict_
     if (v0) atomicAdd(&out[0], v0);
     if (v1) atomicAdd(&out[1], v1);
   }
+}
+template <bool LIGHTS>
+__global__ __launch_bounds__(256) void k_cull_audit(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
+                                                    const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
+                                                    const float* __restrict__ mask, CullAuditArgs a,
+                                                    const unsigned long long* __restrict__ table,
+                                                    unsigned long long* __restrict__ out) {
+  cull_audit_body<LIGHTS ? kVarLights : 0>(lens, pairs, seq_table, rec_table, mask, a, table, out);
+}
+__global__ __launch_bounds__(256) void k_cull_audit_near(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
+                                                         const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
+                                                         const float* __restrict__ mask, CullAuditArgs a,
+                                                         const unsigned long long* __restrict__ table,
+                                                         unsigned long long* __restrict__ out) {
+  cull_audit_body<kVarLights | kVarNear>(lens, pairs, seq_table, rec_table, mask, a, table, out);
 }
 
 // The table is complete (built here, or completed by an all-gather): what fraction of all (block, cell, path)
@@ -1142,7 +1160,11 @@ lf_status lfk_cull_finish(lf_ctx* ctx, uint64_t hash) {
     const dim3 grid((unsigned)((ctx->cull_cells + 255) / 256), (unsigned)n_own_blk);
     hipEvent_t ev = lf_timing_begin(ctx, LFK_CULL_AUDIT);
     // (the audit sees every light of the context, whatever the table was built for: lf_test_knob("cull_ignore_light"))
-    if (L.n_lights > 1)
+    if (lf_has_point_light(L))      // (a point light, also as the only light: the exact test at the audit ray's exit point)
+      hipLaunchKernelGGL(k_cull_audit_near, grid, dim3(256), 0, ctx->stream, ctx->lens_dev, ctx->pairs_dev,
+                         (const int*)(ctx->prog_dev + ctx->prog_seq_off), (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),
+                         audit_mask, a, ctx->cull_dev, ctx->cull_popc_dev + 1);
+    else if (L.n_lights > 1)
       hipLaunchKernelGGL(k_cull_audit<true>, grid, dim3(256), 0, ctx->stream, ctx->lens_dev, ctx->pairs_dev,
                          (const int*)(ctx->prog_dev + ctx->prog_seq_off), (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),
                          audit_mask, a, ctx->cull_dev, ctx->cull_popc_dev + 1);
@@ -1360,6 +1382,7 @@ static uint64_t cull_inputs_hash(const lf_ctx* ctx, CullLevelArgs a, const int* 
     std::memset(L.light_dir, 0, sizeof(L.light_dir)); std::memset(L.light_radiance, 0, sizeof(L.light_radiance));
     std::memset(L.light_inv_one_minus_cos, 0, sizeof(L.light_inv_one_minus_cos));
     std::memset(L.light_ss, 0, sizeof(L.light_ss)); std::memset(L.light_thr, 0, sizeof(L.light_thr));
+    std::memset(L.light_kind, 0, sizeof(L.light_kind)); std::memset(L.light_pos, 0, sizeof(L.light_pos));
   }
   uint64_t h = 0xcbf29ce484222325ull;
   h = fnv(h, &a, sizeof(a));
@@ -1402,6 +1425,12 @@ lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp) {
     a.lsx[a.n_lights] = sun ? L.sun_dir[0] : L.light_dir[k][0];
     a.lsy[a.n_lights] = sun ? L.sun_dir[1] : L.light_dir[k][1];
     a.lrho[a.n_lights] = lf_cull_lobe_rho(sun ? L.sun_inv_one_minus_cos : L.light_inv_one_minus_cos[k]);
+    // a point light enters as the direction unit(L) from the front vertex (light_dir[k]; light 0's is sun_dir too), its
+    // radius widened by what that direction can differ from the one an exit point of the front element sees it in
+    if (L.n_lights > 0 && L.light_kind[k] != LF_LIGHT_DIRECTIONAL && !ctx->cull_no_widening) {
+      const double lx = L.light_pos[k][0], ly = L.light_pos[k][1], lz = (double)L.light_pos[k][2] - (double)L.surf[0].zv;
+      a.lrho[a.n_lights] += lf_cull_near_widening(lf_front_reach(L.surf[0].radius, ctx->raw_semi_ap[0]), std::sqrt(lx * lx + ly * ly + lz * lz));
+    }
     a.n_lights++;
   }
   a.sx = a.lsx[0]; a.sy = a.lsy[0]; a.rho = a.lrho[0];

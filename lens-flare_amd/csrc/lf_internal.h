@@ -140,7 +140,16 @@ struct LfLensDev {
   float light_inv_one_minus_cos[LF_MAX_LIGHTS];
   float light_ss[LF_MAX_LIGHTS];
   float light_thr[LF_MAX_LIGHTS];   // lf_march_lobe_thr of light k (light 0's also travels as MarchArgs::lobe_thr)
+  // Point lights (lf_set_lights_ex): light k's kind (lf_light_kind) and, for LF_LIGHT_POINT, its position in lens millimetres;
+  // light_dir[k] is then unit(position - front vertex), what the cull pre-pass and lf_get_lights take.  Read by the
+  // kVarNear kernels alone, and behind everything else: no field another kernel reads has moved.
+  int light_kind[LF_MAX_LIGHTS];
+  float light_pos[LF_MAX_LIGHTS][3];
 };
+inline bool lf_has_point_light(const LfLensDev& L) {
+  for (int k = 0; k < L.n_lights; k++) if (L.light_kind[k] != LF_LIGHT_DIRECTIONAL) return true;
+  return false;
+}
 // Ghost occlusion (lf_set_ghost_occlusion): the LfOcclDev record of a launch lies BEHIND the device's LfLensDev, in the same
 // allocation, at kLensOcclOffset -- not inside it: LfLensDev keeps its size and its 4-byte alignment, so the kernels a context
 // without occlusion launches compile to what they were, and nothing keyed on the lens (the cull table's hash) sees it.
@@ -559,7 +568,8 @@ struct lf_ctx {
   bool cull_force = false;                     // lf_test_knob("cull_force"): the culled kernel whatever the table starts
   bool cull_weights_first = false;             // lf_test_knob("cull_weights_first"): k_march_cull<K, true>
   int cull_ignore_light = -1;                  // lf_test_knob("cull_ignore_light"): the pre-pass / resolve leave this light out (a table wrong by construction)
-  bool cull_no_prefix = false;                 // lf_test_knob("cull_no_prefix"): every started path marched alone from the sensor (round 5)
+  bool cull_no_widening = false;               // lf_test_knob("cull_no_widening"): a point light's radius in the cull table NOT widened (a table wrong by construction)
+  bool cull_no_prefix = false;                // lf_test_knob("cull_no_prefix"): every started path marched alone from the sensor (round 5)
   int scene_compact = -1;                      // lf_test_knob("scene_compact"): -1 = by the tree's size, 0 / 1 forced
   bool comm_force_exchange = false;            // lf_test_knob("comm_force_exchange"): the collectives also with one rank
   int scene_lens_strided = -1;                 // lf_test_knob("scene_lens_strided"): k_scene_lens's wave tile: -1 by the tree's size, 0 / 1
@@ -657,12 +667,26 @@ inline void lf_install_split(lf_ctx* ctx, const LfSplit& s) {
 }
 // the kernel variant of the weighted march (lf_march_events.h: kVarBare .. kVarCoatFilt, | kVarLights: several lights, | kVarStack,
 // | kVarOccl: ghost occlusion -- always with kVarLights, whose epilogue it extends: one light is a list of one)
+// | kVarNear: some installed light is a point light (lf_set_lights_ex) -- with kVarLights too, also when it is the only light
 inline int lf_march_variant(const lf_ctx* ctx) {
+  const bool near = lf_has_point_light(ctx->lens);
   return (ctx->coat.n > 0 ? 1 : 0) | (ctx->mask_filter == LF_MASK_BILINEAR ? 2 : 0) |
-         ((ctx->lens.n_lights > 1 || ctx->ghost_occlusion) ? 4 : 0) |
+         ((ctx->lens.n_lights > 1 || ctx->ghost_occlusion || near) ? 4 : 0) |
          (ctx->coat.n_stacked > 0 ? 8 : 0) |   // (kVarStack: only ever with kVarCoat -- a stacked interface counts in coat.n)
-         (ctx->ghost_occlusion ? 16 : 0);
+         (ctx->ghost_occlusion ? 16 : 0) |
+         (near ? 32 : 0);
 }
+// The front element as a point light sees it (lf_set_lights_ex): r_f = sqrt(h0^2 + sag(h0)^2), the largest distance from the
+// front vertex to a point of its clear aperture (radius 0: flat; a semi-aperture beyond the sphere: the hemisphere's)
+inline double lf_front_reach(float radius, float semi_aperture) {
+  const double h = semi_aperture, R = std::fabs((double)radius);
+  const double sag = radius == 0.0f ? 0.0 : (h < R ? R - std::sqrt(R * R - h * h) : R);
+  return std::sqrt(h * h + sag * sag);
+}
+// ... and how much wider than its lobe the cull pre-pass takes a point light at distance dist from the front vertex, in
+// direction space around unit(L): for P on the front cap |unit(L - P) - unit(L)| <= |P| / min(|L - P|, |L|) <= r_f / (dist - r_f)
+// (DESIGN.md section 5), with the relative and absolute float slack lf_cull_lobe_rho carries
+inline float lf_cull_near_widening(double r_f, double dist) { return (float)(r_f / (dist - r_f) * 1.001 + 1e-5); }
 // the cull table is not this context's alone: shared between ranks, or built only in part (the frame dealt by blocks)
 inline bool lf_cull_table_split(const lf_ctx* ctx) {
   return ctx->split.table != LfSplit::kOwn || ctx->split.deal == LfSplit::kBlocks;
@@ -696,6 +720,10 @@ lf_status lfk_lens_rays(lf_ctx* ctx, int lambda, int n, const float* d_xy, const
 lf_status lf_occlusion_ready(const lf_ctx* ctx, const char* who);
 lf_status lf_fill_occlusion(const lf_ctx* ctx, double world_per_mm, LfOcclDev* o);
 lf_status lfk_ghost_ray_visibility(lf_ctx* ctx, const LfOcclDev& o, size_t n, const float* d_rays, unsigned char* d_vis);
+// point lights (lf_set_lights_ex): the installed ones against the front element of the lens as it is now (`who` names the
+// caller in the refusal, LF_ERR_STATE); the batched per-ray lobe factors (d_rays: n x 6 floats, d_out: n x n_lights floats)
+lf_status lf_point_lights_fit(const lf_ctx* ctx, const char* who);
+lf_status lfk_ghost_ray_light_factors(lf_ctx* ctx, size_t n, const float* d_rays, float* d_out);
 // lf_lens_camera.hip
 lf_status lf_lenscam_prepare(lf_ctx* ctx);            // table + calibration up to date (no-op when clean)
 lf_status lf_upload_primary_table(lf_ctx* ctx);       // LfPrimaryDev from ctx->lens (k_lens_rays needs it too)

@@ -512,7 +512,7 @@ void k_march(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ 
             // with a 1/16 margin computed once on the host; the lobe factor itself is evaluated
             // without cancellation after the weight re-march, see lobe_q, and decides)
             lanemask lit[K], lit_any = 0ull;
-            if (VAR & kVarLights) lit_any = lights_pretest<K, !kW1>(lens, r, alive, lit);
+            if (VAR & kVarLights) lit_any = lights_pretest<K, !kW1, VAR>(lens, r, alive, lit);
 #pragma unroll
             for (int j = 0; j < K; j++) {
               if (VAR & kVarLights) break;
@@ -698,6 +698,22 @@ __global__ __launch_bounds__(256) void k_ghost_ray_visibility(LfOcclDev o, int n
   visible[i] = ghost_ray_visible(o, r[0], r[1], r[2], r[3], r[4], r[5]) ? 1 : 0;
 }
 
+// lf_ghost_ray_light_factors: per exit ray {origin xyz (z absolute), direction xyz} and installed light k, (1 - q_k)^2 where
+// the ray lies inside light k and 0 elsewhere -- the lit epilogue's own test and factor (light_admits_at), without a weight
+__global__ __launch_bounds__(256) void k_ghost_ray_light_factors(const LfLensDev* __restrict__ lens, int n, const float* __restrict__ rays,
+                                                                 float* __restrict__ out) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rays + 6 * (size_t)i;
+  const int nl = lens->n_lights;
+  for (int k = 0; k < nl; k++) {
+    float q;
+    const bool in = light_admits_at<kVarLights | kVarNear>(lens, k, r[0], r[1], r[2] - lens->surf[0].zv, r[3], r[4], r[5], q);
+    const float om = 1.0f - q;
+    out[(size_t)i * (size_t)nl + (size_t)k] = in ? om * om : 0.0f;
+  }
+}
+
 // The support texture of the bilinear stop mask (lf_set_mask_filter; DESIGN.md section 5, "the support texture"):
 // S is 2 mw x 2 mh, separable per axis with clamped indices, S[2 i] = max(t[i - 1], t[i]), S[2 i + 1] =
 // max(t[i], t[i + 1]) of t = max(texel, 0): the nearest lookup of the geometry-only march, run on (S, 2 mw, 2 mh),
@@ -805,6 +821,8 @@ void lf_derive_lens(lf_ctx* ctx, int n, int stop, int n_lambda, const float* rad
   std::memcpy(L.light_inv_one_minus_cos, keep.light_inv_one_minus_cos, sizeof(L.light_inv_one_minus_cos));
   std::memcpy(L.light_ss, keep.light_ss, sizeof(L.light_ss));
   std::memcpy(L.light_thr, keep.light_thr, sizeof(L.light_thr));
+  std::memcpy(L.light_kind, keep.light_kind, sizeof(L.light_kind));
+  std::memcpy(L.light_pos, keep.light_pos, sizeof(L.light_pos));
   L.n_surf = n; L.stop = stop; L.n_lambda = n_lambda;
   float z = 0.0f;
   for (int k = 0; k < n; k++) {
@@ -1229,6 +1247,16 @@ static int march_strata(int spp) {
 // what a launch uploads before anything runs: the event program, the lens (with the launch's fixed-point grid), the paths
 static lf_status march_upload(lf_ctx* ctx, int spp, int total_paths = 0) {
   ctx->lens.pitch = ctx->sensor_w_mm / (float)ctx->W;
+  if (lf_has_point_light(ctx->lens)) {
+    // the installed point lights against the front element as it is NOW: lf_set_lens keeps the lights, a launch through a
+    // lens whose front element has come too close to one is refused (lf_set_lights_ex's limits, lensflare.h)
+    const lf_status st = lf_point_lights_fit(ctx, "lf_trace_ghosts");
+    if (st != LF_OK) return st;
+    if (ctx->ghost_occlusion)
+      return lf_fail(ctx, LF_ERR_STATE, "lf_trace_ghosts: ghost occlusion with a point light installed is not supported (a point light's "
+                                        "shadow ray ends at the light: no kernel is built for it) -- switch lf_set_ghost_occlusion off, "
+                                        "or install directional lights only");
+  }
   if (ctx->events_dirty) {
     lf_status st = build_event_table(ctx);
     if (st != LF_OK) return st;
@@ -1432,6 +1460,12 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
                                                   case kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarOccl | kVarLights | kVarCoatFilt); break; \
                                                   case kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
                                                   case kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                   case kVarNear | kVarLights | kVarBare: LF_LAUNCH_MARCH2(KK, kVarNear | kVarLights | kVarBare); break; \
+                                   case kVarNear | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarNear | kVarLights | kVarCoat); break; \
+                                   case kVarNear | kVarLights | kVarFilt: LF_LAUNCH_MARCH2(KK, kVarNear | kVarLights | kVarFilt); break; \
+                                   case kVarNear | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarNear | kVarLights | kVarCoatFilt); break; \
+                                   case kVarNear | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarNear | kVarStack | kVarLights | kVarCoat); break; \
+                                   case kVarNear | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarNear | kVarStack | kVarLights | kVarCoatFilt); break; \
                                                   default: LF_LAUNCH_MARCH2(KK, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_MARCH2(KK, CC)                                                                   \
   hipLaunchKernelGGL((k_march<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
@@ -1530,6 +1564,15 @@ lf_status lfk_ghost_ray_visibility(lf_ctx* ctx, const LfOcclDev& o, size_t n, co
   if (n == 0) return LF_OK;
   hipLaunchKernelGGL(k_ghost_ray_visibility, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, o, (int)n, d_rays,
                      d_vis);
+  LF_HIP(ctx, hipGetLastError());
+  return LF_OK;
+}
+
+// (the caller has uploaded ctx->lens to lens_dev on the same stream; d_out: n x n_lights floats)
+lf_status lfk_ghost_ray_light_factors(lf_ctx* ctx, size_t n, const float* d_rays, float* d_out) {
+  if (n == 0) return LF_OK;
+  hipLaunchKernelGGL(k_ghost_ray_light_factors, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->lens_dev, (int)n,
+                     d_rays, d_out);
   LF_HIP(ctx, hipGetLastError());
   return LF_OK;
 }

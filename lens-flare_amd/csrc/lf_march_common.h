@@ -91,10 +91,26 @@ __device__ __forceinline__ bool light_admits(const LfLensDev* __restrict__ lens,
   q = lobe_q(dx, dy, dz, sx, sy, sz, lens->light_ss[k], lens->light_inv_one_minus_cos[k]);
   return cg > lens->light_thr[k] && q < 1.0f;
 }
+// ... of the ray that left the front element at (px, py, front vertex + hz) along d: under VAR & kVarNear a POINT light k
+// (lens->light_kind[k], wave-uniform: a scalar branch) takes the direction to it from that point -- s = L_k - P per lane,
+// inside iff d.s > 0 and q < 1 (lf_point_lobe_q, lf_march_events.h); a directional light, and every light of a kernel
+// without kVarNear, is decided by the direction alone, as above.
+template <int VAR>
+__device__ __forceinline__ bool light_admits_at(const LfLensDev* __restrict__ lens, int k, float px, float py, float hz, float dx, float dy,
+                                                float dz, float& q) {
+  if ((VAR & kVarNear) && lens->light_kind[k] != LF_LIGHT_DIRECTIONAL) {
+    float cg;
+    q = lf_point_lobe_q(dx, dy, dz, px, py, lens->surf[0].zv + hz, lens->light_pos[k][0], lens->light_pos[k][1], lens->light_pos[k][2],
+                        lens->light_inv_one_minus_cos[k], cg);
+    return cg > 0.0f && q < 1.0f;
+  }
+  return light_admits(lens, k, dx, dy, dz, q);
+}
 // The pre-test of a completed path's K rays: lit[j] = the lanes of alive[j] that ANY light's pre-test admits (d.s_k > thr_k)
 // and then -- GATE, the geometry-first kernels: what lobe_gate is to one light -- that lie inside ANY light's lobe, so that
 // a wavelength none of whose lanes will contribute to any light is not marched again.  Returns the union of the masks.
-template <int K, bool GATE>
+// (VAR & kVarNear: a point light's pre-test is lf_point_pretest on the ray's exit point, a superset of its lobe)
+template <int K, bool GATE, int VAR = kVarLights>
 __device__ __forceinline__ lanemask lights_pretest(const LfLensDev* __restrict__ lens, const Ray (&r)[K], const lanemask (&alive)[K],
                                                    lanemask (&lit)[K]) {
   const int n = lens->n_lights;
@@ -103,6 +119,11 @@ __device__ __forceinline__ lanemask lights_pretest(const LfLensDev* __restrict__
   for (int j = 0; j < K; j++) {
     bool near = false;
     for (int k = 0; k < n; k++) {
+      if ((VAR & kVarNear) && lens->light_kind[k] != LF_LIGHT_DIRECTIONAL) {
+        near = lf_point_pretest(r[j].dx, r[j].dy, r[j].dz, r[j].px, r[j].py, lens->surf[0].zv + r[j].hz, lens->light_pos[k][0],
+                                lens->light_pos[k][1], lens->light_pos[k][2], lens->light_thr[k]) || near;
+        continue;
+      }
       const float cg = fmaf(r[j].dx, lens->light_dir[k][0], fmaf(r[j].dy, lens->light_dir[k][1], r[j].dz * lens->light_dir[k][2]));
       near = near || cg > lens->light_thr[k];
     }
@@ -115,7 +136,7 @@ __device__ __forceinline__ lanemask lights_pretest(const LfLensDev* __restrict__
   for (int j = 0; j < K; j++) {
     if (lit[j] != 0ull) {
       bool in = false;
-      for (int k = 0; k < n; k++) { float q; in = light_admits(lens, k, r[j].dx, r[j].dy, r[j].dz, q) || in; }
+      for (int k = 0; k < n; k++) { float q; in = light_admits_at<VAR>(lens, k, r[j].px, r[j].py, r[j].hz, r[j].dx, r[j].dy, r[j].dz, q) || in; }
       lit[j] &= __ballot(in);
     }
     lit_any |= lit[j];
@@ -155,7 +176,7 @@ __device__ __forceinline__ void lights_epilogue(const LfLensDev* __restrict__ le
   unsigned w_tested = 0u, w_blocked = 0u;   // ... the wave's tallies (wave-uniform)
   for (int k = 0; k < n; k++) {
     float qq;
-    const bool in = light_admits(lens, k, rw.dx, rw.dy, rw.dz, qq);
+    const bool in = light_admits_at<VAR>(lens, k, rw.px, rw.py, rw.hz, rw.dx, rw.dy, rw.dz, qq);
     const float om = 1.0f - qq;
     float contrib = wq * (om * om);
     contrib = (mine && in && contrib > 0.0f) ? contrib : 0.0f;

@@ -361,8 +361,41 @@ __device__ __forceinline__ lanemask stop_event(Ray& r, float dzv, float h2, floa
 enum : int { kVarBare = 0, kVarCoat = 1, kVarFilt = 2, kVarCoatFilt = 3,
              kVarLights = 4,    // | kVarLights: the context holds several lights (lf_set_lights): the lobe pre-test and the lit epilogue loop over them
              kVarStack = 8,     // | kVarStack (only with kVarCoat): some interface holds a stack of layers (lf_set_lens_coating_stacks)
-             kVarOccl = 16 };   // | kVarOccl (only with kVarLights): a lit ray adds only what the scene does not block (lf_set_ghost_occlusion);
+             kVarOccl = 16,     // | kVarOccl (only with kVarLights): a lit ray adds only what the scene does not block (lf_set_ghost_occlusion);
                                 //   differs from its kVarLights twin in lights_epilogue alone (lf_march_common.h)
+             kVarNear = 32 };   // | kVarNear (only with kVarLights): some light is a POINT light (lf_set_lights_ex): the pre-test, the gate
+                                //   and the lit epilogue form the direction to such a light per lane, from the ray's exit point
+
+// ---- a light at a finite distance (lf_set_lights_ex, LF_LIGHT_POINT; DESIGN.md section 4, "point lights") -------------
+// The lobe factor of a ray that has left the front element at (px, py, z) (z absolute: front vertex z + hz) along d, for a
+// light at L: s = L - P (three float subtractions), ss = |s|^2, and the sun's expression (lf_march_common.h lobe_q) on the
+// non-unit s -- with the IEEE root and division, so that the host (lf_light_lobe_factor) and the kernels, which all
+// call THIS definition, agree bit for bit.  cg = d.s: the ray looks towards the light iff cg > 0.
+__host__ __device__ inline float lf_point_lobe_q(float dx, float dy, float dz, float px, float py, float z, float Lx, float Ly,
+                                                 float Lz, float inv_1mc, float& cg) {
+  const float sx = Lx - px, sy = Ly - py, sz = Lz - z;
+  const float ss = fmaf(sx, sx, fmaf(sy, sy, sz * sz));
+  cg = fmaf(dx, sx, fmaf(dy, sy, dz * sz));
+  const float cx = fmaf(dy, sz, -(dz * sy)), cy = fmaf(dz, sx, -(dx * sz)), cz = fmaf(dx, sy, -(dy * sx));
+  const float c2 = fmaf(cx, cx, fmaf(cy, cy, cz * cz));
+  const float dd = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+  const float ds = dd * ss;
+  const float den = fmaf(sqrtf(ds), cg, ds);      // (correctly rounded on both sides: -fhip-fp32-correctly-rounded-divide-sqrt)
+  return (c2 / den) * inv_1mc;
+}
+// ... and the cheap test that SELECTS lanes for it (any superset of cg > 0 && q < 1 will do): cos(theta) > thr, thr the
+// directional pre-test's threshold (1/16 of the lobe and 4e-7 below cos(alpha), 0 < thr: lf_march_lobe_thr_of), as
+// cg > 0 && cg^2 > thr^2 |d|^2 |s|^2 -- no root, no division.  The float error of cg^2 / (|d|^2 |s|^2) is below 4e-7
+// relative (five roundings), 2e-7 in the cosine; thr^2 is taken 1e-6 smaller (5e-7 in the cosine) on top of thr's own
+// margin, and the exact test's own rounding (q good to 1e-6 relative) moves its edge by 1e-6 (1 - cos(alpha)) at most.
+__host__ __device__ inline bool lf_point_pretest(float dx, float dy, float dz, float px, float py, float z, float Lx, float Ly,
+                                                 float Lz, float thr) {
+  const float sx = Lx - px, sy = Ly - py, sz = Lz - z;
+  const float ss = fmaf(sx, sx, fmaf(sy, sy, sz * sz));
+  const float cg = fmaf(dx, sx, fmaf(dy, sy, dz * sz));
+  const float dd = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+  return cg > 0.0f && cg * cg > ((thr * thr) * 0.999999f) * (dd * ss);
+}
 // The stop of a kernel instantiated for variant VAR.  Under the filter the geometry-only march (W = false) runs
 // the UNCHANGED nearest lookup on the support texture S (2 mw x 2 mh floats behind the texels, k_mask_support:
 // S > 0 exactly where one of the four texels of the bilinear footprint is open), the weighted march the

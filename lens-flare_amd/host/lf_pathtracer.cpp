@@ -183,20 +183,29 @@ void PathTracer::use_geometric_ghosts(int n_surfaces, int stop_index, int n_lamb
   check(lf_set_sun(ctx_, sun_dir, rad, sun_angular_radius), "lf_set_sun");
   geometric_ = true;
   geo_spp_ = spp;
-  lights_from_flares_ = false;
+  lights_from_flares_ = lights_from_scene_ = false;
   frame_ready_ = false;
 }
 
 void PathTracer::set_lights(int n_lights, const float* dir, const float* radiance, const float* angular_radius) {
   if (!geometric_) throw std::runtime_error("set_lights: use_geometric_ghosts comes first (it installs the lens)");
   check(lf_set_lights(ctx_, n_lights, dir, radiance, angular_radius), "lf_set_lights");
-  lights_from_flares_ = false;
+  lights_from_flares_ = lights_from_scene_ = false;
   frame_ready_ = false;
 }
 
 void PathTracer::use_lights_from_flares(float angular_radius) {
   if (!geometric_) throw std::runtime_error("use_lights_from_flares: use_geometric_ghosts comes first (it installs the lens)");
   lights_from_flares_ = true;
+  lights_from_scene_ = false;
+  lights_radius_ = angular_radius;
+  frame_ready_ = false;
+}
+
+void PathTracer::use_lights_from_scene(float angular_radius) {
+  if (!geometric_) throw std::runtime_error("use_lights_from_scene: use_geometric_ghosts comes first (it installs the lens)");
+  lights_from_scene_ = true;
+  lights_from_flares_ = false;
   lights_radius_ = angular_radius;
   frame_ready_ = false;
 }
@@ -238,8 +247,9 @@ void PathTracer::generate_ghost_buffer() {
   // (same place in the frame: main thread, before the workers start) and raytrace_pixel reads it.
   if (!camera) throw std::runtime_error("generate_ghost_buffer: camera not set");
   upload_textures();
-  if (ghost_occlusion_) {
-    // the ghosts' shadow rays leave from the camera's pose as it stands at this frame (find_sun_pos may never have run)
+  if (ghost_occlusion_ || lights_from_scene_) {
+    // the ghosts' shadow rays leave from -- and the scene's point lights are mapped through -- the camera's pose as it
+    // stands at this frame (find_sun_pos may never have run)
     double pos[3] = {camera->pos.x, camera->pos.y, camera->pos.z};
     check(lf_set_camera(ctx_, camera->c2w, pos, camera->hFov, camera->vFov), "lf_set_camera");
   }
@@ -266,7 +276,8 @@ void PathTracer::generate_ghost_buffer() {
   plan.jitter = counter_jitter ? LF_FRAME_JITTER_COUNTER : LF_FRAME_JITTER_MT19937;
   plan.mt_seed = jitter_seed; plan.counter_key = 0x1e45f1a4eULL;
   plan.ghosts = geometric_ ? LF_FRAME_GHOSTS_MARCH : LF_FRAME_GHOSTS_PARAXIAL;
-  plan.sun_from_flares = lights_from_flares_ ? 1 : 0;   // (0: use_geometric_ghosts / set_lights installed the lights explicitly)
+  // (0: use_geometric_ghosts / set_lights installed the lights explicitly; 2: the flares and the device scene's PointLights)
+  plan.sun_from_flares = lights_from_scene_ ? 2 : lights_from_flares_ ? 1 : 0;
   plan.sun_angular_radius = lights_radius_;
   plan.geo_spp = geo_spp_; plan.geo_key = 0x1e45f1a4eULL;
   plan.lens_camera_mode = geometric_ ? lens_camera_mode : 0;

@@ -131,6 +131,11 @@ class PathTracer {
   // ... or every in-frame light of the flare state (flare_origins / flare_radiance as find_sun_pos or the host left
   // them), taken over by the frame sequence at every generate_ghost_buffer (lf_set_lights_from_flares)
   void use_lights_from_flares(float angular_radius);
+  // ... or those AND every PointLight of the device scene (set_scene / load_collada), as point lights of the march at their
+  // own distance: lf_set_lights_from_scene at every generate_ghost_buffer, through the camera's pose at the frame and
+  // lens_world_per_mm.  Opt-in: a mirror that never calls this renders what it rendered.  Not together with
+  // use_ghost_occlusion when the scene holds a PointLight in front of the lens (the launch is refused).
+  void use_lights_from_scene(float angular_radius);
   // after use_geometric_ghosts: the scene hides the march's ghosts (lf_set_ghost_occlusion, scale lens_world_per_mm): a lit
   // ghost ray adds only what no primitive between the front element and the sky blocks.  Needs a device scene (set_scene /
   // load_collada) and the camera at the frame.  Off by default: the frames are those of a mirror without this call.
@@ -160,7 +165,7 @@ class PathTracer {
   lf_ctx* ctx_ = nullptr;
   bool frame_ready_ = false, textures_uploaded_ = false, geometric_ = false, device_scene_ = false;
   int geo_spp_ = 0;
-  bool lights_from_flares_ = false;
+  bool lights_from_flares_ = false, lights_from_scene_ = false;
   bool ghost_occlusion_ = false;
   float lights_radius_ = 0.05f;
   std::vector<double> star_;    // host mirror of raytrace_starburst for every pixel
