@@ -571,8 +571,10 @@ lf_status lf_get_lights(lf_ctx* ctx, int* n_lights, float* dir, float* radiance,
  * 4 | 32, lf_get_ghost_occlusion's *march_variant); a context without one launches exactly what it launched before.
  * lf_set_lens KEEPS the installed lights; if the new front element is too close to an installed point light,
  * lf_trace_ghosts (and lf_cull_prepare, lf_ghost_ray_light_factors) refuse with LF_ERR_STATE until the lights or the lens
- * change.  NOT SUPPORTED: ghost occlusion together with a point light -- lf_trace_ghosts refuses with LF_ERR_STATE (the
- * shadow ray of a point light ends at the light; no kernel is built for it).
+ * change.  GHOST OCCLUSION together with a point light needs shadow rays that end at the light:
+ * lf_set_ghost_occlusion_reach(LF_OCCLUSION_REACH_LIGHT) below.  Under the default, LF_OCCLUSION_REACH_SKY, lf_trace_ghosts
+ * refuses the combination with LF_ERR_STATE and names that call: a ray that runs on to the sky would let a wall BEHIND the
+ * lamp hide it.
  * lf_get_lights reports a point light as the unit vector from the front vertex to its position; lf_get_lights_ex its kind
  * and its position as stored (any pointer may be NULL; arrays of LF_MAX_LIGHTS lights).
  * COST, as measured (the bench frame, 1080p x 256 spp, table rebuilt and audited inside every frame; profiles/near_light_cost.json):
@@ -630,6 +632,44 @@ lf_status lf_get_ghost_occlusion_stats(lf_ctx* ctx, uint64_t out[2]);
  * meets no primitive, else 0.  Preconditions as lf_trace_ghosts' with occlusion on (which must be on: it carries
  * world_per_mm), except that no light is needed. */
 lf_status lf_ghost_ray_visibility(lf_ctx* ctx, size_t n, const float* rays, unsigned char* visible);
+/* THE REACH OF A SHADOW RAY: ghost occlusion for point lights.  "Does this ray see the sky" is the wrong question for a lamp
+ * in the room: a wall behind the lamp must not hide it, a wall between the lens and the lamp must.  A setting of the context
+ * beside lf_set_ghost_occlusion, and separate from it:
+ *   LF_OCCLUSION_REACH_SKY (default)  every shadow ray runs to max_t = +inf: the contract above, to the letter -- and with a
+ *                                     point light installed and occlusion on, lf_trace_ghosts refuses with LF_ERR_STATE;
+ *   LF_OCCLUSION_REACH_LIGHT          the shadow ray of light k runs from min_t = 0 to max_t = reach_k; with occlusion on and
+ *                                     a point light installed lf_trace_ghosts launches (the kVarNear | kVarOccl kernels:
+ *                                     *march_variant = 4 | 16 | 32 plus the coat / filter / stack bits).
+ * Any other value: LF_ERR_INVALID, the previous state stays.  The setting survives lf_set_lens, lf_set_lights*, lf_focus_lens,
+ * lf_set_frame and switching lf_set_ghost_occlusion off and on; it has no effect while occlusion is off, and none without a
+ * point light: under LF_OCCLUSION_REACH_LIGHT directional lights alone launch the variant (4 | 16 | ...) and render the
+ * frames they render under LF_OCCLUSION_REACH_SKY, bit for bit.
+ * The contract per (ray, light k) is the occlusion contract above with ONE change, the end of the shadow ray:
+ *   - a directional light: reach_k = +inf;
+ *   - a point light stored at L (float32 lens millimetres, as lf_get_lights_ex reports it), the re-marched ray's exit point
+ *     (px, py, z) (z absolute) and direction d, all in double and in this order:
+ *         s = ((double)Lx - px, (double)Ly - py, (double)Lz - z),     dc = unit(d)  (d times 1 / |d|, the shadow ray's own dc),
+ *         t = wpm ((s.x dc.x + s.y dc.y) + s.z dc.z),                 reach_k = t > 0 ? t : 0
+ *     -- the ray parameter, in world units, of the point of the ray nearest the lamp (c2w is a rotation).  No epsilon is
+ *     taken off either end.  A lamp many kilometres away behaves as the sun in its direction does;
+ *   - origin and direction of the shadow ray are unchanged; contrib_k is computed as ever and added iff the any-hit walk
+ *     over [0, reach_k], with the scene term's double-precision primitive tests, finds nothing;
+ *   - the decision for light k does not depend on the other lights: a frame of K lights of mixed kinds is the sum of the K
+ *     single-light frames under the same settings, bit for bit; the stats, rays_hit_light and every other counter keep
+ *     their meaning.
+ * A primitive that encloses the lamp blocks it, as it blocks the scene term's shadow rays to a PointLight. */
+typedef enum { LF_OCCLUSION_REACH_SKY = 0, LF_OCCLUSION_REACH_LIGHT = 1 } lf_occlusion_reach;
+lf_status lf_set_ghost_occlusion_reach(lf_ctx* ctx, int reach);
+lf_status lf_get_ghost_occlusion_reach(lf_ctx* ctx, int* reach);
+/* Host arithmetic, no device: reach_k of ONE exit ray {origin xyz in lens millimetres (z absolute), direction xyz} for ONE
+ * light (kind, vec as lf_set_lights_ex takes them): +inf for LF_LIGHT_DIRECTIONAL, the definition above -- the one the
+ * kernels call, bit for bit -- for LF_LIGHT_POINT.  world_per_mm not finite or <= 0, or a non-finite input: LF_ERR_INVALID. */
+lf_status lf_ghost_shadow_reach(int kind, const float vec[3], const float ray[6], double world_per_mm, double* reach);
+/* ... and on the device, for the state INSTALLED: visible[i n_lights + k] = 1 iff the shadow ray of exit ray i finds nothing
+ * over [0, reach_k] -- the epilogue's own mapping, reach and walk, whether or not the ray lies in lobe k.  Preconditions as
+ * lf_ghost_ray_visibility's, plus a lens and at least one light; with a point light installed under
+ * LF_OCCLUSION_REACH_SKY it refuses as the launch does. */
+lf_status lf_ghost_ray_light_visibility(lf_ctx* ctx, size_t n, const float* rays, unsigned char* visible);
 /* Sun hand-over from the scene to the march: turn in-frame flare `flare` of lf_find_sun_pos /
  * lf_set_flares (normalised screen position flare_origins[flare], radiance flare_radiance[flare];
  * src/pathtracer/pathtracer.cpp:32-64, camera.cpp:245-273) into the lens-space light of

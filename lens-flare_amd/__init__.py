@@ -40,6 +40,7 @@ ABI_SYMBOLS = [
     "lf_set_lights_ex", "lf_get_lights_ex", "lf_validate_light", "lf_light_lobe_factor", "lf_ghost_ray_light_factors",
     "lf_set_lights_from_scene",
     "lf_set_ghost_occlusion", "lf_get_ghost_occlusion", "lf_get_ghost_occlusion_stats", "lf_ghost_ray_visibility",
+    "lf_set_ghost_occlusion_reach", "lf_get_ghost_occlusion_reach", "lf_ghost_shadow_reach", "lf_ghost_ray_light_visibility",
     "lf_set_sun_from_flares", "lf_paraxial_efl", "lf_paraxial_image_scale", "lf_set_ghost_pairs", "lf_set_pupil_subcells", "lf_set_tile_stride", "lf_trace_ghosts", "lf_set_march_culling", "lf_get_cull_info", "lf_get_cull_table", "lf_get_cull_started_fraction", "lf_get_cull_reason", "lf_set_cull_audit", "lf_get_cull_audit", "lf_test_knob", "lf_comm_share_cull", "lf_set_cull_share", "lf_cull_prepare", "lf_cull_table_view", "lf_cull_commit", "lf_get_march_fix_bits", "lf_generate_lens_rays", "lf_get_counters", "lf_reset_counters", "lf_get_executed_events", "lf_get_march_stats", "lf_native_sqrt", "lf_native_rcp", "lf_set_starburst_spectrum", "lf_load_collada", "lf_march_tables",
     "lf_timing_enable", "lf_timing_reset", "lf_timing_get",
     "lf_clear_ghost_buffer", "lf_draw_ghost", "lf_rasterize_textured_triangle", "lf_fill_textured_pixel",
@@ -310,6 +311,38 @@ def light_lobe_factors(kind, vec, angular_radius, rays):
             raise LensFlareError(st, "lf_light_lobe_factor")
         qs[i], ins[i] = q.value, bool(inside.value)
     return qs, ins
+
+
+# where the shadow ray of a point light ends under ghost occlusion (lf_set_ghost_occlusion_reach): at the sky (the default: occlusion
+# with a point light installed is refused) or at the light
+OCCLUSION_REACH_SKY, OCCLUSION_REACH_LIGHT = 0, 1
+
+
+def ghost_shadow_reach(kind, vec, rays, world_per_mm):
+    """reach_k of n x 6 exit rays {origin xyz in lens mm (z absolute), direction xyz} for one light, float64 array of n: +inf for
+    LIGHT_DIRECTIONAL; for LIGHT_POINT at vec the ray parameter, in world units, of the ray's point nearest the lamp, never
+    below 0 (lf_ghost_shadow_reach, host only: the definition the occlusion kernels call)."""
+    if int(kind) not in (LIGHT_DIRECTIONAL, LIGHT_POINT):
+        raise ValueError("ghost_shadow_reach: kind must be LIGHT_DIRECTIONAL or LIGHT_POINT")
+    v = np.asarray(vec)
+    if v.shape != (3,):
+        raise ValueError("ghost_shadow_reach: vec must be 3 numbers")
+    r = np.asarray(rays)
+    if r.ndim != 2 or r.shape[1] != 6:
+        raise ValueError("ghost_shadow_reach: rays must be n x 6 (origin xyz in lens mm, direction xyz)")
+    v, r, w = np.ascontiguousarray(v, np.float32), np.ascontiguousarray(r, np.float32), float(world_per_mm)
+    if not np.isfinite(v).all() or not np.isfinite(r).all() or not (np.abs(r[:, 3:]).max(axis=1) > 0.0).all():
+        raise ValueError("ghost_shadow_reach: vec and rays must be finite, directions non-zero")
+    if not (w > 0.0 and np.isfinite(w)):
+        raise ValueError("ghost_shadow_reach: world_per_mm must be > 0 and finite")
+    out, t = np.zeros(len(r), np.float64), C.c_double()
+    fn, vp, base = load_library().lf_ghost_shadow_reach, _fp(v, C.c_float), r.ctypes.data
+    for i in range(len(r)):
+        st = fn(int(kind), vp, C.cast(base + 24 * i, C.POINTER(C.c_float)), C.c_double(w), C.byref(t))
+        if st != 0:
+            raise LensFlareError(st, "lf_ghost_shadow_reach")
+        out[i] = t.value
+    return out
 
 
 # how the march and the lens camera read the stop mask (lf_set_mask_filter)
@@ -943,6 +976,37 @@ class LensFlare:
         self._ck(self.lib.lf_ghost_ray_visibility(self.ctx, C.c_size_t(len(r)), _fp(r, C.c_float),
                                                   vis.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return vis.astype(bool)
+
+    def set_ghost_occlusion_reach(self, reach):
+        """Where the shadow ray of a POINT light ends: OCCLUSION_REACH_SKY (the default: the ray runs on to the sky, and occlusion
+        with a point light installed is refused) or OCCLUSION_REACH_LIGHT (it ends at the point of the ray nearest the lamp: a
+        wall behind the lamp does not hide it).  A setting of the context; no effect while occlusion is off, none on
+        directional lights."""
+        if isinstance(reach, bool) or not isinstance(reach, (int, np.integer)) or int(reach) not in (OCCLUSION_REACH_SKY, OCCLUSION_REACH_LIGHT):
+            raise ValueError("set_ghost_occlusion_reach: OCCLUSION_REACH_SKY (0) or OCCLUSION_REACH_LIGHT (1)")
+        self._ck(self.lib.lf_set_ghost_occlusion_reach(self.ctx, int(reach)))
+
+    def get_ghost_occlusion_reach(self):
+        reach = C.c_int(0)
+        self._ck(self.lib.lf_get_ghost_occlusion_reach(self.ctx, C.byref(reach)))
+        return reach.value
+
+    def ghost_ray_light_visibility(self, rays):
+        """rays: n x 6 (origin xyz in lens millimetres, direction xyz).  Returns n x n_lights bools: does ray i's shadow ray find
+        nothing over [0, reach_k] -- to the sky for a directional light, to the lamp for a point light (the mapping, reach and
+        any-hit walk of the march's shadow rays, on the state installed; whether or not the ray lies in lobe k)."""
+        r = np.asarray(rays)
+        if r.ndim != 2 or r.shape[1] != 6:
+            raise ValueError("ghost_ray_light_visibility: rays must be n x 6 (origin xyz in lens mm, direction xyz)")
+        r = np.ascontiguousarray(r, np.float32)
+        if not np.isfinite(r).all() or not (np.abs(r[:, 3:]).max(axis=1) > 0.0).all():
+            raise ValueError("ghost_ray_light_visibility: rays must be finite, directions non-zero")
+        n = C.c_int(0)
+        self._ck(self.lib.lf_get_lights(self.ctx, C.byref(n), None, None, None))
+        vis = np.zeros((len(r), max(1, n.value)), np.uint8)
+        self._ck(self.lib.lf_ghost_ray_light_visibility(self.ctx, C.c_size_t(len(r)), _fp(r, C.c_float),
+                                                        vis.ctypes.data_as(C.POINTER(C.c_ubyte))))
+        return vis[:, :n.value].astype(bool)
 
     def set_ghost_pairs(self, pairs=None, include_primary=True):
         if pairs is None or len(pairs) == 0:

@@ -266,6 +266,15 @@ lf_status lf_occlusion_ready(const lf_ctx* ctx, const char* who) {
   return lf_fail(ctx, LF_ERR_STATE, std::string(who) + ": ghost occlusion needs" + missing);
 }
 
+// occlusion is on: a point light among the installed ones needs shadow rays that end at it (lf_set_ghost_occlusion_reach)
+lf_status lf_occlusion_reach_ready(const lf_ctx* ctx, const char* who) {
+  if (!lf_has_point_light(ctx->lens) || ctx->ghost_occl_reach == LF_OCCLUSION_REACH_LIGHT) return LF_OK;
+  return lf_fail(ctx, LF_ERR_STATE, std::string(who) + ": ghost occlusion with a point light installed is not supported while the shadow rays "
+                                    "run to the sky (a point light's shadow ray ends at the light) -- "
+                                    "lf_set_ghost_occlusion_reach(LF_OCCLUSION_REACH_LIGHT) ends them there; or switch "
+                                    "lf_set_ghost_occlusion off, or install directional lights only");
+}
+
 lf_status lf_fill_occlusion(const lf_ctx* ctx, double world_per_mm, LfOcclDev* o) {
   std::memset(o, 0, sizeof(*o));
   // the camera position is the centre of the paraxial entrance pupil at the reference wavelength, as the lens camera
@@ -1552,6 +1561,70 @@ lf_status lf_ghost_ray_visibility(lf_ctx* ctx, size_t n, const float* rays, unsi
   if (e == hipSuccess) st = lfk_ghost_ray_visibility(ctx, o, n, d_rays, d_vis);
   if (e == hipSuccess && st == LF_OK) e = hipStreamSynchronize(ctx->stream);
   if (e == hipSuccess && st == LF_OK) e = hipMemcpy(visible, d_vis, n, hipMemcpyDeviceToHost);
+  if (d_rays) (void)hipFree(d_rays);
+  if (d_vis) (void)hipFree(d_vis);
+  if (st != LF_OK) return st;
+  LF_HIP(ctx, e);
+  return LF_OK;
+}
+
+// ---- where a point light's shadow ray ends ("the reach of a shadow ray") --------------------------
+lf_status lf_set_ghost_occlusion_reach(lf_ctx* ctx, int reach) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (reach != LF_OCCLUSION_REACH_SKY && reach != LF_OCCLUSION_REACH_LIGHT)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_ghost_occlusion_reach: LF_OCCLUSION_REACH_SKY (0) or LF_OCCLUSION_REACH_LIGHT (1)");
+  ctx->ghost_occl_reach = reach;
+  return LF_OK;
+}
+
+lf_status lf_get_ghost_occlusion_reach(lf_ctx* ctx, int* reach) {
+  if (!ctx || !reach) return LF_ERR_INVALID;
+  *reach = ctx->ghost_occl_reach;
+  return LF_OK;
+}
+
+// The reach of ONE exit ray's shadow ray for ONE light, host arithmetic: the definition the kernels call
+// (lf_march_events.h lf_point_shadow_reach), bit for bit
+lf_status lf_ghost_shadow_reach(int kind, const float vec[3], const float ray[6], double world_per_mm, double* reach) {
+  if (!vec || !ray || !reach || (kind != LF_LIGHT_DIRECTIONAL && kind != LF_LIGHT_POINT)) return LF_ERR_INVALID;
+  if (!(world_per_mm > 0.0) || !std::isfinite(world_per_mm)) return LF_ERR_INVALID;
+  for (int c = 0; c < 3; c++) if (!std::isfinite(vec[c])) return LF_ERR_INVALID;
+  for (int c = 0; c < 6; c++) if (!std::isfinite(ray[c])) return LF_ERR_INVALID;
+  *reach = kind == LF_LIGHT_POINT
+               ? lfm::lf_point_shadow_reach(ray[3], ray[4], ray[5], ray[0], ray[1], ray[2], vec[0], vec[1], vec[2], world_per_mm)
+               : (double)INFINITY;
+  return LF_OK;
+}
+
+lf_status lf_ghost_ray_light_visibility(lf_ctx* ctx, size_t n, const float* rays, unsigned char* visible) {
+  if (!ctx || (n > 0 && (!rays || !visible))) return LF_ERR_INVALID;
+  if (n > 0x7fffffffull / LF_MAX_LIGHTS) return lf_fail(ctx, LF_ERR_INVALID, "lf_ghost_ray_light_visibility: too many rays for one call");
+  if (!ctx->ghost_occlusion)
+    return lf_fail(ctx, LF_ERR_STATE, "lf_ghost_ray_light_visibility: ghost occlusion is off (lf_set_ghost_occlusion gives the mapping its scale)");
+  lf_status st = lf_occlusion_ready(ctx, "lf_ghost_ray_light_visibility");
+  if (st != LF_OK) return st;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_ghost_ray_light_visibility before lf_set_lens");
+  if (!ctx->sun_valid)
+    return lf_fail(ctx, LF_ERR_STATE, "lf_ghost_ray_light_visibility: no light installed (lf_set_sun / lf_set_lights / lf_set_lights_ex)");
+  st = lf_point_lights_fit(ctx, "lf_ghost_ray_light_visibility");
+  if (st != LF_OK) return st;
+  st = lf_occlusion_reach_ready(ctx, "lf_ghost_ray_light_visibility");
+  if (st != LF_OK) return st;
+  if (n == 0) return LF_OK;
+  LfOcclDev o;
+  st = lf_fill_occlusion(ctx, ctx->ghost_occl_wpm, &o);
+  if (st != LF_OK) return st;
+  LF_HIP(ctx, hipSetDevice(ctx->device));
+  const size_t nl = (size_t)ctx->lens.n_lights;
+  float* d_rays = nullptr;
+  unsigned char* d_vis = nullptr;
+  hipError_t e = hipMalloc((void**)&d_rays, n * 6 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_vis, n * nl);
+  if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * 6 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpyAsync(ctx->lens_dev, &ctx->lens, sizeof(LfLensDev), hipMemcpyHostToDevice, ctx->stream);
+  if (e == hipSuccess) st = lfk_ghost_ray_light_visibility(ctx, o, n, d_rays, d_vis);
+  if (e == hipSuccess && st == LF_OK) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && st == LF_OK) e = hipMemcpy(visible, d_vis, n * nl, hipMemcpyDeviceToHost);
   if (d_rays) (void)hipFree(d_rays);
   if (d_vis) (void)hipFree(d_vis);
   if (st != LF_OK) return st;

@@ -868,6 +868,12 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
                                                       case kVarNear | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarLights | kVarCoatFilt); break; \
                                                       case kVarNear | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarStack | kVarLights | kVarCoat); break; \
                                                       case kVarNear | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                                      case kVarNear | kVarOccl | kVarLights | kVarBare: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarOccl | kVarLights | kVarBare); break; \
+                                                      case kVarNear | kVarOccl | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarOccl | kVarLights | kVarCoat); break; \
+                                                      case kVarNear | kVarOccl | kVarLights | kVarFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarOccl | kVarLights | kVarFilt); break; \
+                                                      case kVarNear | kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarOccl | kVarLights | kVarCoatFilt); break; \
+                                                      case kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
+                                                      case kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
                                                   default: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_CULL2(KK, WW, SS, CC)                                                                       \
   hipLaunchKernelGGL((k_march_cull<KK, WW, SS, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
@@ -896,6 +902,12 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
                                               case kVarNear | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarLights | kVarCoatFilt); break; \
                                               case kVarNear | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarStack | kVarLights | kVarCoat); break; \
                                               case kVarNear | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                              case kVarNear | kVarOccl | kVarLights | kVarBare: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarOccl | kVarLights | kVarBare); break; \
+                                              case kVarNear | kVarOccl | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarOccl | kVarLights | kVarCoat); break; \
+                                              case kVarNear | kVarOccl | kVarLights | kVarFilt: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarOccl | kVarLights | kVarFilt); break; \
+                                              case kVarNear | kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarOccl | kVarLights | kVarCoatFilt); break; \
+                                              case kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
+                                              case kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
                                                   default: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_ITEMS2(KK, CC)                                                                             \
   hipLaunchKernelGGL((k_march_items<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \

@@ -522,6 +522,8 @@ struct lf_ctx {
   bool ghost_accumulate = false;                          // lf_set_ghost_accumulate
   bool ghost_occlusion = false;                           // lf_set_ghost_occlusion (a setting of the context: nothing clears it)
   double ghost_occl_wpm = 0.001;                          // ... its world units per lens millimetre
+  int ghost_occl_reach = LF_OCCLUSION_REACH_SKY;          // lf_set_ghost_occlusion_reach (a setting of the context too): where a point
+                                                          // light's shadow ray ends; SKY: occlusion with a point light is refused
   LfLensDev* lens_dev = nullptr;
   LfPairsDev pairs{};
   LfPairsDev* pairs_dev = nullptr;
@@ -668,6 +670,8 @@ inline void lf_install_split(lf_ctx* ctx, const LfSplit& s) {
 // the kernel variant of the weighted march (lf_march_events.h: kVarBare .. kVarCoatFilt, | kVarLights: several lights, | kVarStack,
 // | kVarOccl: ghost occlusion -- always with kVarLights, whose epilogue it extends: one light is a list of one)
 // | kVarNear: some installed light is a point light (lf_set_lights_ex) -- with kVarLights too, also when it is the only light
+// | kVarNear | kVarOccl together: launched only under LF_OCCLUSION_REACH_LIGHT (lf_set_ghost_occlusion_reach); under
+//   LF_OCCLUSION_REACH_SKY the launch's upload refuses the combination before any switch on the variant is reached
 inline int lf_march_variant(const lf_ctx* ctx) {
   const bool near = lf_has_point_light(ctx->lens);
   return (ctx->coat.n > 0 ? 1 : 0) | (ctx->mask_filter == LF_MASK_BILINEAR ? 2 : 0) |
@@ -720,6 +724,10 @@ lf_status lfk_lens_rays(lf_ctx* ctx, int lambda, int n, const float* d_xy, const
 lf_status lf_occlusion_ready(const lf_ctx* ctx, const char* who);
 lf_status lf_fill_occlusion(const lf_ctx* ctx, double world_per_mm, LfOcclDev* o);
 lf_status lfk_ghost_ray_visibility(lf_ctx* ctx, const LfOcclDev& o, size_t n, const float* d_rays, unsigned char* d_vis);
+// ... per installed light, over [0, reach_k] (d_vis: n x n_lights bytes; the lens as uploaded holds the lights), and the
+// refusal of occlusion with a point light installed unless the shadow rays end at the light (lf_set_ghost_occlusion_reach)
+lf_status lfk_ghost_ray_light_visibility(lf_ctx* ctx, const LfOcclDev& o, size_t n, const float* d_rays, unsigned char* d_vis);
+lf_status lf_occlusion_reach_ready(const lf_ctx* ctx, const char* who);
 // point lights (lf_set_lights_ex): the installed ones against the front element of the lens as it is now (`who` names the
 // caller in the refusal, LF_ERR_STATE); the batched per-ray lobe factors (d_rays: n x 6 floats, d_out: n x n_lights floats)
 lf_status lf_point_lights_fit(const lf_ctx* ctx, const char* who);

@@ -698,6 +698,24 @@ __global__ __launch_bounds__(256) void k_ghost_ray_visibility(LfOcclDev o, int n
   visible[i] = ghost_ray_visible(o, r[0], r[1], r[2], r[3], r[4], r[5]) ? 1 : 0;
 }
 
+// lf_ghost_ray_light_visibility: per exit ray and installed light k, does the shadow ray find nothing over [0, reach_k]?  The
+// kVarNear | kVarOccl epilogue's own mapping, reach (lf_point_shadow_reach; +inf for a directional light) and walk, one walk
+// per (ray, light): the per-light definition itself, which the epilogue's reuse by monotonicity has to reproduce.
+__global__ __launch_bounds__(256) void k_ghost_ray_light_visibility(const LfLensDev* __restrict__ lens, LfOcclDev o, int n,
+                                                                    const float* __restrict__ rays, unsigned char* __restrict__ visible) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rays + 6 * (size_t)i;
+  const int nl = lens->n_lights;
+  for (int k = 0; k < nl; k++) {
+    double reach = (double)INFINITY;
+    if (lens->light_kind[k] != LF_LIGHT_DIRECTIONAL)
+      reach = lf_point_shadow_reach(r[3], r[4], r[5], r[0], r[1], r[2], lens->light_pos[k][0], lens->light_pos[k][1], lens->light_pos[k][2],
+                                    o.wpm);
+    visible[(size_t)i * (size_t)nl + (size_t)k] = ghost_ray_visible(o, r[0], r[1], r[2], r[3], r[4], r[5], reach) ? 1 : 0;
+  }
+}
+
 // lf_ghost_ray_light_factors: per exit ray {origin xyz (z absolute), direction xyz} and installed light k, (1 - q_k)^2 where
 // the ray lies inside light k and 0 elsewhere -- the lit epilogue's own test and factor (light_admits_at), without a weight
 __global__ __launch_bounds__(256) void k_ghost_ray_light_factors(const LfLensDev* __restrict__ lens, int n, const float* __restrict__ rays,
@@ -1252,10 +1270,11 @@ static lf_status march_upload(lf_ctx* ctx, int spp, int total_paths = 0) {
     // lens whose front element has come too close to one is refused (lf_set_lights_ex's limits, lensflare.h)
     const lf_status st = lf_point_lights_fit(ctx, "lf_trace_ghosts");
     if (st != LF_OK) return st;
-    if (ctx->ghost_occlusion)
-      return lf_fail(ctx, LF_ERR_STATE, "lf_trace_ghosts: ghost occlusion with a point light installed is not supported (a point light's "
-                                        "shadow ray ends at the light: no kernel is built for it) -- switch lf_set_ghost_occlusion off, "
-                                        "or install directional lights only");
+    // ... and their shadow rays have to end at them (lf_set_ghost_occlusion_reach): under LF_OCCLUSION_REACH_SKY the launch is refused
+    if (ctx->ghost_occlusion) {
+      const lf_status reach = lf_occlusion_reach_ready(ctx, "lf_trace_ghosts");
+      if (reach != LF_OK) return reach;
+    }
   }
   if (ctx->events_dirty) {
     lf_status st = build_event_table(ctx);
@@ -1466,6 +1485,12 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
                                    case kVarNear | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarNear | kVarLights | kVarCoatFilt); break; \
                                    case kVarNear | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarNear | kVarStack | kVarLights | kVarCoat); break; \
                                    case kVarNear | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarNear | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                   case kVarNear | kVarOccl | kVarLights | kVarBare: LF_LAUNCH_MARCH2(KK, kVarNear | kVarOccl | kVarLights | kVarBare); break; \
+                                   case kVarNear | kVarOccl | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarNear | kVarOccl | kVarLights | kVarCoat); break; \
+                                   case kVarNear | kVarOccl | kVarLights | kVarFilt: LF_LAUNCH_MARCH2(KK, kVarNear | kVarOccl | kVarLights | kVarFilt); break; \
+                                   case kVarNear | kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarNear | kVarOccl | kVarLights | kVarCoatFilt); break; \
+                                   case kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
+                                   case kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
                                                   default: LF_LAUNCH_MARCH2(KK, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_MARCH2(KK, CC)                                                                   \
   hipLaunchKernelGGL((k_march<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
@@ -1564,6 +1589,15 @@ lf_status lfk_ghost_ray_visibility(lf_ctx* ctx, const LfOcclDev& o, size_t n, co
   if (n == 0) return LF_OK;
   hipLaunchKernelGGL(k_ghost_ray_visibility, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, o, (int)n, d_rays,
                      d_vis);
+  LF_HIP(ctx, hipGetLastError());
+  return LF_OK;
+}
+
+// (the caller has uploaded ctx->lens to lens_dev on the same stream; d_vis: n x n_lights bytes)
+lf_status lfk_ghost_ray_light_visibility(lf_ctx* ctx, const LfOcclDev& o, size_t n, const float* d_rays, unsigned char* d_vis) {
+  if (n == 0) return LF_OK;
+  hipLaunchKernelGGL(k_ghost_ray_light_visibility, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->lens_dev, o,
+                     (int)n, d_rays, d_vis);
   LF_HIP(ctx, hipGetLastError());
   return LF_OK;
 }

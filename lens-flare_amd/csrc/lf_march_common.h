@@ -53,7 +53,9 @@ __device__ __forceinline__ lanemask lobe_gate(const Ray (&r)[K], lanemask (&lit)
 // expressions in the same order, in double): oc = (px wpm, py wpm, (z - z_ref) wpm), origin = pos + c2w oc, direction =
 // c2w unit(d) -- in a lens-camera frame the ghost's shadow ray and the scene image agree.  The shadow ray runs from
 // min_t = 0 to max_t = +inf: the camera's clip planes belong to the image, not to what stands between the lens and a light.
-__device__ __forceinline__ lfw::DRay ghost_shadow_ray(const LfOcclDev& o, float px, float py, float z, float dx, float dy, float dz) {
+// (max_t: where the ray ends -- a point light's reach under LF_OCCLUSION_REACH_LIGHT, lf_point_shadow_reach; +inf everywhere else)
+__device__ __forceinline__ lfw::DRay ghost_shadow_ray(const LfOcclDev& o, float px, float py, float z, float dx, float dy, float dz,
+                                                      double max_t = (double)INFINITY) {
   using namespace lfw;
   const double wpm = o.wpm;
   const V3 oc = v3((double)px * wpm, (double)py * wpm, ((double)z - o.z_ref) * wpm);
@@ -65,12 +67,13 @@ __device__ __forceinline__ lfw::DRay ghost_shadow_ray(const LfOcclDev& o, float 
                   v3((dc.x * o.c2w[0] + dc.y * o.c2w[1]) + dc.z * o.c2w[2],
                      (dc.x * o.c2w[3] + dc.y * o.c2w[4]) + dc.z * o.c2w[5],
                      (dc.x * o.c2w[6] + dc.y * o.c2w[7]) + dc.z * o.c2w[8]),
-                  0.0, (double)INFINITY);
+                  0.0, max_t);
 }
 // ... and whether it sees the sky: the scene kernels' any-hit walk (lf_scene_walk.h closest_hit, h == nullptr) over the
 // resident tree, the stack of deferred children in the lane's own array
-__device__ inline bool ghost_ray_visible(const LfOcclDev& o, float px, float py, float z, float dx, float dy, float dz) {
-  lfw::DRay ray = ghost_shadow_ray(o, px, py, z, dx, dy, dz);
+__device__ inline bool ghost_ray_visible(const LfOcclDev& o, float px, float py, float z, float dx, float dy, float dz,
+                                         double max_t = (double)INFINITY) {
+  lfw::DRay ray = ghost_shadow_ray(o, px, py, z, dx, dy, dz, max_t);
   LfSceneDev sc{};
   sc.nodes = o.nodes; sc.prims = o.prims;
   int stack[lfw::kStackDepth];
@@ -165,6 +168,16 @@ __device__ __forceinline__ void lights_channel_factors(const LfLensDev* __restri
 // adds per epilogue that tested anything.  Only the lanes with something to add walk (a few per wave), each with its own
 // stack of deferred children (a lane's own array, kStackDepth ints of scratch): no LDS beside the kernel's own, so the
 // workgroups per CU stay what the kVarLights twin's LDS allows.
+//
+// VAR & kVarOccl & kVarNear (lf_set_ghost_occlusion_reach, LF_OCCLUSION_REACH_LIGHT with a point light installed): the shadow
+// ray of light k ends at reach_k -- +inf for a directional light, lf_point_shadow_reach for a point light -- so one walk no
+// longer answers for every light.  The same any-hit walk over [0, reach_k], and its answers reused by monotonicity: a
+// primitive's test forms its root without looking at max_t and accepts it iff it lies in [0, max_t] (lf_scene_walk.h
+// hit_sphere, hit_triangle), and the box test only ever drops what the double ray provably misses, so "something within
+// [0, T]" is exactly "some primitive's root <= T": nothing within [0, T] settles every shorter segment, something within
+// [0, T] every longer one.  A lane keeps the longest segment it found free and the shortest it found blocked, and walks
+// only for a reach between the two: the directional lights (all +inf) still share one walk, two lamps on the same side of
+// every occluder share one, and each answer is the per-light definition's, whatever the other lights are.
 template <int VAR = kVarLights>
 __device__ __forceinline__ void lights_epilogue(const LfLensDev* __restrict__ lens, const float* __restrict__ s_chan, const Ray& rw,
                                                 bool mine, int l, unsigned long long* __restrict__ acc, unsigned& n_light) {
@@ -173,6 +186,9 @@ __device__ __forceinline__ void lights_epilogue(const LfLensDev* __restrict__ le
   // kVarOccl: the launch's occlusion record behind the lens (wave-uniform: scalar loads), this lane's walk once made
   const LfOcclDev& occl = *(const LfOcclDev*)((const char*)lens + kLensOcclOffset);
   int vis = -1;                      // (1 = the ray sees the sky)
+  // ... | kVarNear: what this lane's walks have settled -- nothing stands within [0, seen_to], something within [0, dark_from]
+  double seen_to = -1.0, dark_from = 0.0;
+  bool dark_any = false;
   unsigned w_tested = 0u, w_blocked = 0u;   // ... the wave's tallies (wave-uniform)
   for (int k = 0; k < n; k++) {
     float qq;
@@ -180,7 +196,28 @@ __device__ __forceinline__ void lights_epilogue(const LfLensDev* __restrict__ le
     const float om = 1.0f - qq;
     float contrib = wq * (om * om);
     contrib = (mine && in && contrib > 0.0f) ? contrib : 0.0f;
-    if (VAR & kVarOccl) {
+    if ((VAR & kVarOccl) && (VAR & kVarNear)) {
+      const bool test = contrib > 0.0f;
+      // (the light's kind through the scalar cache, as in light_admits_at: a scalar branch around the lanes' reach)
+      const bool point = lens->light_kind[k] != LF_LIGHT_DIRECTIONAL;
+      if (test) {
+        const float z = occl.front_zv + rw.hz;
+        double reach = (double)INFINITY;
+        if (point)
+          reach = lf_point_shadow_reach(rw.dx, rw.dy, rw.dz, rw.px, rw.py, z, lens->light_pos[k][0], lens->light_pos[k][1],
+                                        lens->light_pos[k][2], occl.wpm);
+        bool v;
+        if (reach <= seen_to) v = true;
+        else if (dark_any && reach >= dark_from) v = false;
+        else {
+          v = ghost_ray_visible(occl, rw.px, rw.py, z, rw.dx, rw.dy, rw.dz, reach);
+          if (v) seen_to = reach; else { dark_from = reach; dark_any = true; }
+        }
+        if (!v) contrib = 0.0f;
+      }
+      w_tested += (unsigned)__popcll(__ballot(test));
+      w_blocked += (unsigned)__popcll(__ballot(test && contrib == 0.0f));
+    } else if (VAR & kVarOccl) {
       const bool test = contrib > 0.0f;
       if (test) {
         if (vis < 0)

@@ -365,6 +365,8 @@ enum : int { kVarBare = 0, kVarCoat = 1, kVarFilt = 2, kVarCoatFilt = 3,
                                 //   differs from its kVarLights twin in lights_epilogue alone (lf_march_common.h)
              kVarNear = 32 };   // | kVarNear (only with kVarLights): some light is a POINT light (lf_set_lights_ex): the pre-test, the gate
                                 //   and the lit epilogue form the direction to such a light per lane, from the ray's exit point
+                                // kVarNear | kVarOccl (launched only under lf_set_ghost_occlusion_reach(LF_OCCLUSION_REACH_LIGHT)): the shadow
+                                //   ray of a point light ends at the light (lf_point_shadow_reach below, lights_epilogue in lf_march_common.h)
 
 // ---- a light at a finite distance (lf_set_lights_ex, LF_LIGHT_POINT; DESIGN.md section 4, "point lights") -------------
 // The lobe factor of a ray that has left the front element at (px, py, z) (z absolute: front vertex z + hz) along d, for a
@@ -395,6 +397,21 @@ __host__ __device__ inline bool lf_point_pretest(float dx, float dy, float dz, f
   const float cg = fmaf(dx, sx, fmaf(dy, sy, dz * sz));
   const float dd = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
   return cg > 0.0f && cg * cg > ((thr * thr) * 0.999999f) * (dd * ss);
+}
+// How far the shadow ray of a POINT light reaches (lf_set_ghost_occlusion_reach, LF_OCCLUSION_REACH_LIGHT): the ray parameter, in
+// world units, of the point of the ray nearest the light -- s = L - P in double, dc = unit(d) exactly as the shadow ray's own
+// direction is formed (lf_march_common.h ghost_shadow_ray: multiply by 1 / norm), t = wpm (s . dc) with the scene's dot
+// product order, never below 0.  The camera's c2w is a rotation, so t is the parameter of the world ray as well.  Double
+// division and root are IEEE on both sides and nothing here contracts: the host (lf_ghost_shadow_reach) and the kernels,
+// which all call THIS definition, agree bit for bit.  A wall behind the lamp (t_hit > reach) does not hide it.
+__host__ __device__ inline double lf_point_shadow_reach(float dx, float dy, float dz, float px, float py, float z, float Lx, float Ly,
+                                                        float Lz, double wpm) {
+  const double sx = (double)Lx - px, sy = (double)Ly - py, sz = (double)Lz - z;
+  const double ax = (double)dx, ay = (double)dy, az = (double)dz;
+  const double rn = 1. / sqrt((ax * ax + ay * ay) + az * az);
+  const double cx = ax * rn, cy = ay * rn, cz = az * rn;
+  const double t = wpm * ((sx * cx + sy * cy) + sz * cz);
+  return t > 0.0 ? t : 0.0;
 }
 // The stop of a kernel instantiated for variant VAR.  Under the filter the geometry-only march (W = false) runs
 // the UNCHANGED nearest lookup on the support texture S (2 mw x 2 mh floats behind the texels, k_mask_support:

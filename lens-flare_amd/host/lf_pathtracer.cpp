@@ -216,6 +216,11 @@ void PathTracer::use_ghost_occlusion(bool on) {
   frame_ready_ = false;
 }
 
+void PathTracer::use_ghost_occlusion_reach(int reach) {
+  check(lf_set_ghost_occlusion_reach(ctx_, reach), "lf_set_ghost_occlusion_reach");
+  frame_ready_ = false;
+}
+
 void PathTracer::set_scene(int n_spheres, const double* spheres, const int* sphere_material,
                            int n_triangles, const double* tri_positions, const double* tri_normals,
                            const int* tri_material, int n_materials, const double* materials,

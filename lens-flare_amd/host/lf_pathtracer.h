@@ -133,13 +133,18 @@ class PathTracer {
   void use_lights_from_flares(float angular_radius);
   // ... or those AND every PointLight of the device scene (set_scene / load_collada), as point lights of the march at their
   // own distance: lf_set_lights_from_scene at every generate_ghost_buffer, through the camera's pose at the frame and
-  // lens_world_per_mm.  Opt-in: a mirror that never calls this renders what it rendered.  Not together with
-  // use_ghost_occlusion when the scene holds a PointLight in front of the lens (the launch is refused).
+  // lens_world_per_mm.  Opt-in: a mirror that never calls this renders what it rendered.  Together with
+  // use_ghost_occlusion, a scene with a PointLight in front of the lens needs use_ghost_occlusion_reach(
+  // LF_OCCLUSION_REACH_LIGHT) (below); without it the launch is refused.
   void use_lights_from_scene(float angular_radius);
   // after use_geometric_ghosts: the scene hides the march's ghosts (lf_set_ghost_occlusion, scale lens_world_per_mm): a lit
   // ghost ray adds only what no primitive between the front element and the sky blocks.  Needs a device scene (set_scene /
   // load_collada) and the camera at the frame.  Off by default: the frames are those of a mirror without this call.
   void use_ghost_occlusion(bool on);
+  // where the shadow ray of a point light ends (lf_occlusion_reach): LF_OCCLUSION_REACH_LIGHT lets a lamp of the scene be
+  // hidden by what stands between the lens and it, and by nothing behind it.  A setting of the context, installed at once
+  // (lf_set_ghost_occlusion_reach): it does not travel in the frame's plan.
+  void use_ghost_occlusion_reach(int reach);
   // replaces PathTracer::bvh / scene (pathtracer.h:116-124): hand the static scene to the device
   // so that the sample loop of raytrace_pixel (BVH closest hit + direct lighting) runs there too;
   // argument layout as lf_set_scene (include/lensflare.h)

@@ -221,8 +221,89 @@ static int geowall_main(int argc, char** argv) {
   return 0;
 }
 
+// shim_demo geolamp <lens.txt> <mask.f32> <mw> <mh> <W> <H> <spp> <lamp x y z> <angular radius> <outprefix>
+//                   <wall: 0 none, 1 between camera and lamp, 2 across half the beam, 3 behind the lamp>
+// A lamp in the room and a wall: the march's ghosts of a PointLight of the scene (use_lights_from_scene) under
+// use_ghost_occlusion + use_ghost_occlusion_reach(LF_OCCLUSION_REACH_LIGHT).  The lamp stands at <x y z> in world units
+// (identity pose at the origin, 1 scene unit = 1 m, z < 0); the wall is a quad square to the lamp's direction, its half
+// side 0.4 of its distance: half way to the lamp and centred on it (1), or shifted so that its edge crosses the lamp's
+// direction (2), or twice as far as the lamp (3).  Without a wall the scene holds one small sphere behind the camera and
+// occlusion stays off.  Dumps the ghost buffer and prints the shadow tests made / blocked.
+static int geolamp_main(int argc, char** argv) {
+  if (argc < 15) return 1;
+  std::ifstream in(argv[2]);
+  int n, stop, nl;
+  float sensor_w;
+  in >> n >> stop >> nl >> sensor_w;
+  std::vector<float> radius(n), thick(n), semi(n), ior((size_t)n * nl);
+  for (int k = 0; k < n; k++) {
+    in >> radius[k] >> thick[k] >> semi[k];
+    for (int l = 0; l < nl; l++) in >> ior[(size_t)l * n + k];
+  }
+  const size_t mw = atoi(argv[4]), mh = atoi(argv[5]), W = atoi(argv[6]), H = atoi(argv[7]);
+  const int spp = atoi(argv[8]);
+  const double lamp[3] = {atof(argv[9]), atof(argv[10]), atof(argv[11])};
+  const float alpha = (float)atof(argv[12]);
+  const std::string out = argv[13];
+  const int wall = atoi(argv[14]);
+  try {
+    PathTracer pt(0);
+    Camera cam;
+    CameraApertureTexture ap;
+    ap.init_from_texels(read_f32(argv[3], mw * mh).data(), mw, mh);
+    cam.aperture_texture = &ap;
+    cam.ghost_aperture_texture = &ap;
+    pt.clear();
+    pt.set_frame_size(W, H);
+    pt.camera = &cam;
+    pt.counter_jitter = true;
+    pt.axis_ray = Vector2D(0.5, 0.5);
+    const float ahead[3] = {0.0f, 0.0f, -1.0f};                      // (replaced by the scene's lamp at the frame)
+    pt.use_geometric_ghosts(n, stop, nl, radius.data(), thick.data(), ior.data(), semi.data(), sensor_w, ahead, alpha, spp);
+    // the lamp's direction s from the camera, two unit vectors u, v square to it
+    const double ll = std::sqrt(lamp[0] * lamp[0] + lamp[1] * lamp[1] + lamp[2] * lamp[2]);
+    const double s[3] = {lamp[0] / ll, lamp[1] / ll, lamp[2] / ll};
+    double u[3] = {-s[2], 0.0, s[0]};                                // (s x y: the lamp is never along y here, z < 0)
+    const double ul = std::sqrt(u[0] * u[0] + u[2] * u[2]);
+    u[0] /= ul; u[2] /= ul;
+    const double v[3] = {s[1] * u[2] - s[2] * u[1], s[2] * u[0] - s[0] * u[2], s[0] * u[1] - s[1] * u[0]};
+    const double light[7] = {1.0, lamp[0], lamp[1], lamp[2], 1.0, 0.9, 0.5};   // a PointLight
+    const double mats[4] = {0.0, 0.5, 0.5, 0.5};                     // diffuse grey
+    if (wall) {
+      const double dist = wall == 3 ? 2.0 * ll : 0.5 * ll, half = 0.4 * dist, shift = wall == 2 ? -half : 0.0;
+      double c[4][3];
+      const double cu[4] = {-half + shift, half + shift, half + shift, -half + shift}, cv[4] = {-half, -half, half, half};
+      for (int i = 0; i < 4; i++)
+        for (int a = 0; a < 3; a++) c[i][a] = dist * s[a] + cu[i] * u[a] + cv[i] * v[a];
+      double pos[18], nrm[18];
+      const int idx[6] = {0, 1, 2, 0, 2, 3};
+      for (int i = 0; i < 6; i++)
+        for (int a = 0; a < 3; a++) { pos[3 * i + a] = c[idx[i]][a]; nrm[3 * i + a] = -s[a]; }
+      const int tri_mat[2] = {0, 0};
+      pt.set_scene(0, nullptr, nullptr, 2, pos, nrm, tri_mat, 1, mats, 1, light);
+      pt.use_ghost_occlusion(true);
+      pt.use_ghost_occlusion_reach(LF_OCCLUSION_REACH_LIGHT);
+    } else {
+      const double sphere[4] = {0.0, 0.0, 10.0, 0.1};
+      const int sphere_mat[1] = {0};
+      pt.set_scene(1, sphere, sphere_mat, 0, nullptr, nullptr, nullptr, 1, mats, 1, light);
+    }
+    pt.use_lights_from_scene(alpha);
+    pt.generate_ghost_buffer();
+    dump(out + ".ghost.f64", &pt.ghost_buffer.data[0].x, W * H * 3);
+    uint64_t st[2] = {0, 0};
+    if (lf_get_ghost_occlusion_stats(pt.context(), st) != LF_OK) throw std::runtime_error(pt.last_error());
+    printf("shadow tests %llu blocked %llu\n", (unsigned long long)st[0], (unsigned long long)st[1]);
+  } catch (const std::exception& e) {
+    fprintf(stderr, "shim_demo geolamp: %s\n", e.what());
+    return 3;
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
   if (argc > 1 && std::string(argv[1]) == "geo") return geo_main(argc, argv);
+  if (argc > 1 && std::string(argv[1]) == "geolamp") return geolamp_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "geowall") return geowall_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "geolights") return geolights_main(argc, argv);
   if (argc < 5) return 1;
