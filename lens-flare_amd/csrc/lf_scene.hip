@@ -17,8 +17,10 @@
 // emitters (-H, pathtracer.cpp:86-138) -- draw from the order-free Philox counter RNG: the reference
 // draws them from its shared MT19937 only when a camera ray hits something, which makes every later
 // pixel's jitter depend on every earlier pixel's hits, so no device schedule can reproduce its stream.
-// They are therefore validated statistically against frames the reference rendered
-// (tests/test_gpu_area_lights.py, tests/test_gpu_env_light.py) and refused in MT19937 parity mode.
+// They are refused in MT19937 parity mode and validated twice: statistically against frames the reference
+// rendered (tests/test_gpu_area_lights.py, tests/test_gpu_env_light.py), and draw for draw against the float64
+// oracle, which consumes the counters below and is itself pinned to the reference's
+// stream (tests/test_gpu_sampled_lights.py: 1e-9 per probe and pixel).
 // Not covered (the call fails loudly rather than approximating): spot lights (a stub in the reference,
 // light.cpp:64-72).  The Mirror / Glass / Microfacet BSDFs are unfilled stubs in the reference
 // (advanced_bsdf.cpp: f() = 0): a host hands them over as black diffuse occluders.
@@ -94,6 +96,42 @@ __device__ inline int upper_bound_d(const double* __restrict__ a, int n, double 
   return lo;
 }
 
+// sinf / cosf as the reference's libm computes them.  UniformHemisphereSampler3D::get_sample (sampler.cpp:30-44) takes the
+// sine and cosine of its angles in FLOAT, and a float result that differs in its last bit moves a sample's radiance by
+// ~1e-7: the device's own sinf / cosf do differ from glibc's in a few per cent of their arguments.  glibc >= 2.28 computes
+// both in double and rounds once (the algorithm of Arm's Optimized Routines, math/sinf.c, cosf.c, sincosf.h: reduction by
+// pi/2 with a 2^24-scaled quadrant count, a degree-7 / degree-8 polynomial); restated here it gives glibc's float bit for
+// bit for every float in [2^-31, 2 pi] (checked exhaustively on the host), which covers theta = acos(xi) and phi = 2 pi xi
+// of draws clamped to [1e-7, 0.99999999].  Valid for |x| < 120 only.
+__device__ inline float ref_sincos_poly(double x, double x2, bool flip, int n) {
+  const double c0 = 0x1p0, c1 = -0x1.ffffffd0c621cp-2, c2 = 0x1.55553e1068f19p-5, c3 = -0x1.6c087e89a359dp-10,
+               c4 = 0x1.99343027bf8c3p-16, s1 = -0x1.555545995a603p-3, s2 = 0x1.1107605230bc4p-7,
+               s3 = -0x1.994eb3774cf24p-13;
+  if ((n & 1) == 0) {
+    const double x3 = x * x2, t1 = fma(x2, s3, s2), x7 = x3 * x2, sv = fma(x3, s1, x);
+    return (float)fma(x7, t1, sv);
+  }
+  const double sg = flip ? -1.0 : 1.0;   // (the second table: the cosine's coefficients negated)
+  const double x4 = x2 * x2, t2 = fma(x2, sg * c4, sg * c3), t1 = fma(x2, sg * c1, sg * c0), x6 = x4 * x2;
+  const double cv = fma(x4, sg * c2, t1);
+  return (float)fma(x6, t2, cv);
+}
+__device__ inline float ref_sincosf(float y, int want_cos) {
+  const unsigned top = (__float_as_uint(y) >> 20) & 0x7ffu;
+  double x = (double)y;
+  if (top < 0x3f4u) {              // |y| < pi/4 by the top 12 bits
+    if (top < 0x398u) return want_cos ? 1.0f : y;   // |y| < 2^-12
+    return ref_sincos_poly(x, x * x, false, want_cos);
+  }
+  const double r = x * 0x1.45F306DC9C883p+23;       // 2^24 * 2 / pi
+  const int n = ((int)r + 0x800000) >> 24;
+  x = fma(-(double)n, 0x1.921FB54442D18p0, x);
+  const double sgn = ((n & 3) == 1 || (n & 3) == 2) ? -1.0 : 1.0;
+  return ref_sincos_poly(x * sgn, x * x, (n & 2) != 0, n ^ want_cos);
+}
+__device__ inline float ref_sinf(float y) { return ref_sincosf(y, 0); }
+__device__ inline float ref_cosf(float y) { return ref_sincosf(y, 1); }
+
 // SOFT = false is the kernel of scenes with delta lights only (no sampled light, no environment, no
 // hemisphere sampling): the sampled-light code costs ~100 vector registers, i.e. one of the three
 // waves a SIMD otherwise holds (25 -> 35 ms on the 1080p timing frame), so it is compiled out there.
@@ -126,10 +164,10 @@ __device__ V3 shade_hit(const LfSceneDev& sc, const LfEnvDev& ev, bool hemispher
     for (int k = 0; k < num_samples; k++) {
       const uint4 rr = philox4x32_10(make_uint4(rng_ctr.x, rng_ctr.y, 0x11650000u, (unsigned)k), rng_key);
       const double xi1 = random_uniform_from_raw(rr.x), xi2 = random_uniform_from_raw(rr.y);
-      // UniformHemisphereSampler3D::get_sample (sampler.cpp:30-44): sinf / cosf of the double angles
+      // UniformHemisphereSampler3D::get_sample (sampler.cpp:30-44): sinf / cosf of the double angles (the reference's: ref_sinf)
       const double theta = acos(xi1), phi = 2.0 * 3.14159265358979323 * xi2;
-      const V3 wi = v3((double)(sinf((float)theta) * cosf((float)phi)),
-                       (double)(sinf((float)theta) * sinf((float)phi)), (double)cosf((float)theta));
+      const V3 wi = v3((double)(ref_sinf((float)theta) * ref_cosf((float)phi)),
+                       (double)(ref_sinf((float)theta) * ref_sinf((float)phi)), (double)ref_cosf((float)theta));
       // o2w * wi: the columns of o2w are X, Y, Z
       const V3 ww = v3((wi.x * X.x + wi.y * Y.x) + wi.z * Z.x, (wi.x * X.y + wi.y * Y.y) + wi.z * Z.y,
                        (wi.x * X.z + wi.y * Y.z) + wi.z * Z.z);
@@ -165,8 +203,11 @@ __device__ V3 shade_hit(const LfSceneDev& sc, const LfEnvDev& ev, bool hemispher
                                        rng_key);
         const double xi1 = random_uniform_from_raw(rr.x), xi2 = random_uniform_from_raw(rr.y);
         if (lt.type == 2) {  // InfiniteHemisphereLight::sample_L (light.cpp:35-48)
+          // its sampler is UniformHemisphereSampler3D (light.h:42; sampler.cpp:30-44): sinf / cosf of the angles
+          // as floats and float products, as in the -H estimator above
           const double theta = acos(xi1), phi = 2.0 * 3.14159265358979323 * xi2;
-          const double xs = sin(theta) * cos(phi), ys = sin(theta) * sin(phi), zs = cos(theta);
+          const double xs = (double)(ref_sinf((float)theta) * ref_cosf((float)phi)), ys = (double)(ref_sinf((float)theta) * ref_sinf((float)phi));
+          const double zs = (double)ref_cosf((float)theta);
           wi = v3(xs, zs, -ys);   // sampleToWorld: columns (1,0,0), (0,0,-1), (0,1,0)
           dist = INFINITY;
           pdf = 1.0 / (2.0 * 3.14159265358979323);

@@ -412,6 +412,17 @@ static uint32_t mt_next(mt_state* m) {
   y ^= (y >> 18);
   return y;
 }
+/* the same generator one draw at a time (lf_scene_oracle.c: the sampled lights consume a number of draws
+ * that depends on what each camera ray hits) */
+struct lfo_mt { mt_state m; };
+lfo_mt* lfo_mt_open(uint32_t seed, size_t skip) {
+  lfo_mt* g = (lfo_mt*)malloc(sizeof(lfo_mt));
+  mt_seed(&g->m, seed);
+  for (size_t i = 0; i < skip; i++) (void)mt_next(&g->m);
+  return g;
+}
+uint32_t lfo_mt_draw(lfo_mt* g) { return mt_next(&g->m); }
+void lfo_mt_close(lfo_mt* g) { free(g); }
 void lfo_mt19937_raw(uint32_t seed, size_t skip, size_t n, uint32_t* out) {
   mt_state m;
   mt_seed(&m, seed);
@@ -597,15 +608,24 @@ size_t lfo_tile_order(int W, int H, int tile, uint32_t* order) {
  * lfo_scene_term in lf_scene_oracle.c; NULL = nothing is hit */
 static const double* g_scene_term = NULL;
 void lfo_set_scene_term(const double* scene) { g_scene_term = scene; }
+/* optional stream positions, one per visit: how many draws the generator had handed out when the visit's 32
+ * falloff draws began (lfo_scene_frame reports them: with sampled lights the sample loop consumes a number
+ * of draws that depends on what its rays hit); NULL = the fixed stride 2*ns_aa + 32 */
+static const uint64_t* g_stream_pos = NULL;
+void lfo_set_stream_positions(const uint64_t* pos) { g_stream_pos = pos; }
 
 void lfo_render_pixels(const lfo_frame* f, const float* ap, const lfo_aperture_stats* st,
                        const double* ghost, const uint32_t* order, size_t n_order,
                        uint32_t mt_seed_, int n_threads, double* sample) {
   /* raytrace_pixel :819-899 with a zero scene term.  Draws per visited pixel: 2*ns_aa (pixel
    * jitter, consumed but irrelevant when nothing is hit) then 32 (falloff). */
-  size_t per = 2 * (size_t)f->ns_aa + 32;
-  uint32_t* raw = (uint32_t*)malloc(sizeof(uint32_t) * per * n_order);
-  lfo_mt19937_raw(mt_seed_, 0, per * n_order, raw);
+  size_t per = 2 * (size_t)f->ns_aa + 32, n_raw = per * n_order;
+  if (g_stream_pos) {
+    n_raw = 0;
+    for (size_t v = 0; v < n_order; v++) if (g_stream_pos[v] + 32 > n_raw) n_raw = (size_t)g_stream_pos[v] + 32;
+  }
+  uint32_t* raw = (uint32_t*)malloc(sizeof(uint32_t) * (n_raw ? n_raw : 1));
+  lfo_mt19937_raw(mt_seed_, 0, n_raw, raw);
   if (n_threads < 1) n_threads = 1;
 #pragma omp parallel for schedule(dynamic, 16) num_threads(n_threads)
   for (long long v = 0; v < (long long)n_order; v++) {
@@ -613,7 +633,8 @@ void lfo_render_pixels(const lfo_frame* f, const float* ap, const lfo_aperture_s
     size_t x = p % (size_t)f->W, y = p / (size_t)f->W;
     double sb[3], fo[3];
     lfo_starburst_pixel(f, ap, st, x, y, sb, NULL);
-    lfo_irradiance_falloff_pixel(f, x, y, 5.0, raw + per * (size_t)v + 2 * (size_t)f->ns_aa, fo);
+    lfo_irradiance_falloff_pixel(f, x, y, 5.0,
+                                 g_stream_pos ? raw + g_stream_pos[v] : raw + per * (size_t)v + 2 * (size_t)f->ns_aa, fo);
     double total[3] = {0, 0, 0};
     double rc = 1. / (double)(f->ns_aa + 1); /* :875 divides by the loop variable = ns_aa+1 */
     for (int c = 0; c < 3; c++) {

@@ -500,6 +500,122 @@ def set_scene_term(scene):
         lib().lfo_set_scene_term(_p(scene, C.c_double))
 
 
+def set_stream_positions(pos):
+    """Per visit, where in the MT19937 stream its 32 falloff draws begin (scene_frame's stream_pos); None =
+    the fixed stride 2 * ns_aa + 32.  Keep the array alive while in use."""
+    if pos is None:
+        lib().lfo_set_stream_positions(None)
+    else:
+        assert pos.dtype == np.uint64 and pos.flags.c_contiguous
+        lib().lfo_set_stream_positions(_p(pos, C.c_uint64))
+
+
+# ---- sampled lights (second half of lf_scene_oracle.c): area / hemisphere / environment lights and the -H
+# estimator, from the reference's MT19937 stream or from the device's Philox counters
+class SceneDesc(C.Structure):
+    _fields_ = [("n_spheres", C.c_int), ("spheres", C.POINTER(C.c_double)), ("sph_mat", C.POINTER(C.c_int)),
+                ("n_tris", C.c_int), ("tri_pos", C.POINTER(C.c_double)), ("tri_nrm", C.POINTER(C.c_double)),
+                ("tri_mat", C.POINTER(C.c_int)), ("materials", C.POINTER(C.c_double)),
+                ("n_lights", C.c_int), ("lights", C.POINTER(C.c_double)),
+                ("ns_area_light", C.c_int), ("hemisphere", C.c_int),
+                ("env_w", C.c_int), ("env_h", C.c_int), ("env", C.POINTER(C.c_double))]
+
+
+def scene_desc(spheres, tris, light_rows, ns_area_light=1, hemisphere=False, env=None):
+    """spheres / tris as LensFlare.set_scene takes them (kind 'd' diffuse, 'e' emission, 'm' one of the
+    reference's stub BSDFs: black); light_rows: n x 16 as lf_set_scene_lights; env: (h, w, 3) or None.
+    Returns the struct; the arrays it points into hang on it."""
+    mats, sp, spm, tp, tn, tm = [], [], [], [], [], []
+
+    def mat(kind, a, b, c):
+        mats.append([1.0, a, b, c] if kind == "e" else [0.0, 0.0, 0.0, 0.0] if kind == "m" else [0.0, a, b, c])
+        return len(mats) - 1
+
+    for s in spheres:
+        sp.append(list(s[:4])); spm.append(mat(*s[4:8]))
+    for t in tris:
+        tp.append(list(t[:9])); tn.append(list(t[9:18])); tm.append(mat(*t[18:22]))
+    f64 = lambda a: np.ascontiguousarray(np.array(a, np.float64).reshape(-1))  # noqa: E731
+    i32 = lambda a: np.ascontiguousarray(np.array(a, np.int32).reshape(-1))    # noqa: E731
+    keep = dict(sp=f64(sp), spm=i32(spm), tp=f64(tp), tn=f64(tn), tm=i32(tm), mats=f64(mats),
+                lights=np.ascontiguousarray(np.array(light_rows, np.float64).reshape(-1, 16)).reshape(-1))
+    d = SceneDesc()
+    d.n_spheres, d.spheres, d.sph_mat = len(sp), _p(keep["sp"], C.c_double), _p(keep["spm"], C.c_int)
+    d.n_tris, d.tri_pos, d.tri_nrm = len(tp), _p(keep["tp"], C.c_double), _p(keep["tn"], C.c_double)
+    d.tri_mat, d.materials = _p(keep["tm"], C.c_int), _p(keep["mats"], C.c_double)
+    d.n_lights, d.lights = len(keep["lights"]) // 16, _p(keep["lights"], C.c_double)
+    d.ns_area_light, d.hemisphere = int(ns_area_light), 1 if hemisphere else 0
+    if env is not None:
+        keep["env"] = np.ascontiguousarray(env, np.float64)
+        d.env_h, d.env_w, d.env = keep["env"].shape[0], keep["env"].shape[1], _p(keep["env"], C.c_double)
+    d._keep = keep
+    return d
+
+
+def scene_frame(desc, W, H, ns_aa, c2w, pos, hfov, vfov, order=None, key=None, seed=5489, skip=0,
+                samples_per_batch=32, max_tol=0.05, nclip=0.01, fclip=100.0):
+    """The sample loop over the pixels of `order` (default: every pixel, row-major).  key = None: the
+    reference's MT19937 stream (seed, skip draws discarded) in visit order -> (scene, stream_pos); key = k:
+    the device's counters -> (scene, flags, n_samples), flags bit 0 = fragile sample, bit 1 = early-out
+    closer than 1e-6."""
+    c2w = np.ascontiguousarray(np.array(c2w, np.float64).reshape(9))
+    pos = np.ascontiguousarray(np.array(pos, np.float64).reshape(3))
+    order = np.ascontiguousarray(np.arange(W * H) if order is None else order, np.uint32)
+    scene = np.zeros((H, W, 3), np.float64)
+    spos = np.zeros(len(order), np.uint64)
+    flags = np.zeros((H, W), np.uint8)
+    ns = np.zeros((H, W), np.int32)
+    lib().lfo_scene_frame(C.byref(desc), W, H, ns_aa, samples_per_batch, C.c_double(max_tol), _p(c2w, C.c_double),
+                          _p(pos, C.c_double), C.c_double(hfov), C.c_double(vfov), C.c_double(nclip),
+                          C.c_double(fclip), _p(order, C.c_uint32), C.c_size_t(len(order)),
+                          0 if key is None else 1, C.c_uint32(seed), C.c_size_t(skip),
+                          C.c_uint64(0 if key is None else key), _p(scene, C.c_double), _p(spos, C.c_uint64),
+                          _p(flags, C.c_uint8), _p(ns, C.c_int))
+    return (scene, spos) if key is None else (scene, flags, ns)
+
+
+def _ctr(ctr, n):
+    c = np.ascontiguousarray(ctr, np.uint32).reshape(-1, 2)
+    assert len(c) == n
+    return c
+
+
+def seq_counter(seq):
+    """(c.x, c.y) of the single-ray probes lf_scene_trace_ray / lf_scene_shade: seq low word, high word | 2^31."""
+    s = np.asarray(seq, np.uint64)
+    return np.stack([(s & np.uint64(0xffffffff)).astype(np.uint32),
+                     ((s >> np.uint64(32)).astype(np.uint32) | np.uint32(0x80000000))], -1)
+
+
+def scene_rays(desc, rays, ctr, key):
+    """est_radiance_global_illumination along explicit rays (n x 8: o, d, min_t, max_t) under the device's
+    counters (ctr: n x 2) -> (n x 8 {hit, t, n xyz, rgb}, fragile n)."""
+    rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 8)
+    c = _ctr(ctr, len(rays))
+    out = np.zeros((len(rays), 8), np.float64)
+    frag = np.zeros(len(rays), np.uint8)
+    lib().lfo_scene_rays(C.byref(desc), C.c_size_t(len(rays)), _p(rays, C.c_double), _p(c, C.c_uint32),
+                         C.c_uint64(key), _p(out, C.c_double), _p(frag, C.c_uint8))
+    return out, frag.astype(bool)
+
+
+def scene_shade(desc, what, rays, t, n, materials, ctr, key):
+    """lf_scene_shade for n intersections the caller found: what 0 .. 3; t: n; n: n x 3; materials: n x 4
+    {kind, rgb} -> (n x 3, fragile n)."""
+    rays = np.ascontiguousarray(rays, np.float64).reshape(-1, 8)
+    tn = np.ascontiguousarray(np.concatenate([np.asarray(t, np.float64).reshape(-1, 1),
+                                              np.asarray(n, np.float64).reshape(-1, 3)], 1))
+    mats = np.ascontiguousarray(materials, np.float64).reshape(-1, 4)
+    assert len(tn) == len(rays) == len(mats)
+    c = _ctr(ctr, len(rays))
+    out = np.zeros((len(rays), 3), np.float64)
+    frag = np.zeros(len(rays), np.uint8)
+    lib().lfo_scene_shade(C.byref(desc), int(what), C.c_size_t(len(rays)), _p(rays, C.c_double), _p(tn, C.c_double),
+                          _p(mats, C.c_double), _p(c, C.c_uint32), C.c_uint64(key), _p(out, C.c_double),
+                          _p(frag, C.c_uint8))
+    return out, frag.astype(bool)
+
+
 # ------------------------------------------------------------------------------------------------
 # independent float64 tracer (oracle/lf_geo_f64.c): the second opinion for the geometric march.
 # Shares no code / recipe / sqrt table with lf_geo_oracle.c; parity unpinned like it (no reference

@@ -162,6 +162,88 @@ def test_lens_frame_equals_the_float32_oracle(pkg, lf, sqrt_table):
     assert np.abs(pin - got).max() > 1e-3
 
 
+def sample_order(ns):
+    """march sample visited by sample number 1 .. ns of the lens camera's loop (lf_fill_lenscam_args: i -> i step mod ns)"""
+    step = max(1, int(math.floor(0.6180339887498949 * ns + 0.5)))
+    while math.gcd(step, ns) != 1:
+        step += 1
+    step = 1 if step % ns == 0 else step
+    return [((s - 1) * step) % ns for s in range(1, ns + 1)]
+
+
+@pytest.mark.parametrize("mode", [1, 2])
+def test_lens_frame_with_sampled_lights_equals_the_oracle_draw_for_draw(pkg, lf, sqrt_table, mode):
+    """The frame of test_lens_frame_equals_the_float32_oracle under an area light, an importance-sampled environment
+    map and the sun: the exit rays the float32 oracle gives for every sensor sample go to the float64 scene oracle
+    together with the counter the device draws that sample's light samples from -- (pixel, sample NUMBER of the loop,
+    not the march sample it visits), the same for every wavelength of the sample in mode 2.  Both kernels: the
+    compacted k_scene_lens<true> (the OWNER's counter travels with the queue entry) and the per-lane
+    k_scene_term<true, true>.  Bar and fragility rule: tests/test_gpu_sampled_lights.py."""
+    import sampled_lights_cases as slc
+    lens = pkg.load_lens_file("dgauss11.lens")
+    mask = load_texels("pentbig500_14.png")
+    W, H, ns, wpm = 48, 32, 9, 0.004
+    pos = [0.3, 0.2, 1.0]
+    c2w = look_at(pos, [0.0, -0.2, -5.5])
+    setup_scene_frame(pkg, lf, lens, mask, W, H, ns, c2w, pos)
+    sun = unit_lights(LIGHTS)[0]
+    rows = [[0.0] + sun[4:7] + sun[1:4] + [0.0] * 9,
+            [3.0, 6.0, 6.0, 5.0, 0.0, 2.5, -5.0, 0.0, -1.0, 0.0, 1.0, 0.0, 0.2, 0.0, 0.3, 1.0],
+            [4.0] + [0.0] * 15]
+    env = slc.env_map(15, 7, "smooth")
+    lf.set_environment_map(env)
+    lf.set_scene_lights(rows)
+    lf.set_light_samples(3)
+    lf.set_lens_camera(mode, wpm, 0.0)
+    frames = []
+    try:
+        for compact in (1, 0):
+            lf.test_knob("scene_compact", compact)
+            lf.set_scene_term(np.zeros((H, W, 3)))
+            lf.render_scene_term()
+            frames.append(lf.read_buffer(pkg.SCENE_BUFFER))
+    finally:
+        lf.test_knob("scene_compact", -1)
+    info = lf.lens_camera()
+    desc = lfo.scene_desc(SPHERES, TRIS, rows, 3, False, env)
+    order = sample_order(ns)
+    number = np.empty(ns, np.uint32)
+    number[order] = np.arange(1, ns + 1)            # march sample -> sample number
+    ctr = np.stack([np.repeat(np.arange(W * H, dtype=np.uint32), ns), np.tile(number, W * H)], -1)
+    lfo.geo_follow_device(sqrt_table)
+    try:
+        z_ref, _ = pkg.paraxial_entrance_pupil(lens)
+        want = np.zeros((H * W, 3))
+        fragile = np.zeros(H * W, bool)
+        for l in ((0, 1, 2) if mode == 2 else (1,)):
+            smp = lfo.geo_lens_samples(lens, W, H, ns, KEY, l, np.arange(W * H), mask)
+            o, d = lfo.lens_exit_to_world(smp[..., 0:3], smp[..., 3:6], c2w, pos, wpm, z_ref)
+            rays = np.concatenate([o, d, np.full(o.shape[:-1] + (1,), 0.01), np.full(o.shape[:-1] + (1,), 100.0)], -1)
+            alive = (smp[..., 6] > 0).reshape(-1)
+            L = np.zeros((H * W * ns, 3))
+            out, frag = lfo.scene_rays(desc, rays.reshape(-1, 8)[alive], ctr[alive], KEY)
+            L[alive] = out[:, 5:8]
+            fr = np.zeros(H * W * ns, bool)
+            fr[alive] = frag
+            fragile |= fr.reshape(H * W, ns).any(axis=1)
+            w = smp[..., 6].astype(np.float64).reshape(-1) * info["exposure"]
+            pix = (L * w[:, None]).reshape(H * W, ns, 3).sum(axis=1) / (ns + 1)
+            if mode == 2:
+                want[:, l] = pix[:, l]              # 3 wavelengths: the identity weights
+            else:
+                want = pix
+    finally:
+        lfo.geo_follow_device(None)
+    assert (want.max(axis=-1) > 0.02).mean() > 0.5 and fragile.sum() <= slc.PIXEL_CAP * W * H, fragile.sum()
+    for k, got in enumerate(frames):
+        err = np.abs(got.reshape(-1, 3) - want) / np.maximum(np.abs(want), 1e-300)
+        err[got.reshape(-1, 3) == want] = 0.0
+        worst = err[~fragile].max()
+        print(f"lens camera mode {mode} {'compacted' if k == 0 else 'per lane'}: {W * H} pixels, {int(fragile.sum())} "
+              f"fragile, largest deviation {worst:.3e}")
+        assert worst <= slc.TOL, (k, worst)
+
+
 def test_lens_frame_against_the_independent_float64_tracer(pkg, lf):
     """The same frame by the float64 textbook tracer (oracle/lf_geo_f64.c: no shared recipe, no sqrt
     table): every pixel within 1e-4 relative + the summed potential weight of its fragile samples."""
