@@ -701,6 +701,81 @@ lf_status lf_set_lights_from_flares(lf_ctx* ctx, double efl_mm, float angular_ra
  * installed; no light at all: LF_ERR_INVALID.  Needs lf_set_frame, lf_set_lens and lf_set_camera. */
 lf_status lf_set_lights_from_scene(lf_ctx* ctx, double efl_mm, float angular_radius, double world_per_mm, int* n_directional,
                                    int* n_point);
+/* AREA LIGHTS (rectangular emitters): the reference's AreaLight (scene/light.cpp:76-94), a one-sided rectangle -- the lamp of
+ * its Cornell-box scenes -- as a light of the march.  LF_LIGHT_AREA is the third lf_light_kind.  The three-float calls above
+ * (lf_set_lights_ex, lf_validate_light, lf_light_lobe_factor, lf_ghost_shadow_reach) keep refusing it: three floats cannot
+ * describe a rectangle.  The calls below take LF_LIGHT_GEOM_FLOATS = 12 floats per light:
+ *   kinds 0 and 1     floats 0..2 are the vec of lf_set_lights_ex, the rest are ignored and stored as 0;
+ *   LF_LIGHT_AREA     floats 0..2 the centre C, 3..5 the direction it emits towards, 6..8 dim_x (e1) and 9..11 dim_y (e2), both
+ *                     FULL edge vectors, all in lens millimetres (front vertex at z = 0, the scene at z < 0): the rectangle is
+ *                     C + u e1 + v e2, u, v in [-1/2, 1/2], as the reference samples it.  The direction is stored normalised
+ *                     (in double, then narrowed) and need not be the rectangle's normal (the reference does not ask for that
+ *                     either); angular_radius[k] is ignored and reported back as 0.
+ * lf_set_lights_geom replaces ALL lights; a refusal leaves the previous ones installed; lf_set_lights_ex IS lf_set_lights_geom
+ * with only the first three floats filled.  An area light must have all 12 floats and its radiance finite, the radiance
+ * >= 0, a direction that is not zero, |e1 x e2| >= 1e-6 |e1| |e2|, and each of its four corners C +- e1/2 +- e2/2 within the
+ * point light's limits, z <= -2 r_f and |corner| >= 4 r_f: otherwise LF_ERR_INVALID with a message that names the limit
+ * (before lf_set_lens: LF_ERR_STATE).  lf_set_lens keeps the installed lights; a front element that has come too close to an
+ * installed rectangle makes the launch refuse with LF_ERR_STATE, as for a point light.  lf_get_lights_ex reports an area
+ * light as kind 2 with vec = its centre, lf_get_lights the unit vector from the front vertex to the centre.
+ * The per-ray contract (float32, every multiply-add an explicit fmaf, dot products nested fmaf(x, x', fmaf(y, y', z z'))): a
+ * ray has left the front element at P = (px, py, front_zv + hz) along d;
+ *     s = P - C          p = d x e2          det = e1 . p          a = s . p
+ *     qv = s x e1        b = d . qv          tn = e2 . qv
+ *     inside iff det != 0 and 2 |a| <= |det| and 2 |b| <= |det| and tn sign(det) > 0 and d . dir < 0
+ *     contrib = wn / wd                      (factor 1: an area light has no lobe, radiance is constant along a ray)
+ * -- the ray-parallelogram test without a division or a root; d . dir < 0 is the reference's cosTheta < 0.  Everything else
+ * of the multi-light contract holds: one fixed-point value per (ray, light, channel), a frame of K lights of mixed kinds
+ * is the sum of the K single-light frames bit for bit, rays_hit_light counts (ray, light) contributions, and the range
+ * contract (lf_get_march_fix_bits) is unchanged, the factor being <= 1.  An in-focus ghost of a rectangle is a sharp quad.
+ * THE CULL TABLE takes an area light as the cone lf_area_light_cull_cone returns: dir = unit(C) from the front vertex and
+ * rho = max over the four corners of |unit(corner) - unit(C)| plus r_f / (dmin - r_f), dmin the distance from the front
+ * vertex to the nearest point of the rectangle, with the point light's slack.  The audit keeps the
+ * exact per-ray test.  A large or near rectangle fills the table and takes the path tree (LF_CULL_TABLE_TOO_FULL).
+ * KERNELS: a context with an area light -- also as its only light -- launches the kVarArea variants (*march_variant =
+ * 4 | 32 | 64 plus the coat, filter, stack and occlusion bits), which handle all three kinds; a context without one launches
+ * exactly what it launched before.
+ * OCCLUSION: under LF_OCCLUSION_REACH_SKY the launch refuses an area light as it refuses a point light.  Under
+ * LF_OCCLUSION_REACH_LIGHT the shadow ray of an area light ends just before the rectangle: the expressions above in double
+ * on the float-stored geometry and the ray, t = tn / det, reach = max(0, wpm t |d| - (double)0.00001f) -- the reference's
+ * EPS_F, as its shadow rays to sampled lights take it off (pathtracer.cpp:195): an emissive mesh lying in the light's
+ * plane, the Cornell lamp, does not shadow its own light.  Two limits: a mesh nearer the plane than EPS_F times the
+ * obliquity is the host's to keep clear; and with the lens camera on an emissive mesh is already imaged by the scene term,
+ * so such a host drops the primary path (lf_set_ghost_pairs include_primary = 0) or the lamp's direct image is added twice.
+ * COST, as measured (the bench frame, 1080p x 256 spp, table rebuilt and audited inside every frame; profiles/area_light_cost.json):
+ * the sun 35.01 ms, through the parent commit's library 34.92 (the kernels are the parent's); a 40 x 24 mm rectangle at 300 mm
+ * 56.02 ms against 46.20 for the point light (0.05 rad) at its centre (the table starts 11.4 % against 9.9 %); a 500 x 500 mm panel
+ * at 3 m 73.15 ms against 38.94 (11.3 % against 7.9 %; 1029 M against 306 M lit rays).  Under occlusion with
+ * LF_OCCLUSION_REACH_LIGHT behind a wall over half the beam: 314.9 ms against 256.7, and 422.4 against 205.3.  The library's build
+ * takes 7 min 05 s instead of 4 min 47 s (183 more kernels). */
+#define LF_LIGHT_AREA 2             /* lf_light_kind's third value, known to the twelve-float calls alone */
+#define LF_LIGHT_GEOM_FLOATS 12
+lf_status lf_set_lights_geom(lf_ctx* ctx, int n_lights, const int* kind, const float* geom, const float* radiance,
+                             const float* angular_radius);
+/* (any pointer may be NULL; arrays of LF_MAX_LIGHTS lights; a directional light's floats 0..2 are its direction as stored) */
+lf_status lf_get_lights_geom(lf_ctx* ctx, int* n_lights, int* kind, float* geom, float* radiance, float* angular_radius);
+/* Host arithmetic, no device: one light as lf_set_lights_geom validates it (lf_validate_light's arguments otherwise). */
+lf_status lf_validate_light_geom(int kind, const float* geom, const float radiance[3], float angular_radius, float front_radius,
+                                 float front_semi_aperture, char* message, size_t message_size);
+/* Host arithmetic, no device: ONE exit ray {origin xyz (z absolute), direction xyz} and ONE light.  *factor = what contrib is
+ * multiplied by, (1 - q)^2 or, for an area light, 1, where the ray contributes and 0 elsewhere; *inside; *t = for an area
+ * light the ray parameter of its plane, tn / det in double (P + t d; +inf for the other kinds).  Any of the three may be
+ * NULL.  An area light's is the definition the kernels call, bit for bit. */
+lf_status lf_light_geom_factor(int kind, const float* geom, float angular_radius, const float ray[6], float* factor, int* inside,
+                               double* t);
+/* ... and the pre-test that selects lanes for an area light's exact test, any superset of it: the rectangle's bounding
+ * sphere seen from the exit point (host arithmetic, the kernels' own definition) */
+lf_status lf_area_light_pretest(const float* geom, const float ray[6], int* admitted);
+/* Host arithmetic, no device: lf_ghost_shadow_reach for the twelve-float kinds (kinds 0 and 1: the same values). */
+lf_status lf_ghost_shadow_reach_geom(int kind, const float* geom, const float ray[6], double world_per_mm, double* reach);
+/* Host arithmetic, no device: what the cull table takes an area light as, for a front element of the given radius (0:
+ * flat) and semi-aperture.  A rectangle lf_validate_light_geom refuses: LF_ERR_INVALID. */
+lf_status lf_area_light_cull_cone(const float* geom, float front_radius, float front_semi_aperture, float dir[3], float* rho);
+/* lf_set_lights_from_scene plus every AreaLight of the installed scene lights (type 3): position as a point light's, direction
+ * as c2w^T v, dim_x and dim_y as c2w^T v / world_per_mm, in double, then narrowed; its rgb is the radiance.  A rectangle that
+ * fails validation is skipped and not counted; more than LF_MAX_LIGHTS in all: LF_ERR_INVALID, nothing is installed. */
+lf_status lf_set_lights_from_scene_ex(lf_ctx* ctx, double efl_mm, float angular_radius, double world_per_mm, int* n_directional,
+                                      int* n_point, int* n_area);
 /* Paraxial effective focal length of a prescription at one wavelength (host arithmetic, no
  * device): the system matrix from the reference's own T / R operators (pathtracer.cpp:527-533);
  * ior_row = the n indices of that wavelength (media BEHIND each interface).  Arguments as
@@ -834,6 +909,7 @@ lf_status lf_get_cull_audit(lf_ctx* ctx, uint64_t* rays, uint64_t* lit, int* lau
  *                               table wrong by construction; the march and the audit still see light k (the audit's test)
  *   "cull_no_widening" 0/1      1: a point light (lf_set_lights_ex) enters the cull table with a directional light's radius, not
  *                               widened by r_f / (|L| - r_f) -- a table wrong by construction for a light close to the lens
+ *                               (an area light, lf_set_lights_geom: with its corners' reach alone, not widened by r_f / (dmin - r_f))
  *   "cull_cache" 0/1            0: no cached tree -- every pre-pass marches its boxes (the tree a context holds is kept), same table
  *   "cull_cache_max_mb" MiB     the cached tree's byte budget (default 8192)
  *   "cull_general_kernel" 0/1   build the table with the kernel that takes its rules as arguments (must give the shipped one's table)

@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "lf_set_lights", "lf_get_lights", "lf_set_lights_from_flares",
     "lf_set_lights_ex", "lf_get_lights_ex", "lf_validate_light", "lf_light_lobe_factor", "lf_ghost_ray_light_factors",
     "lf_set_lights_from_scene",
+    "lf_set_lights_geom", "lf_get_lights_geom", "lf_validate_light_geom", "lf_light_geom_factor", "lf_area_light_pretest",
+    "lf_ghost_shadow_reach_geom", "lf_area_light_cull_cone", "lf_set_lights_from_scene_ex",
     "lf_set_ghost_occlusion", "lf_get_ghost_occlusion", "lf_get_ghost_occlusion_stats", "lf_ghost_ray_visibility",
     "lf_set_ghost_occlusion_reach", "lf_get_ghost_occlusion_reach", "lf_ghost_shadow_reach", "lf_ghost_ray_light_visibility",
     "lf_set_sun_from_flares", "lf_paraxial_efl", "lf_paraxial_image_scale", "lf_set_ghost_pairs", "lf_set_pupil_subcells", "lf_set_tile_stride", "lf_trace_ghosts", "lf_set_march_culling", "lf_get_cull_info", "lf_get_cull_table", "lf_get_cull_started_fraction", "lf_get_cull_reason", "lf_set_cull_audit", "lf_get_cull_audit", "lf_test_knob", "lf_comm_share_cull", "lf_set_cull_share", "lf_cull_prepare", "lf_cull_table_view", "lf_cull_commit", "lf_get_march_fix_bits", "lf_generate_lens_rays", "lf_get_counters", "lf_reset_counters", "lf_get_executed_events", "lf_get_march_stats", "lf_native_sqrt", "lf_native_rcp", "lf_set_starburst_spectrum", "lf_load_collada", "lf_march_tables",
@@ -343,6 +345,86 @@ def ghost_shadow_reach(kind, vec, rays, world_per_mm):
             raise LensFlareError(st, "lf_ghost_shadow_reach")
         out[i] = t.value
     return out
+
+
+# the third kind, known to the twelve-float calls alone (lf_set_lights_geom): a one-sided rectangle -- centre, direction,
+# dim_x, dim_y (full edge vectors) in lens millimetres
+LIGHT_AREA, LIGHT_GEOM_FLOATS = 2, 12
+
+
+def _geom(geom):
+    g = np.ascontiguousarray(geom, np.float32).reshape(-1)
+    if len(g) == 3:
+        g = np.concatenate([g, np.zeros(9, np.float32)])
+    if len(g) != LIGHT_GEOM_FLOATS:
+        raise ValueError("a light's geometry is 12 floats (kinds 0 and 1: the first 3 count)")
+    return np.ascontiguousarray(g, np.float32)
+
+
+def validate_light_geom(kind, geom, radiance, angular_radius, front_radius, front_semi_aperture):
+    """(status, message) of one light as lf_set_lights_geom validates it (lf_validate_light_geom, host only)"""
+    g = _geom(geom)
+    r = np.ascontiguousarray(radiance, np.float32).reshape(3)
+    msg = C.create_string_buffer(512)
+    st = load_library().lf_validate_light_geom(int(kind), _fp(g, C.c_float), _fp(r, C.c_float), C.c_float(angular_radius),
+                                               C.c_float(front_radius), C.c_float(front_semi_aperture), msg, C.c_size_t(512))
+    return int(st), msg.value.decode()
+
+
+def light_geom_factors(kind, geom, angular_radius, rays):
+    """n x 6 exit rays, one light -> (factor float32, inside bool, t float64) (lf_light_geom_factor, host only: an area light's
+    is the definition the kernels call; t = the ray parameter of its plane)"""
+    g = _geom(geom)
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    fs, ins, ts = np.zeros(len(r), np.float32), np.zeros(len(r), bool), np.zeros(len(r), np.float64)
+    f, inside, t = C.c_float(), C.c_int(), C.c_double()
+    fn, gp, ar, base = load_library().lf_light_geom_factor, _fp(g, C.c_float), C.c_float(angular_radius), r.ctypes.data
+    for i in range(len(r)):
+        st = fn(int(kind), gp, ar, C.cast(base + 24 * i, C.POINTER(C.c_float)), C.byref(f), C.byref(inside), C.byref(t))
+        if st != 0:
+            raise LensFlareError(st, "lf_light_geom_factor")
+        fs[i], ins[i], ts[i] = f.value, bool(inside.value), t.value
+    return fs, ins, ts
+
+
+def area_light_pretest(geom, rays):
+    """does the pre-test of an area light admit each of n x 6 exit rays (lf_area_light_pretest, host only) -> bool array"""
+    g = _geom(geom)
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    out, a = np.zeros(len(r), bool), C.c_int()
+    fn, gp, base = load_library().lf_area_light_pretest, _fp(g, C.c_float), r.ctypes.data
+    for i in range(len(r)):
+        st = fn(gp, C.cast(base + 24 * i, C.POINTER(C.c_float)), C.byref(a))
+        if st != 0:
+            raise LensFlareError(st, "lf_area_light_pretest")
+        out[i] = bool(a.value)
+    return out
+
+
+def ghost_shadow_reach_geom(kind, geom, rays, world_per_mm):
+    """reach of n x 6 exit rays for one light of any kind, float64 array (lf_ghost_shadow_reach_geom, host only): an area
+    light's shadow ray ends EPS_F before its rectangle's plane"""
+    g = _geom(geom)
+    r = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    out, t = np.zeros(len(r), np.float64), C.c_double()
+    fn, gp, base = load_library().lf_ghost_shadow_reach_geom, _fp(g, C.c_float), r.ctypes.data
+    for i in range(len(r)):
+        st = fn(int(kind), gp, C.cast(base + 24 * i, C.POINTER(C.c_float)), C.c_double(float(world_per_mm)), C.byref(t))
+        if st != 0:
+            raise LensFlareError(st, "lf_ghost_shadow_reach_geom")
+        out[i] = t.value
+    return out
+
+
+def area_light_cull_cone(geom, front_radius, front_semi_aperture):
+    """(dir float32 x 3, rho) the cull table takes an area light as (lf_area_light_cull_cone, host only)"""
+    g = _geom(geom)
+    d, rho = np.zeros(3, np.float32), C.c_float()
+    st = load_library().lf_area_light_cull_cone(_fp(g, C.c_float), C.c_float(front_radius), C.c_float(front_semi_aperture),
+                                                _fp(d, C.c_float), C.byref(rho))
+    if st != 0:
+        raise LensFlareError(st, "lf_area_light_cull_cone")
+    return d, float(rho.value)
 
 
 # how the march and the lens camera read the stop mask (lf_set_mask_filter)
@@ -922,6 +1004,38 @@ class LensFlare:
         self._ck(self.lib.lf_set_lights_from_scene(self.ctx, C.c_double(efl_mm), C.c_float(angular_radius),
                                                    C.c_double(world_per_mm), C.byref(nd), C.byref(npt)))
         return nd.value, npt.value
+
+    # ---- area lights (lf_set_lights_geom)
+    def set_lights_geom(self, kinds, geoms, radiances, angular_radii):
+        """Lights of all three kinds (lf_set_lights_geom): 12 floats per light -- kinds 0 and 1 the vector of set_lights_ex in
+        the first three, LIGHT_AREA centre, direction, dim_x, dim_y in lens millimetres.  Replaces all lights."""
+        k = np.ascontiguousarray(kinds, np.int32).reshape(-1)
+        g = np.ascontiguousarray([_geom(x) for x in geoms], np.float32).reshape(-1, LIGHT_GEOM_FLOATS)
+        r = np.ascontiguousarray(radiances, np.float32).reshape(-1, 3)
+        a = np.ascontiguousarray(angular_radii, np.float32).reshape(-1)
+        if not (len(k) == len(g) == len(r) == len(a)):
+            raise ValueError("set_lights_geom: one kind, one geometry, one radiance and one angular radius per light")
+        self._ck(self.lib.lf_set_lights_geom(self.ctx, len(k), _fp(k, C.c_int), _fp(g, C.c_float), _fp(r, C.c_float),
+                                             _fp(a, C.c_float)))
+
+    def lights_geom(self):
+        """(kinds n, geometry n x 12 as stored, radiances n x 3, angular radii n) (lf_get_lights_geom)"""
+        n = C.c_int(0)
+        k = np.zeros(MAX_LIGHTS, np.int32)
+        g = np.zeros((MAX_LIGHTS, LIGHT_GEOM_FLOATS), np.float32)
+        r = np.zeros((MAX_LIGHTS, 3), np.float32)
+        a = np.zeros(MAX_LIGHTS, np.float32)
+        self._ck(self.lib.lf_get_lights_geom(self.ctx, C.byref(n), _fp(k, C.c_int), _fp(g, C.c_float), _fp(r, C.c_float),
+                                             _fp(a, C.c_float)))
+        return k[:n.value].copy(), g[:n.value].copy(), r[:n.value].copy(), a[:n.value].copy()
+
+    def set_lights_from_scene_ex(self, efl_mm=0.0, angular_radius=0.05, world_per_mm=0.001):
+        """set_lights_from_scene plus the scene's AreaLights (lf_set_lights_from_scene_ex); returns (directional, point,
+        area) lights installed"""
+        nd, npt, na = C.c_int(0), C.c_int(0), C.c_int(0)
+        self._ck(self.lib.lf_set_lights_from_scene_ex(self.ctx, C.c_double(efl_mm), C.c_float(angular_radius),
+                                                      C.c_double(world_per_mm), C.byref(nd), C.byref(npt), C.byref(na)))
+        return nd.value, npt.value, na.value
 
     def ghost_ray_light_factors(self, rays):
         """rays: n x 6 (origin xyz in lens millimetres, z absolute; direction xyz).  Returns n x n_lights float32: (1 - q_k)^2

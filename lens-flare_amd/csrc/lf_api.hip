@@ -327,12 +327,117 @@ static lf_status validate_light(int kind, const float* v, const float* rad, floa
   return LF_OK;
 }
 
-// the installed point lights against the front element of the lens as it is now (a launch's precondition: lf_march.hip)
+// One light as lf_set_lights_geom validates it (lf_validate_light_geom is this, exported): g = LF_LIGHT_GEOM_FLOATS floats.
+// Kinds 0 and 1 are lf_set_lights_ex's, on the first three floats; an area light: everything finite, a direction, a
+// rectangle that is not degenerate, each of its four corners within the point light's limits.
+static lf_status validate_light_geom(int kind, const float* g, const float* rad, float ar, bool have_front, float front_radius,
+                                     float front_semi_aperture, std::string* why) {
+  if (kind == LF_LIGHT_DIRECTIONAL || kind == LF_LIGHT_POINT)
+    return validate_light(kind, g, rad, ar, have_front, front_radius, front_semi_aperture, why);
+  if (kind != LF_LIGHT_AREA) {
+    *why = "light: kind must be LF_LIGHT_DIRECTIONAL (0), LF_LIGHT_POINT (1) or LF_LIGHT_AREA (2)";
+    return LF_ERR_INVALID;
+  }
+  for (int c = 0; c < LF_LIGHT_GEOM_FLOATS; c++)
+    if (!std::isfinite(g[c])) { *why = "area light: radiance must be finite and >= 0, the geometry (centre, direction, dim_x, dim_y) finite"; return LF_ERR_INVALID; }
+  for (int c = 0; c < 3; c++)
+    if (!std::isfinite(rad[c]) || rad[c] < 0.0f) { *why = "area light: radiance must be finite and >= 0, the geometry (centre, direction, dim_x, dim_y) finite"; return LF_ERR_INVALID; }
+  const double C[3] = {g[0], g[1], g[2]}, d[3] = {g[3], g[4], g[5]}, e1[3] = {g[6], g[7], g[8]}, e2[3] = {g[9], g[10], g[11]};
+  if (!(d[0] * d[0] + d[1] * d[1] + d[2] * d[2] > 0.0)) { *why = "area light: the direction must not be zero"; return LF_ERR_INVALID; }
+  const double cx = e1[1] * e2[2] - e1[2] * e2[1], cy = e1[2] * e2[0] - e1[0] * e2[2], cz = e1[0] * e2[1] - e1[1] * e2[0];
+  const double n1 = std::sqrt(e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2]), n2 = std::sqrt(e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2]);
+  if (!(n1 > 0.0) || !(n2 > 0.0) || !(std::sqrt(cx * cx + cy * cy + cz * cz) >= 1e-6 * n1 * n2)) {
+    *why = "area light: degenerate rectangle -- |dim_x x dim_y| must be >= 1e-6 |dim_x| |dim_y|";
+    return LF_ERR_INVALID;
+  }
+  if (!have_front) { *why = "area light: its distance limits are the front element's -- lf_set_lens comes first"; return LF_ERR_STATE; }
+  const double r_f = lf_front_reach(front_radius, front_semi_aperture);
+  for (int i = 0; i < 4; i++) {
+    const double su = (i & 1) ? 0.5 : -0.5, sv = (i & 2) ? 0.5 : -0.5;
+    const double p[3] = {C[0] + su * e1[0] + sv * e2[0], C[1] + su * e1[1] + sv * e2[1], C[2] + su * e1[2] + sv * e2[2]};
+    const double dist = std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+    if (!(p[2] <= -2.0 * r_f) || !(dist >= 4.0 * r_f)) {
+      char buf[320];
+      std::snprintf(buf, sizeof(buf), "area light too close to the front element: corner (%g, %g, %g) mm needs z <= -2 r_f = %g and "
+                    "|corner| >= 4 r_f = %g (r_f = %g mm, the front element's reach from its vertex)", p[0], p[1], p[2], -2.0 * r_f, 4.0 * r_f, r_f);
+      *why = buf;
+      return LF_ERR_INVALID;
+    }
+  }
+  return LF_OK;
+}
+
+// the squared radius of an area light's bounding sphere, as its pre-test takes it (lf_area_pretest): the longer half
+// diagonal's square, in double, 1e-6 larger and never rounded down
+static float area_bound2(const float* e1, const float* e2) {
+  double p = 0.0, m = 0.0;
+  for (int c = 0; c < 3; c++) {
+    const double a = (double)e1[c] + (double)e2[c], b = (double)e1[c] - (double)e2[c];
+    p += a * a; m += b * b;
+  }
+  const double rb2 = 0.25 * std::max(p, m) * (1.0 + 1e-6);
+  float f = (float)rb2;
+  if ((double)f < rb2) f = std::nextafterf(f, INFINITY);
+  return f;
+}
+
+void lf_area_cull_cone(const float* C, const float* g, double r_f, bool widen, float dir[3], float* rho) {
+  const double c[3] = {C[0], C[1], C[2]}, e1[3] = {g[3], g[4], g[5]}, e2[3] = {g[6], g[7], g[8]};
+  const double nc = std::sqrt(c[0] * c[0] + c[1] * c[1] + c[2] * c[2]);
+  const double u[3] = {c[0] / nc, c[1] / nc, c[2] / nc};
+  for (int k = 0; k < 3; k++) dir[k] = (float)u[k];
+  double chord = 0.0;
+  for (int i = 0; i < 4; i++) {
+    const double su = (i & 1) ? 0.5 : -0.5, sv = (i & 2) ? 0.5 : -0.5;
+    const double p[3] = {c[0] + su * e1[0] + sv * e2[0], c[1] + su * e1[1] + sv * e2[1], c[2] + su * e1[2] + sv * e2[2]};
+    const double np_ = std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+    const double dot = (p[0] * u[0] + p[1] * u[1] + p[2] * u[2]) / np_;
+    // (a corner at 90 degrees or more from unit(C): the section is no longer convex -- every direction)
+    if (!(dot > 0.0)) { chord = 2.0; break; }
+    const double dx = p[0] / np_ - u[0], dy = p[1] / np_ - u[1], dz = p[2] / np_ - u[2];
+    chord = std::max(chord, std::sqrt(dx * dx + dy * dy + dz * dz));
+  }
+  if (!widen) { *rho = (float)chord; return; }
+  // dmin: the nearest point of C + s e1 + t e2, s, t in [-1/2, 1/2], to the origin -- the interior minimum if it lies
+  // inside, else the least of the four edges' (each a clamped projection)
+  const double a11 = e1[0] * e1[0] + e1[1] * e1[1] + e1[2] * e1[2], a22 = e2[0] * e2[0] + e2[1] * e2[1] + e2[2] * e2[2];
+  const double a12 = e1[0] * e2[0] + e1[1] * e2[1] + e1[2] * e2[2];
+  const double b1 = -(c[0] * e1[0] + c[1] * e1[1] + c[2] * e1[2]), b2 = -(c[0] * e2[0] + c[1] * e2[1] + c[2] * e2[2]);
+  auto dist_at = [&](double s, double t) {
+    const double p[3] = {c[0] + s * e1[0] + t * e2[0], c[1] + s * e1[1] + t * e2[1], c[2] + s * e1[2] + t * e2[2]};
+    return std::sqrt(p[0] * p[0] + p[1] * p[1] + p[2] * p[2]);
+  };
+  auto clamp = [](double x) { return x < -0.5 ? -0.5 : x > 0.5 ? 0.5 : x; };
+  double dmin = INFINITY;
+  const double den = a11 * a22 - a12 * a12;
+  if (den > 0.0) {
+    const double s = (b1 * a22 - b2 * a12) / den, t = (b2 * a11 - b1 * a12) / den;
+    if (std::fabs(s) <= 0.5 && std::fabs(t) <= 0.5) dmin = dist_at(s, t);
+  }
+  if (!std::isfinite(dmin)) {
+    for (int i = 0; i < 2; i++) {
+      const double f = i ? 0.5 : -0.5;
+      dmin = std::min(dmin, dist_at(clamp((b1 - f * a12) / a11), f));   // t = f: minimise over s
+      dmin = std::min(dmin, dist_at(f, clamp((b2 - f * a12) / a22)));   // s = f: minimise over t
+    }
+  }
+  *rho = (float)chord + lf_cull_near_widening(r_f, dmin);
+}
+
+// the installed point and area lights against the front element of the lens as it is now (a launch's precondition: lf_march.hip)
 lf_status lf_point_lights_fit(const lf_ctx* ctx, const char* who) {
   const LfLensDev& L = ctx->lens;
   for (int k = 0; k < L.n_lights; k++) {
     if (L.light_kind[k] == LF_LIGHT_DIRECTIONAL) continue;
     std::string why;
+    if (L.light_kind[k] == LF_LIGHT_AREA) {
+      float g[LF_LIGHT_GEOM_FLOATS];
+      for (int c = 0; c < 3; c++) g[c] = L.light_pos[k][c];
+      for (int c = 0; c < 9; c++) g[3 + c] = L.light_area[k][c];
+      if (validate_light_geom(LF_LIGHT_AREA, g, L.light_radiance[k], 0.0f, ctx->lens_valid, ctx->raw_radius[0], ctx->raw_semi_ap[0], &why) != LF_OK)
+        return lf_fail(ctx, LF_ERR_STATE, std::string(who) + ": light " + std::to_string(k) + " no longer fits the lens installed since -- " + why);
+      continue;
+    }
     if (validate_light(LF_LIGHT_POINT, L.light_pos[k], L.light_radiance[k], ctx->light_radius[k], ctx->lens_valid, ctx->raw_radius[0],
                        ctx->raw_semi_ap[0], &why) != LF_OK)
       return lf_fail(ctx, LF_ERR_STATE, std::string(who) + ": light " + std::to_string(k) + " no longer fits the lens installed since -- " + why);
@@ -935,36 +1040,53 @@ lf_status lf_validate_light(int kind, const float vec[3], const float radiance[3
   return st;
 }
 
+// (stride: floats per light in vec -- 3: the three-float calls, which know kinds 0 and 1 alone; LF_LIGHT_GEOM_FLOATS: lf_set_lights_geom)
 static lf_status set_lights(lf_ctx* ctx, const char* who, int n_lights, const int* kind, const float* vec, const float* radiance,
-                            const float* angular_radius) {
+                            const float* angular_radius, int stride = 3) {
   if (n_lights < 1 || n_lights > LF_MAX_LIGHTS)
     return lf_fail(ctx, LF_ERR_INVALID, std::string(who) + ": 1 .. LF_MAX_LIGHTS (" + std::to_string(LF_MAX_LIGHTS) + ") lights per launch");
   // every light is validated before any is installed: a refusal leaves the previous lights in place
   LfLensDev L = ctx->lens;
+  float radius[LF_MAX_LIGHTS];
   for (int k = 0; k < n_lights; k++) {
-    const float* d = vec + 3 * k;
+    const float* d = vec + stride * k;
     const float* rad = radiance + 3 * k;
     const float ar = angular_radius[k];
     const int kd = kind ? kind[k] : LF_LIGHT_DIRECTIONAL;
     std::string why;
-    const lf_status st = validate_light(kd, d, rad, ar, ctx->lens_valid, ctx->raw_radius[0], ctx->raw_semi_ap[0], &why);
+    const lf_status st = stride == 3 ? validate_light(kd, d, rad, ar, ctx->lens_valid, ctx->raw_radius[0], ctx->raw_semi_ap[0], &why)
+                                     : validate_light_geom(kd, d, rad, ar, ctx->lens_valid, ctx->raw_radius[0], ctx->raw_semi_ap[0], &why);
     if (st != LF_OK) return lf_fail(ctx, st, why);
     // a point light's direction: from the front vertex (z = 0 in the prescription's coordinates) to its position
+    // (an area light's: to its centre)
     const double n = std::sqrt((double)d[0] * d[0] + (double)d[1] * d[1] + (double)d[2] * d[2]);
     for (int c = 0; c < 3; c++) {
       L.light_dir[k][c] = (float)(d[c] / n);
       L.light_radiance[k][c] = rad[c];
-      L.light_pos[k][c] = kd == LF_LIGHT_POINT ? d[c] : 0.0f;
+      L.light_pos[k][c] = kd != LF_LIGHT_DIRECTIONAL ? d[c] : 0.0f;
     }
     L.light_kind[k] = kd;
+    radius[k] = ar;
     L.light_inv_one_minus_cos[k] = (float)(1.0 / (1.0 - std::cos((double)ar)));
     L.light_ss[k] = (float)((double)L.light_dir[k][0] * L.light_dir[k][0] +
                             (double)L.light_dir[k][1] * L.light_dir[k][1] +
                             (double)L.light_dir[k][2] * L.light_dir[k][2]);
     L.light_thr[k] = lf_march_lobe_thr_of(L.light_inv_one_minus_cos[k]);
+    for (int c = 0; c < 9; c++) L.light_area[k][c] = 0.0f;
+    if (kd == LF_LIGHT_AREA) {
+      // the direction normalised in double, then narrowed; the edges as given; no lobe: the angular radius is ignored (0), the
+      // lobe's scalars hold a quarter sphere's (finite, read by no kernel), light_thr the bounding sphere's squared radius
+      const double nd = std::sqrt((double)d[3] * d[3] + (double)d[4] * d[4] + (double)d[5] * d[5]);
+      for (int c = 0; c < 3; c++) L.light_area[k][c] = (float)((double)d[3 + c] / nd);
+      for (int c = 3; c < 9; c++) L.light_area[k][c] = d[3 + c];
+      radius[k] = 0.0f;
+      L.light_inv_one_minus_cos[k] = 1.0f;
+      L.light_thr[k] = area_bound2(d + 6, d + 9);
+    }
   }
   for (int k = n_lights; k < LF_MAX_LIGHTS; k++) {
     for (int c = 0; c < 3; c++) L.light_dir[k][c] = L.light_radiance[k][c] = L.light_pos[k][c] = 0.0f;
+    for (int c = 0; c < 9; c++) L.light_area[k][c] = 0.0f;
     L.light_inv_one_minus_cos[k] = L.light_ss[k] = L.light_thr[k] = 0.0f;
     L.light_kind[k] = LF_LIGHT_DIRECTIONAL;
   }
@@ -974,7 +1096,7 @@ static lf_status set_lights(lf_ctx* ctx, const char* who, int n_lights, const in
   L.sun_inv_one_minus_cos = L.light_inv_one_minus_cos[0];
   L.sun_ss = L.light_ss[0];
   ctx->lens = L;
-  for (int k = 0; k < LF_MAX_LIGHTS; k++) ctx->light_radius[k] = k < n_lights ? angular_radius[k] : 0.0f;
+  for (int k = 0; k < LF_MAX_LIGHTS; k++) ctx->light_radius[k] = k < n_lights ? radius[k] : 0.0f;
   ctx->sun_valid = true;
   return LF_OK;
 }
@@ -1024,6 +1146,111 @@ lf_status lf_get_lights(lf_ctx* ctx, int* n_lights, float* dir, float* radiance,
     }
     if (angular_radius) angular_radius[k] = ctx->light_radius[k];
   }
+  return LF_OK;
+}
+
+// ---- the twelve-float family (lf_set_lights_geom: area lights; DESIGN.md section 4, "area lights") ---------------------
+lf_status lf_set_lights_geom(lf_ctx* ctx, int n_lights, const int* kind, const float* geom, const float* radiance,
+                             const float* angular_radius) {
+  if (!ctx || !kind || !geom || !radiance || !angular_radius) return LF_ERR_INVALID;
+  return set_lights(ctx, "lf_set_lights_geom", n_lights, kind, geom, radiance, angular_radius, LF_LIGHT_GEOM_FLOATS);
+}
+
+lf_status lf_get_lights_geom(lf_ctx* ctx, int* n_lights, int* kind, float* geom, float* radiance, float* angular_radius) {
+  if (!ctx) return LF_ERR_INVALID;
+  const LfLensDev& L = ctx->lens;
+  const int n = ctx->sun_valid ? L.n_lights : 0;
+  if (n_lights) *n_lights = n;
+  for (int k = 0; k < n; k++) {
+    if (kind) kind[k] = L.light_kind[k];
+    if (geom) {
+      float* g = geom + LF_LIGHT_GEOM_FLOATS * k;
+      for (int c = 0; c < 3; c++) g[c] = L.light_kind[k] != LF_LIGHT_DIRECTIONAL ? L.light_pos[k][c] : L.light_dir[k][c];
+      for (int c = 0; c < 9; c++) g[3 + c] = L.light_area[k][c];
+    }
+    for (int c = 0; c < 3; c++) if (radiance) radiance[3 * k + c] = L.light_radiance[k][c];
+    if (angular_radius) angular_radius[k] = ctx->light_radius[k];
+  }
+  return LF_OK;
+}
+
+lf_status lf_validate_light_geom(int kind, const float* geom, const float radiance[3], float angular_radius, float front_radius,
+                                 float front_semi_aperture, char* message, size_t message_size) {
+  if (message && message_size) message[0] = 0;
+  if (!geom || !radiance) return LF_ERR_INVALID;
+  if (!(front_semi_aperture > 0.0f) || !std::isfinite(front_semi_aperture) || !std::isfinite(front_radius)) return LF_ERR_INVALID;
+  std::string why;
+  const lf_status st = validate_light_geom(kind, geom, radiance, angular_radius, true, front_radius, front_semi_aperture, &why);
+  if (message && message_size) std::snprintf(message, message_size, "%s", why.c_str());
+  return st;
+}
+
+// an area light's geometry as lf_set_lights_geom stores it: the centre, then direction (normalised in double, narrowed),
+// dim_x, dim_y -- what the kernels' definitions take; false: not finite, or no direction
+static bool stored_area(const float* geom, float C[3], float g[9]) {
+  for (int c = 0; c < LF_LIGHT_GEOM_FLOATS; c++) if (!std::isfinite(geom[c])) return false;
+  const double nd = std::sqrt((double)geom[3] * geom[3] + (double)geom[4] * geom[4] + (double)geom[5] * geom[5]);
+  if (!(nd > 0.0)) return false;
+  for (int c = 0; c < 3; c++) { C[c] = geom[c]; g[c] = (float)((double)geom[3 + c] / nd); }
+  for (int c = 3; c < 9; c++) g[c] = geom[3 + c];
+  return true;
+}
+
+lf_status lf_light_geom_factor(int kind, const float* geom, float angular_radius, const float ray[6], float* factor, int* inside,
+                               double* t) {
+  if (!geom || !ray) return LF_ERR_INVALID;
+  if (kind == LF_LIGHT_DIRECTIONAL || kind == LF_LIGHT_POINT) {
+    float q = 0.0f;
+    int in = 0;
+    const lf_status st = lf_light_lobe_factor(kind, geom, angular_radius, ray, &q, &in);
+    if (st != LF_OK) return st;
+    const float om = 1.0f - q;
+    if (factor) *factor = in ? om * om : 0.0f;
+    if (inside) *inside = in;
+    if (t) *t = (double)INFINITY;
+    return LF_OK;
+  }
+  if (kind != LF_LIGHT_AREA) return LF_ERR_INVALID;
+  float C[3], g[9];
+  if (!stored_area(geom, C, g)) return LF_ERR_INVALID;
+  for (int c = 0; c < 6; c++) if (!std::isfinite(ray[c])) return LF_ERR_INVALID;
+  const bool in = lfm::lf_area_inside(ray[3], ray[4], ray[5], ray[0], ray[1], ray[2], C, g);
+  if (factor) *factor = in ? 1.0f : 0.0f;
+  if (inside) *inside = in ? 1 : 0;
+  if (t) (void)lfm::lf_area_shadow_reach(ray[3], ray[4], ray[5], ray[0], ray[1], ray[2], C, g, 1.0, t);
+  return LF_OK;
+}
+
+lf_status lf_area_light_pretest(const float* geom, const float ray[6], int* admitted) {
+  if (!geom || !ray || !admitted) return LF_ERR_INVALID;
+  float C[3], g[9];
+  if (!stored_area(geom, C, g)) return LF_ERR_INVALID;
+  for (int c = 0; c < 6; c++) if (!std::isfinite(ray[c])) return LF_ERR_INVALID;
+  *admitted = lfm::lf_area_pretest(ray[3], ray[4], ray[5], ray[0], ray[1], ray[2], C, area_bound2(g + 3, g + 6)) ? 1 : 0;
+  return LF_OK;
+}
+
+lf_status lf_ghost_shadow_reach_geom(int kind, const float* geom, const float ray[6], double world_per_mm, double* reach) {
+  if (!geom || !ray || !reach) return LF_ERR_INVALID;
+  if (kind == LF_LIGHT_DIRECTIONAL || kind == LF_LIGHT_POINT) return lf_ghost_shadow_reach(kind, geom, ray, world_per_mm, reach);
+  if (kind != LF_LIGHT_AREA) return LF_ERR_INVALID;
+  if (!(world_per_mm > 0.0) || !std::isfinite(world_per_mm)) return LF_ERR_INVALID;
+  float C[3], g[9];
+  if (!stored_area(geom, C, g)) return LF_ERR_INVALID;
+  for (int c = 0; c < 6; c++) if (!std::isfinite(ray[c])) return LF_ERR_INVALID;
+  *reach = lfm::lf_area_shadow_reach(ray[3], ray[4], ray[5], ray[0], ray[1], ray[2], C, g, world_per_mm);
+  return LF_OK;
+}
+
+lf_status lf_area_light_cull_cone(const float* geom, float front_radius, float front_semi_aperture, float dir[3], float* rho) {
+  if (!geom || !dir || !rho) return LF_ERR_INVALID;
+  if (!(front_semi_aperture > 0.0f) || !std::isfinite(front_semi_aperture) || !std::isfinite(front_radius)) return LF_ERR_INVALID;
+  const float rad[3] = {0.0f, 0.0f, 0.0f};
+  std::string why;
+  if (validate_light_geom(LF_LIGHT_AREA, geom, rad, 0.0f, true, front_radius, front_semi_aperture, &why) != LF_OK) return LF_ERR_INVALID;
+  float C[3], g[9];
+  if (!stored_area(geom, C, g)) return LF_ERR_INVALID;
+  lf_area_cull_cone(C, g, lf_front_reach(front_radius, front_semi_aperture), true, dir, rho);
   return LF_OK;
 }
 
@@ -1208,29 +1435,33 @@ lf_status lf_set_lights_from_flares(lf_ctx* ctx, double efl_mm, float angular_ra
 // the INVERSE of the lens camera's mapping, in double: p_lens = c2w^T (p_world - pos) / wpm + (0, 0, z_ref), z_ref the
 // paraxial entrance pupil's z (lf_fill_occlusion's, lf_get_lens_camera's).  A point light the front element's limits
 // refuse (behind the camera, or closer than lf_set_lights_ex allows) is skipped and not counted.
-lf_status lf_set_lights_from_scene(lf_ctx* ctx, double efl_mm, float angular_radius, double world_per_mm, int* n_directional,
-                                   int* n_point) {
+// (areas: lf_set_lights_from_scene_ex -- every AreaLight too, type 3: position as a point, direction as c2w^T v, dim_x and dim_y
+// as c2w^T v / wpm, in double, then narrowed; a rectangle lf_set_lights_geom's validation refuses is skipped and not counted)
+static lf_status set_lights_from_scene(lf_ctx* ctx, const std::string& who, bool areas, double efl_mm, float angular_radius,
+                                       double world_per_mm, int* n_directional, int* n_point, int* n_area) {
   if (!ctx) return LF_ERR_INVALID;
   if (n_directional) *n_directional = 0;
   if (n_point) *n_point = 0;
-  if (ctx->W == 0) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lights_from_scene before lf_set_frame");
-  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lights_from_scene before lf_set_lens");
-  if (!ctx->cam_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lights_from_scene before lf_set_camera");
+  if (n_area) *n_area = 0;
+  if (ctx->W == 0) return lf_fail(ctx, LF_ERR_STATE, who + " before lf_set_frame");
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, who + " before lf_set_lens");
+  if (!ctx->cam_valid) return lf_fail(ctx, LF_ERR_STATE, who + " before lf_set_camera");
   if (!(world_per_mm > 0.0) || !std::isfinite(world_per_mm))
-    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lights_from_scene: world_per_mm must be > 0 and finite");
+    return lf_fail(ctx, LF_ERR_INVALID, who + ": world_per_mm must be > 0 and finite");
   LF_HIP(ctx, hipSetDevice(ctx->device));
   LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
   int kind[LF_MAX_LIGHTS];
-  float vec[3 * LF_MAX_LIGHTS], rad[3 * LF_MAX_LIGHTS], ar[LF_MAX_LIGHTS];
-  int n = 0, n_dir = 0, n_pt = 0;
-  const std::string too_many = "lf_set_lights_from_scene: more lights than one launch marches (LF_MAX_LIGHTS = " + std::to_string(LF_MAX_LIGHTS) +
+  float vec[LF_LIGHT_GEOM_FLOATS * LF_MAX_LIGHTS] = {}, rad[3 * LF_MAX_LIGHTS], ar[LF_MAX_LIGHTS];
+  constexpr int GF = LF_LIGHT_GEOM_FLOATS;
+  int n = 0, n_dir = 0, n_pt = 0, n_ar = 0;
+  const std::string too_many = who + ": more lights than one launch marches (LF_MAX_LIGHTS = " + std::to_string(LF_MAX_LIGHTS) +
                                "; compose launches with lf_set_ghost_accumulate)";
   if (ctx->flares_valid) {
     LfFlares f;
     LF_HIP(ctx, hipMemcpy(&f, ctx->flares, sizeof(f), hipMemcpyDeviceToHost));
     if (f.n_flares > LF_MAX_LIGHTS || f.n_in_frame > LF_MAX_LIGHTS) return lf_fail(ctx, LF_ERR_INVALID, too_many);
     for (int k = 0; k < f.n_flares; k++) {
-      const lf_status st = light_of_flare(ctx, "lf_set_lights_from_scene", f, k, &efl_mm, vec + 3 * n, rad + 3 * n);
+      const lf_status st = light_of_flare(ctx, who.c_str(), f, k, &efl_mm, vec + GF * n, rad + 3 * n);
       if (st != LF_OK) return st;
       kind[n] = LF_LIGHT_DIRECTIONAL; ar[n] = angular_radius;
       n++; n_dir++;
@@ -1243,10 +1474,32 @@ lf_status lf_set_lights_from_scene(lf_ctx* ctx, double efl_mm, float angular_rad
     if (ctx->raw_stop >= 0 &&
         lf_paraxial_entrance_pupil(ctx->raw_n, ctx->raw_stop, ctx->raw_radius, ctx->raw_thickness,
                                    ctx->raw_ior + (size_t)(ctx->lens.n_lambda / 2) * ctx->raw_n, &z_ref, &mag) != LF_OK)
-      return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lights_from_scene: the stop has no finite paraxial image through the front group");
+      return lf_fail(ctx, LF_ERR_INVALID, who + ": the stop has no finite paraxial image through the front group");
     const double r_f = lf_front_reach(ctx->raw_radius[0], ctx->raw_semi_ap[0]);
     const double* M = ctx->cam.c2w;
     for (const LfLight& l : lts) {
+      if (l.type == 3 && areas) {
+        // the rectangle in lens millimetres: a point, a direction and two edges through the inverse mapping
+        const double w[3] = {l.v[0] - ctx->cam.pos[0], l.v[1] - ctx->cam.pos[1], l.v[2] - ctx->cam.pos[2]};
+        float g[GF];
+        g[0] = (float)(((M[0] * w[0] + M[3] * w[1]) + M[6] * w[2]) / world_per_mm);
+        g[1] = (float)(((M[1] * w[0] + M[4] * w[1]) + M[7] * w[2]) / world_per_mm);
+        g[2] = (float)(((M[2] * w[0] + M[5] * w[1]) + M[8] * w[2]) / world_per_mm + z_ref);
+        const double* const vs[3] = {l.dir, l.dim_x, l.dim_y};
+        for (int i = 0; i < 3; i++) {
+          const double sc = i == 0 ? 1.0 : world_per_mm;
+          for (int c = 0; c < 3; c++) g[3 + 3 * i + c] = (float)(((M[c] * vs[i][0] + M[3 + c] * vs[i][1]) + M[6 + c] * vs[i][2]) / sc);
+        }
+        const float rgb[3] = {(float)l.rgb[0], (float)l.rgb[1], (float)l.rgb[2]};
+        std::string why;
+        if (validate_light_geom(LF_LIGHT_AREA, g, rgb, 0.0f, true, ctx->raw_radius[0], ctx->raw_semi_ap[0], &why) != LF_OK) continue;
+        if (n >= LF_MAX_LIGHTS) return lf_fail(ctx, LF_ERR_INVALID, too_many);
+        for (int c = 0; c < GF; c++) vec[GF * n + c] = g[c];
+        for (int c = 0; c < 3; c++) rad[3 * n + c] = rgb[c];
+        kind[n] = LF_LIGHT_AREA; ar[n] = 0.0f;
+        n++; n_ar++;
+        continue;
+      }
       if (l.type != 1) continue;
       const double w[3] = {l.v[0] - ctx->cam.pos[0], l.v[1] - ctx->cam.pos[1], l.v[2] - ctx->cam.pos[2]};
       const float p[3] = {(float)(((M[0] * w[0] + M[3] * w[1]) + M[6] * w[2]) / world_per_mm),
@@ -1255,17 +1508,29 @@ lf_status lf_set_lights_from_scene(lf_ctx* ctx, double efl_mm, float angular_rad
       const double dist = std::sqrt((double)p[0] * p[0] + (double)p[1] * p[1] + (double)p[2] * p[2]);
       if (!std::isfinite(dist) || !((double)p[2] <= -2.0 * r_f) || !(dist >= 4.0 * r_f)) continue;   // (behind the limit: skipped)
       if (n >= LF_MAX_LIGHTS) return lf_fail(ctx, LF_ERR_INVALID, too_many);
-      for (int c = 0; c < 3; c++) { vec[3 * n + c] = p[c]; rad[3 * n + c] = (float)l.rgb[c]; }
+      for (int c = 0; c < 3; c++) { vec[GF * n + c] = p[c]; rad[3 * n + c] = (float)l.rgb[c]; }
       kind[n] = LF_LIGHT_POINT; ar[n] = angular_radius;
       n++; n_pt++;
     }
   }
-  if (n < 1) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lights_from_scene: no flare in the frame and no point light in front of the lens");
-  const lf_status st = set_lights(ctx, "lf_set_lights_from_scene", n, kind, vec, rad, ar);
+  if (n < 1) return lf_fail(ctx, LF_ERR_INVALID, who + (areas ? ": no flare in the frame and no point or area light in front of the lens"
+                                                                : ": no flare in the frame and no point light in front of the lens"));
+  const lf_status st = set_lights(ctx, who.c_str(), n, kind, vec, rad, ar, GF);
   if (st != LF_OK) return st;
   if (n_directional) *n_directional = n_dir;
   if (n_point) *n_point = n_pt;
+  if (n_area) *n_area = n_ar;
   return LF_OK;
+}
+
+lf_status lf_set_lights_from_scene(lf_ctx* ctx, double efl_mm, float angular_radius, double world_per_mm, int* n_directional,
+                                   int* n_point) {
+  return set_lights_from_scene(ctx, "lf_set_lights_from_scene", false, efl_mm, angular_radius, world_per_mm, n_directional, n_point, nullptr);
+}
+
+lf_status lf_set_lights_from_scene_ex(lf_ctx* ctx, double efl_mm, float angular_radius, double world_per_mm, int* n_directional,
+                                      int* n_point, int* n_area) {
+  return set_lights_from_scene(ctx, "lf_set_lights_from_scene_ex", true, efl_mm, angular_radius, world_per_mm, n_directional, n_point, n_area);
 }
 
 lf_status lf_set_ghost_pairs(lf_ctx* ctx, const int* pairs, int n_pairs, int include_primary) {

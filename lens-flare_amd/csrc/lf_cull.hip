@@ -874,6 +874,18 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
                                                       case kVarNear | kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarOccl | kVarLights | kVarCoatFilt); break; \
                                                       case kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
                                                       case kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                                      case kVarArea | kVarNear | kVarLights | kVarBare: LF_LAUNCH_CULL2(KK, WW, SS, kVarArea | kVarNear | kVarLights | kVarBare); break; \
+                                                      case kVarArea | kVarNear | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarArea | kVarNear | kVarLights | kVarCoat); break; \
+                                                      case kVarArea | kVarNear | kVarLights | kVarFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarArea | kVarNear | kVarLights | kVarFilt); break; \
+                                                      case kVarArea | kVarNear | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarArea | kVarNear | kVarLights | kVarCoatFilt); break; \
+                                                      case kVarArea | kVarNear | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarArea | kVarNear | kVarStack | kVarLights | kVarCoat); break; \
+                                                      case kVarArea | kVarNear | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarArea | kVarNear | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                                      case kVarArea | kVarNear | kVarOccl | kVarLights | kVarBare: LF_LAUNCH_CULL2(KK, WW, SS, kVarArea | kVarNear | kVarOccl | kVarLights | kVarBare); break; \
+                                                      case kVarArea | kVarNear | kVarOccl | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarArea | kVarNear | kVarOccl | kVarLights | kVarCoat); break; \
+                                                      case kVarArea | kVarNear | kVarOccl | kVarLights | kVarFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarArea | kVarNear | kVarOccl | kVarLights | kVarFilt); break; \
+                                                      case kVarArea | kVarNear | kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarArea | kVarNear | kVarOccl | kVarLights | kVarCoatFilt); break; \
+                                                      case kVarArea | kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_CULL2(KK, WW, SS, kVarArea | kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
+                                                      case kVarArea | kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_CULL2(KK, WW, SS, kVarArea | kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
                                                   default: LF_LAUNCH_CULL2(KK, WW, SS, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_CULL2(KK, WW, SS, CC)                                                                       \
   hipLaunchKernelGGL((k_march_cull<KK, WW, SS, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
@@ -908,6 +920,18 @@ lf_status lfk_march_culled(lf_ctx* ctx, const MarchArgs& a_in, size_t blocks, si
                                               case kVarNear | kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarOccl | kVarLights | kVarCoatFilt); break; \
                                               case kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
                                               case kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                              case kVarArea | kVarNear | kVarLights | kVarBare: LF_LAUNCH_ITEMS2(KK, kVarArea | kVarNear | kVarLights | kVarBare); break; \
+                                              case kVarArea | kVarNear | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarArea | kVarNear | kVarLights | kVarCoat); break; \
+                                              case kVarArea | kVarNear | kVarLights | kVarFilt: LF_LAUNCH_ITEMS2(KK, kVarArea | kVarNear | kVarLights | kVarFilt); break; \
+                                              case kVarArea | kVarNear | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarArea | kVarNear | kVarLights | kVarCoatFilt); break; \
+                                              case kVarArea | kVarNear | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarArea | kVarNear | kVarStack | kVarLights | kVarCoat); break; \
+                                              case kVarArea | kVarNear | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarArea | kVarNear | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                              case kVarArea | kVarNear | kVarOccl | kVarLights | kVarBare: LF_LAUNCH_ITEMS2(KK, kVarArea | kVarNear | kVarOccl | kVarLights | kVarBare); break; \
+                                              case kVarArea | kVarNear | kVarOccl | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarArea | kVarNear | kVarOccl | kVarLights | kVarCoat); break; \
+                                              case kVarArea | kVarNear | kVarOccl | kVarLights | kVarFilt: LF_LAUNCH_ITEMS2(KK, kVarArea | kVarNear | kVarOccl | kVarLights | kVarFilt); break; \
+                                              case kVarArea | kVarNear | kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarArea | kVarNear | kVarOccl | kVarLights | kVarCoatFilt); break; \
+                                              case kVarArea | kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_ITEMS2(KK, kVarArea | kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
+                                              case kVarArea | kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_ITEMS2(KK, kVarArea | kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
                                                   default: LF_LAUNCH_ITEMS2(KK, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_ITEMS2(KK, CC)                                                                             \
   hipLaunchKernelGGL((k_march_items<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \

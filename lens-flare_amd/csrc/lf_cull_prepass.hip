@@ -1119,6 +1119,14 @@ __global__ __launch_bounds__(256) void k_cull_audit_near(const LfLensDev* __rest
                                                          unsigned long long* __restrict__ out) {
   cull_audit_body<kVarLights | kVarNear>(lens, pairs, seq_table, rec_table, mask, a, table, out);
 }
+// ... an area light among them: lf_area_inside at the audit ray's exit point, never the cone the table took it as
+__global__ __launch_bounds__(256) void k_cull_audit_area(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
+                                                         const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
+                                                         const float* __restrict__ mask, CullAuditArgs a,
+                                                         const unsigned long long* __restrict__ table,
+                                                         unsigned long long* __restrict__ out) {
+  cull_audit_body<kVarLights | kVarNear | kVarArea>(lens, pairs, seq_table, rec_table, mask, a, table, out);
+}
 
 // The table is complete (built here, or completed by an all-gather): what fraction of all (block, cell, path)
 // combinations it starts -- counted from the table itself, so that every rank of a shared table finds the same number
@@ -1160,7 +1168,11 @@ lf_status lfk_cull_finish(lf_ctx* ctx, uint64_t hash) {
     const dim3 grid((unsigned)((ctx->cull_cells + 255) / 256), (unsigned)n_own_blk);
     hipEvent_t ev = lf_timing_begin(ctx, LFK_CULL_AUDIT);
     // (the audit sees every light of the context, whatever the table was built for: lf_test_knob("cull_ignore_light"))
-    if (lf_has_point_light(L))      // (a point light, also as the only light: the exact test at the audit ray's exit point)
+    if (lf_has_area_light(L))
+      hipLaunchKernelGGL(k_cull_audit_area, grid, dim3(256), 0, ctx->stream, ctx->lens_dev, ctx->pairs_dev,
+                         (const int*)(ctx->prog_dev + ctx->prog_seq_off), (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),
+                         audit_mask, a, ctx->cull_dev, ctx->cull_popc_dev + 1);
+    else if (lf_has_point_light(L))      // (a point light, also as the only light: the exact test at the audit ray's exit point)
       hipLaunchKernelGGL(k_cull_audit_near, grid, dim3(256), 0, ctx->stream, ctx->lens_dev, ctx->pairs_dev,
                          (const int*)(ctx->prog_dev + ctx->prog_seq_off), (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),
                          audit_mask, a, ctx->cull_dev, ctx->cull_popc_dev + 1);
@@ -1383,6 +1395,7 @@ static uint64_t cull_inputs_hash(const lf_ctx* ctx, CullLevelArgs a, const int* 
     std::memset(L.light_inv_one_minus_cos, 0, sizeof(L.light_inv_one_minus_cos));
     std::memset(L.light_ss, 0, sizeof(L.light_ss)); std::memset(L.light_thr, 0, sizeof(L.light_thr));
     std::memset(L.light_kind, 0, sizeof(L.light_kind)); std::memset(L.light_pos, 0, sizeof(L.light_pos));
+    std::memset(L.light_area, 0, sizeof(L.light_area));
   }
   uint64_t h = 0xcbf29ce484222325ull;
   h = fnv(h, &a, sizeof(a));
@@ -1427,6 +1440,13 @@ lf_status lfk_cull_prepass(lf_ctx* ctx, int G, int spp) {
     a.lrho[a.n_lights] = lf_cull_lobe_rho(sun ? L.sun_inv_one_minus_cos : L.light_inv_one_minus_cos[k]);
     // a point light enters as the direction unit(L) from the front vertex (light_dir[k]; light 0's is sun_dir too), its
     // radius widened by what that direction can differ from the one an exit point of the front element sees it in
+    // an area light enters as the cone lf_area_light_cull_cone gives it: unit(C) (light_dir[k]) and the angular reach of its
+    // corners, widened like a point light's (cull_no_widening: the corners' reach alone -- a wrong table, for the audit to refute)
+    if (L.n_lights > 0 && L.light_kind[k] == LF_LIGHT_AREA) {
+      float dir[3];
+      lf_area_cull_cone(L.light_pos[k], L.light_area[k], lf_front_reach(L.surf[0].radius, ctx->raw_semi_ap[0]), !ctx->cull_no_widening, dir,
+                        &a.lrho[a.n_lights]);
+    } else
     if (L.n_lights > 0 && L.light_kind[k] != LF_LIGHT_DIRECTIONAL && !ctx->cull_no_widening) {
       const double lx = L.light_pos[k][0], ly = L.light_pos[k][1], lz = (double)L.light_pos[k][2] - (double)L.surf[0].zv;
       a.lrho[a.n_lights] += lf_cull_near_widening(lf_front_reach(L.surf[0].radius, ctx->raw_semi_ap[0]), std::sqrt(lx * lx + ly * ly + lz * lz));

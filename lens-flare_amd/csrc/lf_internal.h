@@ -145,9 +145,19 @@ struct LfLensDev {
   // kVarNear kernels alone, and behind everything else: no field another kernel reads has moved.
   int light_kind[LF_MAX_LIGHTS];
   float light_pos[LF_MAX_LIGHTS][3];
+  // Area lights (lf_set_lights_geom, LF_LIGHT_AREA): light_pos[k] is the rectangle's centre, light_area[k] its direction (unit
+  // as stored), dim_x and dim_y in lens millimetres; light_thr[k] the squared radius of its bounding sphere (area_bound2,
+  // lf_api.hip), light_dir[k] unit(centre - front vertex); there is no lobe (light_inv_one_minus_cos[k] = 1, read by no
+  // kernel).  Read by the kVarArea kernels alone, behind everything else.
+  float light_area[LF_MAX_LIGHTS][9];
 };
+// (a light at a finite distance, point or area: the kVarNear kernels, the exact audit, the launch's fit check)
 inline bool lf_has_point_light(const LfLensDev& L) {
   for (int k = 0; k < L.n_lights; k++) if (L.light_kind[k] != LF_LIGHT_DIRECTIONAL) return true;
+  return false;
+}
+inline bool lf_has_area_light(const LfLensDev& L) {
+  for (int k = 0; k < L.n_lights; k++) if (L.light_kind[k] == LF_LIGHT_AREA) return true;
   return false;
 }
 // Ghost occlusion (lf_set_ghost_occlusion): the LfOcclDev record of a launch lies BEHIND the device's LfLensDev, in the same
@@ -672,13 +682,15 @@ inline void lf_install_split(lf_ctx* ctx, const LfSplit& s) {
 // | kVarNear: some installed light is a point light (lf_set_lights_ex) -- with kVarLights too, also when it is the only light
 // | kVarNear | kVarOccl together: launched only under LF_OCCLUSION_REACH_LIGHT (lf_set_ghost_occlusion_reach); under
 //   LF_OCCLUSION_REACH_SKY the launch's upload refuses the combination before any switch on the variant is reached
+// | kVarArea: some installed light is an area light (lf_set_lights_geom) -- with kVarLights | kVarNear, also as the only light
 inline int lf_march_variant(const lf_ctx* ctx) {
   const bool near = lf_has_point_light(ctx->lens);
   return (ctx->coat.n > 0 ? 1 : 0) | (ctx->mask_filter == LF_MASK_BILINEAR ? 2 : 0) |
          ((ctx->lens.n_lights > 1 || ctx->ghost_occlusion || near) ? 4 : 0) |
          (ctx->coat.n_stacked > 0 ? 8 : 0) |   // (kVarStack: only ever with kVarCoat -- a stacked interface counts in coat.n)
          (ctx->ghost_occlusion ? 16 : 0) |
-         (near ? 32 : 0);
+         (near ? 32 : 0) |
+         (lf_has_area_light(ctx->lens) ? 64 : 0);   // (kVarArea: an area light is a light at a finite distance too -- always with 4 | 32)
 }
 // The front element as a point light sees it (lf_set_lights_ex): r_f = sqrt(h0^2 + sag(h0)^2), the largest distance from the
 // front vertex to a point of its clear aperture (radius 0: flat; a semi-aperture beyond the sphere: the hemisphere's)
@@ -691,6 +703,13 @@ inline double lf_front_reach(float radius, float semi_aperture) {
 // direction space around unit(L): for P on the front cap |unit(L - P) - unit(L)| <= |P| / min(|L - P|, |L|) <= r_f / (dist - r_f)
 // (DESIGN.md section 5), with the relative and absolute float slack lf_cull_lobe_rho carries
 inline float lf_cull_near_widening(double r_f, double dist) { return (float)(r_f / (dist - r_f) * 1.001 + 1e-5); }
+// An area light (lf_set_lights_geom) as the cull pre-pass takes it (lf_area_light_cull_cone is this, exported; lf_api.hip):
+// dir = unit(C) from the front vertex, *rho = max over the four corners of |unit(corner) - unit(C)| -- reached at a corner: the
+// points within an angle below 90 degrees of unit(C) form a cone whose section by the light's plane is convex; a corner at
+// 90 degrees or more: 2, every direction -- plus, with `widen`, r_f / (dmin - r_f), dmin the distance from the front vertex
+// to the nearest point of the rectangle; with lf_cull_near_widening's relative and absolute slack.  C: the centre, g:
+// direction, dim_x, dim_y as stored (LfLensDev::light_area).  All in double.
+void lf_area_cull_cone(const float* C, const float* g, double r_f, bool widen, float dir[3], float* rho);
 // the cull table is not this context's alone: shared between ranks, or built only in part (the frame dealt by blocks)
 inline bool lf_cull_table_split(const lf_ctx* ctx) {
   return ctx->split.table != LfSplit::kOwn || ctx->split.deal == LfSplit::kBlocks;

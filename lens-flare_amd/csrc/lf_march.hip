@@ -715,21 +715,49 @@ __global__ __launch_bounds__(256) void k_ghost_ray_light_visibility(const LfLens
     visible[(size_t)i * (size_t)nl + (size_t)k] = ghost_ray_visible(o, r[0], r[1], r[2], r[3], r[4], r[5], reach) ? 1 : 0;
   }
 }
+// ... with an area light installed: its reach is lf_area_shadow_reach, just before the rectangle (a kernel of its own: the one
+// above stays what it was, register for register)
+__global__ __launch_bounds__(256) void k_ghost_ray_light_visibility_area(const LfLensDev* __restrict__ lens, LfOcclDev o, int n,
+                                                                         const float* __restrict__ rays, unsigned char* __restrict__ visible) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const float* r = rays + 6 * (size_t)i;
+  const int nl = lens->n_lights;
+  for (int k = 0; k < nl; k++) {
+    double reach = (double)INFINITY;
+    if (lens->light_kind[k] == LF_LIGHT_AREA)
+      reach = lf_area_shadow_reach(r[3], r[4], r[5], r[0], r[1], r[2], lens->light_pos[k], lens->light_area[k], o.wpm);
+    else if (lens->light_kind[k] != LF_LIGHT_DIRECTIONAL)
+      reach = lf_point_shadow_reach(r[3], r[4], r[5], r[0], r[1], r[2], lens->light_pos[k][0], lens->light_pos[k][1], lens->light_pos[k][2],
+                                    o.wpm);
+    visible[(size_t)i * (size_t)nl + (size_t)k] = ghost_ray_visible(o, r[0], r[1], r[2], r[3], r[4], r[5], reach) ? 1 : 0;
+  }
+}
 
 // lf_ghost_ray_light_factors: per exit ray {origin xyz (z absolute), direction xyz} and installed light k, (1 - q_k)^2 where
 // the ray lies inside light k and 0 elsewhere -- the lit epilogue's own test and factor (light_admits_at), without a weight
-__global__ __launch_bounds__(256) void k_ghost_ray_light_factors(const LfLensDev* __restrict__ lens, int n, const float* __restrict__ rays,
-                                                                 float* __restrict__ out) {
+// (an area light: 1 where the ray ends on its lit side -- k_ghost_ray_light_factors_area, launched when one is installed)
+template <int VAR>
+__device__ __forceinline__ void ghost_ray_light_factors_body(const LfLensDev* __restrict__ lens, int n, const float* __restrict__ rays,
+                                                             float* __restrict__ out) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
   const float* r = rays + 6 * (size_t)i;
   const int nl = lens->n_lights;
   for (int k = 0; k < nl; k++) {
     float q;
-    const bool in = light_admits_at<kVarLights | kVarNear>(lens, k, r[0], r[1], r[2] - lens->surf[0].zv, r[3], r[4], r[5], q);
+    const bool in = light_admits_at<VAR>(lens, k, r[0], r[1], r[2] - lens->surf[0].zv, r[3], r[4], r[5], q);
     const float om = 1.0f - q;
     out[(size_t)i * (size_t)nl + (size_t)k] = in ? om * om : 0.0f;
   }
+}
+__global__ __launch_bounds__(256) void k_ghost_ray_light_factors(const LfLensDev* __restrict__ lens, int n, const float* __restrict__ rays,
+                                                                 float* __restrict__ out) {
+  ghost_ray_light_factors_body<kVarLights | kVarNear>(lens, n, rays, out);
+}
+__global__ __launch_bounds__(256) void k_ghost_ray_light_factors_area(const LfLensDev* __restrict__ lens, int n, const float* __restrict__ rays,
+                                                                      float* __restrict__ out) {
+  ghost_ray_light_factors_body<kVarLights | kVarNear | kVarArea>(lens, n, rays, out);
 }
 
 // The support texture of the bilinear stop mask (lf_set_mask_filter; DESIGN.md section 5, "the support texture"):
@@ -841,6 +869,7 @@ void lf_derive_lens(lf_ctx* ctx, int n, int stop, int n_lambda, const float* rad
   std::memcpy(L.light_thr, keep.light_thr, sizeof(L.light_thr));
   std::memcpy(L.light_kind, keep.light_kind, sizeof(L.light_kind));
   std::memcpy(L.light_pos, keep.light_pos, sizeof(L.light_pos));
+  std::memcpy(L.light_area, keep.light_area, sizeof(L.light_area));
   L.n_surf = n; L.stop = stop; L.n_lambda = n_lambda;
   float z = 0.0f;
   for (int k = 0; k < n; k++) {
@@ -1491,6 +1520,18 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
                                    case kVarNear | kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarNear | kVarOccl | kVarLights | kVarCoatFilt); break; \
                                    case kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
                                    case kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                   case kVarArea | kVarNear | kVarLights | kVarBare: LF_LAUNCH_MARCH2(KK, kVarArea | kVarNear | kVarLights | kVarBare); break; \
+                                   case kVarArea | kVarNear | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarArea | kVarNear | kVarLights | kVarCoat); break; \
+                                   case kVarArea | kVarNear | kVarLights | kVarFilt: LF_LAUNCH_MARCH2(KK, kVarArea | kVarNear | kVarLights | kVarFilt); break; \
+                                   case kVarArea | kVarNear | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarArea | kVarNear | kVarLights | kVarCoatFilt); break; \
+                                   case kVarArea | kVarNear | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarArea | kVarNear | kVarStack | kVarLights | kVarCoat); break; \
+                                   case kVarArea | kVarNear | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarArea | kVarNear | kVarStack | kVarLights | kVarCoatFilt); break; \
+                                   case kVarArea | kVarNear | kVarOccl | kVarLights | kVarBare: LF_LAUNCH_MARCH2(KK, kVarArea | kVarNear | kVarOccl | kVarLights | kVarBare); break; \
+                                   case kVarArea | kVarNear | kVarOccl | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarArea | kVarNear | kVarOccl | kVarLights | kVarCoat); break; \
+                                   case kVarArea | kVarNear | kVarOccl | kVarLights | kVarFilt: LF_LAUNCH_MARCH2(KK, kVarArea | kVarNear | kVarOccl | kVarLights | kVarFilt); break; \
+                                   case kVarArea | kVarNear | kVarOccl | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarArea | kVarNear | kVarOccl | kVarLights | kVarCoatFilt); break; \
+                                   case kVarArea | kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat: LF_LAUNCH_MARCH2(KK, kVarArea | kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoat); break; \
+                                   case kVarArea | kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarArea | kVarNear | kVarOccl | kVarStack | kVarLights | kVarCoatFilt); break; \
                                                   default: LF_LAUNCH_MARCH2(KK, kVarLights | kVarBare); break; } } while (0)
 #define LF_LAUNCH_MARCH2(KK, CC)                                                                   \
   hipLaunchKernelGGL((k_march<KK, CC>), dim3((unsigned)blocks), dim3(64 * kWgWaves), dyn_lds, ctx->stream, ctx->lens_dev, \
@@ -1596,6 +1637,10 @@ lf_status lfk_ghost_ray_visibility(lf_ctx* ctx, const LfOcclDev& o, size_t n, co
 // (the caller has uploaded ctx->lens to lens_dev on the same stream; d_vis: n x n_lights bytes)
 lf_status lfk_ghost_ray_light_visibility(lf_ctx* ctx, const LfOcclDev& o, size_t n, const float* d_rays, unsigned char* d_vis) {
   if (n == 0) return LF_OK;
+  if (lf_has_area_light(ctx->lens))
+    hipLaunchKernelGGL(k_ghost_ray_light_visibility_area, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->lens_dev, o,
+                       (int)n, d_rays, d_vis);
+  else
   hipLaunchKernelGGL(k_ghost_ray_light_visibility, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->lens_dev, o,
                      (int)n, d_rays, d_vis);
   LF_HIP(ctx, hipGetLastError());
@@ -1605,6 +1650,10 @@ lf_status lfk_ghost_ray_light_visibility(lf_ctx* ctx, const LfOcclDev& o, size_t
 // (the caller has uploaded ctx->lens to lens_dev on the same stream; d_out: n x n_lights floats)
 lf_status lfk_ghost_ray_light_factors(lf_ctx* ctx, size_t n, const float* d_rays, float* d_out) {
   if (n == 0) return LF_OK;
+  if (lf_has_area_light(ctx->lens))
+    hipLaunchKernelGGL(k_ghost_ray_light_factors_area, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->lens_dev, (int)n,
+                       d_rays, d_out);
+  else
   hipLaunchKernelGGL(k_ghost_ray_light_factors, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, ctx->lens_dev, (int)n,
                      d_rays, d_out);
   LF_HIP(ctx, hipGetLastError());

@@ -97,10 +97,16 @@ __device__ __forceinline__ bool light_admits(const LfLensDev* __restrict__ lens,
 // ... of the ray that left the front element at (px, py, front vertex + hz) along d: under VAR & kVarNear a POINT light k
 // (lens->light_kind[k], wave-uniform: a scalar branch) takes the direction to it from that point -- s = L_k - P per lane,
 // inside iff d.s > 0 and q < 1 (lf_point_lobe_q, lf_march_events.h); a directional light, and every light of a kernel
-// without kVarNear, is decided by the direction alone, as above.
+// without kVarNear, is decided by the direction alone, as above.  Under VAR & kVarArea an AREA light k (the same scalar
+// branch on the kind; its twelve geometry floats scalar operands) is decided by lf_area_inside at that point, with q = 0:
+// (1 - q)^2 is exactly 1, the factor of a light without a lobe.
 template <int VAR>
 __device__ __forceinline__ bool light_admits_at(const LfLensDev* __restrict__ lens, int k, float px, float py, float hz, float dx, float dy,
                                                 float dz, float& q) {
+  if ((VAR & kVarArea) && lens->light_kind[k] == LF_LIGHT_AREA) {
+    q = 0.0f;
+    return lf_area_inside(dx, dy, dz, px, py, lens->surf[0].zv + hz, lens->light_pos[k], lens->light_area[k]);
+  }
   if ((VAR & kVarNear) && lens->light_kind[k] != LF_LIGHT_DIRECTIONAL) {
     float cg;
     q = lf_point_lobe_q(dx, dy, dz, px, py, lens->surf[0].zv + hz, lens->light_pos[k][0], lens->light_pos[k][1], lens->light_pos[k][2],
@@ -112,7 +118,8 @@ __device__ __forceinline__ bool light_admits_at(const LfLensDev* __restrict__ le
 // The pre-test of a completed path's K rays: lit[j] = the lanes of alive[j] that ANY light's pre-test admits (d.s_k > thr_k)
 // and then -- GATE, the geometry-first kernels: what lobe_gate is to one light -- that lie inside ANY light's lobe, so that
 // a wavelength none of whose lanes will contribute to any light is not marched again.  Returns the union of the masks.
-// (VAR & kVarNear: a point light's pre-test is lf_point_pretest on the ray's exit point, a superset of its lobe)
+// (VAR & kVarNear: a point light's pre-test is lf_point_pretest on the ray's exit point, a superset of its lobe;
+//  VAR & kVarArea: an area light's is lf_area_pretest, its bounding sphere seen from that point)
 template <int K, bool GATE, int VAR = kVarLights>
 __device__ __forceinline__ lanemask lights_pretest(const LfLensDev* __restrict__ lens, const Ray (&r)[K], const lanemask (&alive)[K],
                                                    lanemask (&lit)[K]) {
@@ -122,6 +129,11 @@ __device__ __forceinline__ lanemask lights_pretest(const LfLensDev* __restrict__
   for (int j = 0; j < K; j++) {
     bool near = false;
     for (int k = 0; k < n; k++) {
+      if ((VAR & kVarArea) && lens->light_kind[k] == LF_LIGHT_AREA) {   // (its bounding sphere, light_thr[k] the radius squared)
+        near = lf_area_pretest(r[j].dx, r[j].dy, r[j].dz, r[j].px, r[j].py, lens->surf[0].zv + r[j].hz, lens->light_pos[k],
+                               lens->light_thr[k]) || near;
+        continue;
+      }
       if ((VAR & kVarNear) && lens->light_kind[k] != LF_LIGHT_DIRECTIONAL) {
         near = lf_point_pretest(r[j].dx, r[j].dy, r[j].dz, r[j].px, r[j].py, lens->surf[0].zv + r[j].hz, lens->light_pos[k][0],
                                 lens->light_pos[k][1], lens->light_pos[k][2], lens->light_thr[k]) || near;
@@ -178,6 +190,9 @@ __device__ __forceinline__ void lights_channel_factors(const LfLensDev* __restri
 // [0, T] every longer one.  A lane keeps the longest segment it found free and the shortest it found blocked, and walks
 // only for a reach between the two: the directional lights (all +inf) still share one walk, two lamps on the same side of
 // every occluder share one, and each answer is the per-light definition's, whatever the other lights are.
+//
+// VAR & kVarArea: an area light's q is 0 (light_admits_at), so its contrib is wn / wd itself; under kVarOccl its reach is
+// lf_area_shadow_reach -- just before the rectangle -- and joins the same reuse of walks.
 template <int VAR = kVarLights>
 __device__ __forceinline__ void lights_epilogue(const LfLensDev* __restrict__ lens, const float* __restrict__ s_chan, const Ray& rw,
                                                 bool mine, int l, unsigned long long* __restrict__ acc, unsigned& n_light) {
@@ -200,10 +215,13 @@ __device__ __forceinline__ void lights_epilogue(const LfLensDev* __restrict__ le
       const bool test = contrib > 0.0f;
       // (the light's kind through the scalar cache, as in light_admits_at: a scalar branch around the lanes' reach)
       const bool point = lens->light_kind[k] != LF_LIGHT_DIRECTIONAL;
+      const bool area = (VAR & kVarArea) && lens->light_kind[k] == LF_LIGHT_AREA;
       if (test) {
         const float z = occl.front_zv + rw.hz;
         double reach = (double)INFINITY;
-        if (point)
+        if (area)        // (... just before the rectangle's plane)
+          reach = lf_area_shadow_reach(rw.dx, rw.dy, rw.dz, rw.px, rw.py, z, lens->light_pos[k], lens->light_area[k], occl.wpm);
+        else if (point)
           reach = lf_point_shadow_reach(rw.dx, rw.dy, rw.dz, rw.px, rw.py, z, lens->light_pos[k][0], lens->light_pos[k][1],
                                         lens->light_pos[k][2], occl.wpm);
         bool v;

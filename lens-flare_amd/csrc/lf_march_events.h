@@ -363,10 +363,13 @@ enum : int { kVarBare = 0, kVarCoat = 1, kVarFilt = 2, kVarCoatFilt = 3,
              kVarStack = 8,     // | kVarStack (only with kVarCoat): some interface holds a stack of layers (lf_set_lens_coating_stacks)
              kVarOccl = 16,     // | kVarOccl (only with kVarLights): a lit ray adds only what the scene does not block (lf_set_ghost_occlusion);
                                 //   differs from its kVarLights twin in lights_epilogue alone (lf_march_common.h)
-             kVarNear = 32 };   // | kVarNear (only with kVarLights): some light is a POINT light (lf_set_lights_ex): the pre-test, the gate
+             kVarNear = 32,     // | kVarNear (only with kVarLights): some light is a POINT light (lf_set_lights_ex): the pre-test, the gate
                                 //   and the lit epilogue form the direction to such a light per lane, from the ray's exit point
                                 // kVarNear | kVarOccl (launched only under lf_set_ghost_occlusion_reach(LF_OCCLUSION_REACH_LIGHT)): the shadow
                                 //   ray of a point light ends at the light (lf_point_shadow_reach below, lights_epilogue in lf_march_common.h)
+             kVarArea = 64 };   // | kVarArea (only with kVarLights | kVarNear): some light is an AREA light (lf_set_lights_geom, LF_LIGHT_AREA):
+                                //   such a light's pre-test, gate and epilogue are the ray-parallelogram test below (lf_area_inside); the
+                                //   kernel handles all three kinds, a context without an area light never launches it
 
 // ---- a light at a finite distance (lf_set_lights_ex, LF_LIGHT_POINT; DESIGN.md section 4, "point lights") -------------
 // The lobe factor of a ray that has left the front element at (px, py, z) (z absolute: front vertex z + hz) along d, for a
@@ -412,6 +415,67 @@ __host__ __device__ inline double lf_point_shadow_reach(float dx, float dy, floa
   const double cx = ax * rn, cy = ay * rn, cz = az * rn;
   const double t = wpm * ((sx * cx + sy * cy) + sz * cz);
   return t > 0.0 ? t : 0.0;
+}
+// ---- an area light (lf_set_lights_geom, LF_LIGHT_AREA; DESIGN.md section 4, "area lights") -----------------------------
+// A one-sided parallelogram C + u e1 + v e2, u, v in [-1/2, 1/2], emitting towards dir.  Is the ray that has left the front
+// element at P = (px, py, z) (z absolute) along d one that ends on its lit side?  The ray-parallelogram test with no
+// division and no root (Moeller-Trumbore's, every quotient cleared by |det|), in THIS order, every multiply-add an fmaf:
+//   s  = P - C                                   three float subtractions
+//   p  = d x e2     p.x = fmaf(d.y, e2.z, -(d.z * e2.y)),  p.y = fmaf(d.z, e2.x, -(d.x * e2.z)),  p.z = fmaf(d.x, e2.y, -(d.y * e2.x))
+//   det = e1 . p    fmaf(e1.x, p.x, fmaf(e1.y, p.y, e1.z * p.z))          (every dot product in this x, y, z nesting)
+//   a  = s . p                                   (u = a / det)
+//   qv = s x e1     the same pattern as p
+//   b  = d . qv     (v = b / det),     tn = e2 . qv     (the ray parameter t = tn / det),     cd = d . dir
+//   inside iff det != 0 and 2 |a| <= |det| and 2 |b| <= |det| and tn sign(det) > 0 and cd < 0
+// (2 |a| is exact; cd < 0 is the reference's cosTheta < 0, its d running from the shaded point to the light.)  C: the centre,
+// g: direction (unit as stored), e1, e2 -- nine floats.  The host (lf_light_geom_factor) and the kernels all call THIS
+// definition: they agree bit for bit.  A lit ray's factor is 1: radiance is constant along a ray, there is no lobe.
+__host__ __device__ inline bool lf_area_inside(float dx, float dy, float dz, float px, float py, float z, const float* __restrict__ C,
+                                               const float* __restrict__ g) {
+  const float e1x = g[3], e1y = g[4], e1z = g[5], e2x = g[6], e2y = g[7], e2z = g[8];
+  const float sx = px - C[0], sy = py - C[1], sz = z - C[2];
+  const float qx = fmaf(dy, e2z, -(dz * e2y)), qy = fmaf(dz, e2x, -(dx * e2z)), qz = fmaf(dx, e2y, -(dy * e2x));
+  const float det = fmaf(e1x, qx, fmaf(e1y, qy, e1z * qz));
+  const float a = fmaf(sx, qx, fmaf(sy, qy, sz * qz));
+  const float vx = fmaf(sy, e1z, -(sz * e1y)), vy = fmaf(sz, e1x, -(sx * e1z)), vz = fmaf(sx, e1y, -(sy * e1x));
+  const float b = fmaf(dx, vx, fmaf(dy, vy, dz * vz));
+  const float tn = fmaf(e2x, vx, fmaf(e2y, vy, e2z * vz));
+  const float cd = fmaf(dx, g[0], fmaf(dy, g[1], dz * g[2]));
+  const float ad = fabsf(det);
+  return det != 0.0f && 2.0f * fabsf(a) <= ad && 2.0f * fabsf(b) <= ad && (det > 0.0f ? tn > 0.0f : tn < 0.0f) && cd < 0.0f;
+}
+// ... and the cheap test that SELECTS lanes for it (any superset of lf_area_inside will do): does the ray's line, taken
+// forwards, meet the rectangle's bounding sphere -- centre C, radius^2 rb2 (the half diagonal's square, rounded up: the host's
+// area_bound2, lf_api.hip)?  With s = C - P, ss = |s|^2, cg = d.s, dd = |d|^2: ss <= rb2 (P inside the sphere), or cg > 0 and
+// cg^2 >= dd (ss - rb2) -- no root, no division.  cg^2 and dd ss carry five roundings each (below 4e-7 relative); ss is
+// taken 1e-5 smaller, which covers both and the subtraction's own rounding.
+__host__ __device__ inline bool lf_area_pretest(float dx, float dy, float dz, float px, float py, float z, const float* __restrict__ C,
+                                                float rb2) {
+  const float sx = C[0] - px, sy = C[1] - py, sz = C[2] - z;
+  const float ss = fmaf(sx, sx, fmaf(sy, sy, sz * sz));
+  const float cg = fmaf(dx, sx, fmaf(dy, sy, dz * sz));
+  const float dd = fmaf(dx, dx, fmaf(dy, dy, dz * dz));
+  return ss <= rb2 || (cg > 0.0f && cg * cg >= dd * fmaf(ss, 0.99999f, -rb2));
+}
+// How far the shadow ray of an AREA light reaches (LF_OCCLUSION_REACH_LIGHT): to just before the rectangle's plane.  The
+// expressions of lf_area_inside again, in double, on the float-stored geometry and the ray: t = tn / det, reach = wpm t |d|
+// minus the reference's EPS_F = (double)0.00001f -- what its shadow rays to sampled lights take off, and lf_scene.hip's: an
+// emissive mesh lying in the light's plane does not shadow its own light -- never below 0 (a ray parallel to the plane, or
+// leaving it behind: 0).  Plain double products and sums in the order written, nothing contracts: the host
+// (lf_ghost_shadow_reach_geom) and the kernels, which all call THIS definition, agree bit for bit.  *t_out: t itself.
+__host__ __device__ inline double lf_area_shadow_reach(float dx, float dy, float dz, float px, float py, float z, const float* __restrict__ C,
+                                                       const float* __restrict__ g, double wpm, double* t_out = nullptr) {
+  const double ax = (double)dx, ay = (double)dy, az = (double)dz;
+  const double e1x = (double)g[3], e1y = (double)g[4], e1z = (double)g[5], e2x = (double)g[6], e2y = (double)g[7], e2z = (double)g[8];
+  const double sx = (double)px - (double)C[0], sy = (double)py - (double)C[1], sz = (double)z - (double)C[2];
+  const double qx = ay * e2z - az * e2y, qy = az * e2x - ax * e2z, qz = ax * e2y - ay * e2x;
+  const double det = (e1x * qx + e1y * qy) + e1z * qz;
+  const double vx = sy * e1z - sz * e1y, vy = sz * e1x - sx * e1z, vz = sx * e1y - sy * e1x;
+  const double tn = (e2x * vx + e2y * vy) + e2z * vz;
+  const double t = tn / det;
+  if (t_out) *t_out = t;
+  const double r = (wpm * t) * sqrt((ax * ax + ay * ay) + az * az) - (double)0.00001f;
+  return r > 0.0 ? r : 0.0;   // (NaN -- det = 0 -- gives 0 as well)
 }
 // The stop of a kernel instantiated for variant VAR.  Under the filter the geometry-only march (W = false) runs
 // the UNCHANGED nearest lookup on the support texture S (2 mw x 2 mh floats behind the texels, k_mask_support:

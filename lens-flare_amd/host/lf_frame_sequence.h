@@ -40,7 +40,8 @@ typedef struct lf_frame_plan {
   int ghosts;                     // lf_frame_ghosts
   int sun_from_flares;            // the march's lights = EVERY in-frame light of the flare state (lf_set_lights_from_flares;
                                   // one flare: exactly lf_set_sun_from_flares(0)); 2: those and the resident scene's
-                                  // PointLights at their own distance (lf_set_lights_from_scene, scale world_per_mm)
+                                  // PointLights at their own distance (lf_set_lights_from_scene, scale world_per_mm);
+                                  // 3: ... and its AreaLights as rectangles (lf_set_lights_from_scene_ex)
   float sun_angular_radius;
   int geo_spp;
   uint64_t geo_key;
@@ -71,7 +72,9 @@ static inline lf_status lf_run_frame(lf_ctx* ctx, const lf_frame_plan* p, const 
   LF_FRAME_STEP(lf_set_ghost_occlusion(ctx, (p->ghost_occlusion && p->ghosts == LF_FRAME_GHOSTS_MARCH) ? 1 : 0,
                                        p->world_per_mm));
   if (p->ghosts == LF_FRAME_GHOSTS_MARCH) {
-    if (p->sun_from_flares == 2)
+    if (p->sun_from_flares == 3)
+      LF_FRAME_STEP(lf_set_lights_from_scene_ex(ctx, 0.0, p->sun_angular_radius, p->world_per_mm, NULL, NULL, NULL));
+    else if (p->sun_from_flares == 2)
       LF_FRAME_STEP(lf_set_lights_from_scene(ctx, 0.0, p->sun_angular_radius, p->world_per_mm, NULL, NULL));
     else if (p->sun_from_flares)
       LF_FRAME_STEP(lf_set_lights_from_flares(ctx, 0.0, p->sun_angular_radius, NULL));

@@ -206,8 +206,14 @@ void PathTracer::use_lights_from_scene(float angular_radius) {
   if (!geometric_) throw std::runtime_error("use_lights_from_scene: use_geometric_ghosts comes first (it installs the lens)");
   lights_from_scene_ = true;
   lights_from_flares_ = false;
+  area_lights_from_scene_ = false;
   lights_radius_ = angular_radius;
   frame_ready_ = false;
+}
+
+void PathTracer::use_area_lights_from_scene(float angular_radius) {
+  use_lights_from_scene(angular_radius);
+  area_lights_from_scene_ = true;
 }
 
 void PathTracer::use_ghost_occlusion(bool on) {
@@ -281,8 +287,9 @@ void PathTracer::generate_ghost_buffer() {
   plan.jitter = counter_jitter ? LF_FRAME_JITTER_COUNTER : LF_FRAME_JITTER_MT19937;
   plan.mt_seed = jitter_seed; plan.counter_key = 0x1e45f1a4eULL;
   plan.ghosts = geometric_ ? LF_FRAME_GHOSTS_MARCH : LF_FRAME_GHOSTS_PARAXIAL;
-  // (0: use_geometric_ghosts / set_lights installed the lights explicitly; 2: the flares and the device scene's PointLights)
-  plan.sun_from_flares = lights_from_scene_ ? 2 : lights_from_flares_ ? 1 : 0;
+  // (0: use_geometric_ghosts / set_lights installed the lights explicitly; 2: the flares and the device scene's PointLights;
+  //  3: ... and its AreaLights)
+  plan.sun_from_flares = lights_from_scene_ ? (area_lights_from_scene_ ? 3 : 2) : lights_from_flares_ ? 1 : 0;
   plan.sun_angular_radius = lights_radius_;
   plan.geo_spp = geo_spp_; plan.geo_key = 0x1e45f1a4eULL;
   plan.lens_camera_mode = geometric_ ? lens_camera_mode : 0;

@@ -137,6 +137,10 @@ class PathTracer {
   // use_ghost_occlusion, a scene with a PointLight in front of the lens needs use_ghost_occlusion_reach(
   // LF_OCCLUSION_REACH_LIGHT) (below); without it the launch is refused.
   void use_lights_from_scene(float angular_radius);
+  // ... and every AreaLight of the device scene as a rectangle of the march (lf_set_lights_from_scene_ex; the angular radius is
+  // the flares' and the point lights': a rectangle has no lobe).  Opt-in, like the call above.  With the lens camera on, an
+  // emissive mesh in the lamp's place is already imaged by the scene term: such a host drops the march's primary path.
+  void use_area_lights_from_scene(float angular_radius);
   // after use_geometric_ghosts: the scene hides the march's ghosts (lf_set_ghost_occlusion, scale lens_world_per_mm): a lit
   // ghost ray adds only what no primitive between the front element and the sky blocks.  Needs a device scene (set_scene /
   // load_collada) and the camera at the frame.  Off by default: the frames are those of a mirror without this call.
@@ -170,7 +174,7 @@ class PathTracer {
   lf_ctx* ctx_ = nullptr;
   bool frame_ready_ = false, textures_uploaded_ = false, geometric_ = false, device_scene_ = false;
   int geo_spp_ = 0;
-  bool lights_from_flares_ = false, lights_from_scene_ = false;
+  bool lights_from_flares_ = false, lights_from_scene_ = false, area_lights_from_scene_ = false;
   bool ghost_occlusion_ = false;
   float lights_radius_ = 0.05f;
   std::vector<double> star_;    // host mirror of raytrace_starburst for every pixel
