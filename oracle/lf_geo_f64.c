@@ -35,6 +35,18 @@
  * arithmetic, written from the textbook below), never the geometry.  Under the filter the stop's weight is
  * continuous across texel edges, so cause bit 2 is not raised; a ray carries a SLOPE ALLOWANCE instead: how
  * far a move of eps_mm at the stop can change its weight (stop_bilinear), added into `frag`.
+ *
+ * The light list (lf_set_lights, lf_set_lights_ex, lf_set_lights_geom): a process-global setting, off by default
+ * (g64_set_lights) -- with none set g64_trace shades with the single sun of g64_lens and every result is bit for bit
+ * what it was.  With a list, every ray that left the front element is tested against every light at its own float64
+ * exit point r.o along r.d, written from the textbook: a directional light by q = (1 - unit(d).unit(s)) / (1 - cos
+ * alpha), factor (1 - q)^2 where q < 1; a point light at L the same with s = L - r.o; an area light by the plane's
+ * intersection and (u, v) through the Gram matrix of its edges, factor 1 (area_lit).  Contributions add, each with
+ * its own light's radiance; counter 6 counts (ray, light) pairs.  A lobe falls to zero continuously and needs no
+ * band; a rectangle's outline is a hard edge: a pair whose hit point lies within eps_light(t) = eps_exit + t eps_dir
+ * + 2.4e-7 |P - C| millimetres of it (or whose ray grazes the plane's horizon, |d.dir| < eps_cos) is decided as
+ * float64 decides, its weight goes into `frag` whichever way that was, and a ninth counter (light_edge_pairs) counts
+ * it -- read with g64_light_edge_pairs(): the array handed to g64_trace keeps the eight slots older callers allocate.
  */
 #define _GNU_SOURCE
 #include <complex.h>
@@ -496,8 +508,89 @@ void g64_set_cull(const uint64_t* table, int blocks_x, int blocks_y, int cells, 
   g64_cull_shift = block_px == 128 ? 7 : block_px == 32 ? 5 : block_px == 16 ? 4 : 6;
 }
 
+/* ---- the light list (lf_set_lights / lf_set_lights_ex / lf_set_lights_geom) -------------------------------------
+ * A process-global setting, off by default: n = 0 restores the single sun of g64_lens, and every result is then bit
+ * for bit what it was before the list existed.  Values as the device stores them (float32 held in doubles, what
+ * lf_get_lights_geom reports): kind 0 directional (geom[0..2] the direction TO the light), 1 point (geom[0..2] its
+ * position, lens millimetres, front vertex at z = 0, scene at z < 0), 2 area (geom = centre, direction, e1, e2). */
+#define G64_MAX_LIGHTS 8
+enum { G64_DIRECTIONAL = 0, G64_POINT = 1, G64_AREA = 2 };
+static int g64_n_lights = 0;
+static int g64_light_kind[G64_MAX_LIGHTS];
+static double g64_light_geom[G64_MAX_LIGHTS][12], g64_light_rad[G64_MAX_LIGHTS][3], g64_light_alpha[G64_MAX_LIGHTS];
+void g64_set_lights(int n, const int* kinds, const double* geom, const double* radiance, const double* angular_radius) {
+  g64_n_lights = 0;
+  if (n <= 0 || n > G64_MAX_LIGHTS) return;
+  for (int k = 0; k < n; k++) {
+    g64_light_kind[k] = kinds[k];
+    memcpy(g64_light_geom[k], geom + 12 * k, sizeof(g64_light_geom[k]));
+    memcpy(g64_light_rad[k], radiance + 3 * k, sizeof(g64_light_rad[k]));
+    g64_light_alpha[k] = angular_radius[k];
+  }
+  g64_n_lights = n;
+}
+/* The edge band of a rectangle: how far (mm, in the rectangle's plane) the float32 march's hit point can lie from
+ * the float64 one.  G64_EPS_EXIT / G64_EPS_DIR are G64_EPS_FACTOR times the largest deviation of the float32 oracle's
+ * exit point (mm) / unit exit direction from this tracer's (g64_exit_deviation below), over the primary path and all
+ * 45 ghost pairs x 3 wavelengths of every sample ray of one 64 x 48 x 64 spp frame (key 0xE95) per lens the tests
+ * install a rectangle with, fragile rays skipped (4.58e6 rays compared per lens, no fate differs):
+ *   dgauss11.lens, 64 pixels of the 36 mm / 1920 sensor          7.696e-5 mm   2.237e-6
+ *   dgauss11_coated.lens, the same crop                          7.696e-5 mm   2.237e-6   (a film moves no ray)
+ * -> 7.70e-5 mm and 2.24e-6, times the factor 10 that eps_mm takes over the march's accumulated error.  (The ghosts
+ * make these figures: the 531 rays of tests/test_geo_rays_vs_f64.py stay within 7.6e-6 mm and 1.2e-6.  Other frames
+ * need their own: the 80-pixel crop 8.84e-5 mm / 2.36e-6, the full 36 mm sensor 6.5e-4 mm / 7.3e-5 -- steep ghost
+ * rays -- under which the band of a 12 x 8 mm rectangle 90 mm away would no longer be the exception.)  The third term
+ * is the float32 test's own rounding, 4 * 2^-24 |P - C| (tests/test_area_ghosts_cpu.py). */
+#define G64_EPS_FACTOR 10.0
+#define G64_EPS_EXIT (G64_EPS_FACTOR * 7.70e-5)
+#define G64_EPS_DIR (G64_EPS_FACTOR * 2.24e-6)
+#define G64_EPS_TEST 2.4e-7
+/* per light of the list, of the last g64_trace: its (ray, light) pairs with a positive contribution, and those in its edge band */
+static uint64_t g64_pairs_lit[G64_MAX_LIGHTS], g64_pairs_edge[G64_MAX_LIGHTS];
+void g64_light_pairs(uint64_t lit[G64_MAX_LIGHTS], uint64_t edge[G64_MAX_LIGHTS]) {
+  memcpy(lit, g64_pairs_lit, sizeof(g64_pairs_lit));
+  memcpy(edge, g64_pairs_edge, sizeof(g64_pairs_edge));
+}
+void g64_light_eps(double out[3]) { out[0] = G64_EPS_EXIT; out[1] = G64_EPS_DIR; out[2] = G64_EPS_TEST; }
+
+/* Is the ray (P, unit d) one that ends on the lit side of the parallelogram C + u e1 + v e2, |u|, |v| <= 1/2, which
+ * emits towards dir?  The plane's intersection t = n.(C - P) / (n.d), n = e1 x e2; (u, v) of the hit point from the
+ * normal equations of (e1, e2) (their Gram matrix); lit iff inside, t > 0 and d.dir < 0.  *edge: the decision is one
+ * float32 may take the other way -- the hit point lies within eps_light(t) = eps_exit + t eps_dir + 2.4e-7 |P - C|
+ * of one of the four edge SEGMENTS (within it of the edge's line, and not further than it beyond the segment's
+ * ends), on either side, or |d.dir| < eps_cos. */
+static int area_lit(const double* g, vec P, vec d, double eps_cos, int* edge) {
+  const vec C = V(g[0], g[1], g[2]), dir = normalise(V(g[3], g[4], g[5]));
+  const vec e1 = V(g[6], g[7], g[8]), e2 = V(g[9], g[10], g[11]);
+  const vec n = V(e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x);
+  const double facing = dotp(d, dir);
+  const double t = dotp(n, sub(C, P)) / dotp(n, d);
+  *edge = 0;
+  if (!(t > 0.0) || !(t < INFINITY)) return 0; /* parallel to the plane, or the plane lies behind: the limits of
+                                                  lf_validate_light_geom keep t far from 0 for a ray leaving the lens */
+  const vec w = sub(add(P, scale(d, t)), C);
+  const double g11 = dotp(e1, e1), g12 = dotp(e1, e2), g22 = dotp(e2, e2), b1 = dotp(w, e1), b2 = dotp(w, e2);
+  const double det = g11 * g22 - g12 * g12; /* = |e1 x e2|^2 */
+  const double u = (g22 * b1 - g12 * b2) / det, v = (g11 * b2 - g12 * b1) / det;
+  const int inside = fabs(u) <= 0.5 && fabs(v) <= 0.5;
+  /* one unit of u moves the point |e1 x e2| / |e2| mm away from the lines u = const, one of v |e1 x e2| / |e1| */
+  const double mm_u = sqrt(det / g22), mm_v = sqrt(det / g11);
+  const double eps = G64_EPS_EXIT + t * G64_EPS_DIR + G64_EPS_TEST * sqrt(dotp(sub(P, C), sub(P, C)));
+  const double du = (fabs(u) - 0.5) * mm_u, dv = (fabs(v) - 0.5) * mm_v; /* signed: > 0 outside */
+  const int near_edge = (fabs(du) < eps && dv < eps) || (fabs(dv) < eps && du < eps);
+  if (fabs(facing) < eps_cos) { *edge = inside || near_edge; return inside && facing < 0.0; }
+  if (!(facing < 0.0)) return 0; /* seen from behind: black, and firmly so */
+  *edge = near_edge;
+  return inside;
+}
+
 /* image, frag: W*H*3 doubles (rows [y0, y1) are written); counters: launched, events, clipped at
- * the stop, vignetted, totally reflected, reached the scene, hit the light, fragile rays */
+ * the stop, vignetted, totally reflected, reached the scene, hit the light ((ray, light) pairs under a list),
+ * fragile rays.  The array a caller passes keeps its EIGHT slots -- a binding written before the light list existed
+ * allocates no more -- and the ninth counter, the (ray, light) pairs whose lit-or-unlit decision lies in a rectangle's
+ * edge band, is read with g64_light_edge_pairs() after the call. */
+static uint64_t g64_edge_pairs_last = 0;
+uint64_t g64_light_edge_pairs(void) { return g64_edge_pairs_last; }
 void g64_trace(const g64_lens* L, int W, int H, int y0, int y1, int spp, const uint32_t key[2],
                int sub_bits, const int* pairs, int n_pairs, const float* mask, int mw, int mh,
                double* image, double* frag, uint64_t counters[8], int n_threads) {
@@ -505,7 +598,17 @@ void g64_trace(const g64_lens* L, int W, int H, int y0, int y1, int spp, const u
   lay_out(L, &S);
   const double lobe = 1.0 / (1.0 - cos(L->sun_angular_radius));
   const vec sun = normalise(V(L->sun_dir[0], L->sun_dir[1], L->sun_dir[2])); /* the angle is between directions */
-  uint64_t total[8] = {0};
+  /* the list's directional lights and lobes, formed as the sun's are */
+  const int n_lights = g64_n_lights;
+  vec to_light[G64_MAX_LIGHTS];
+  double lobe_of[G64_MAX_LIGHTS];
+  for (int k = 0; k < n_lights; k++) {
+    to_light[k] = normalise(V(g64_light_geom[k][0], g64_light_geom[k][1], g64_light_geom[k][2]));
+    lobe_of[k] = 1.0 / (1.0 - cos(g64_light_alpha[k]));
+  }
+  uint64_t total[9] = {0};
+  memset(g64_pairs_lit, 0, sizeof(g64_pairs_lit));
+  memset(g64_pairs_edge, 0, sizeof(g64_pairs_edge));
   if (n_threads < 1) n_threads = 1;
   int G = (int)floor(sqrt((double)spp));
   while ((G + 1) * (G + 1) <= spp) G++;
@@ -513,7 +616,7 @@ void g64_trace(const g64_lens* L, int W, int H, int y0, int y1, int spp, const u
   const int GG = G * G;
 #pragma omp parallel num_threads(n_threads)
   {
-    uint64_t counted[8] = {0}, skipped[8] = {0};
+    uint64_t counted[9] = {0}, skipped[9] = {0}, lit_k[G64_MAX_LIGHTS] = {0}, edge_k[G64_MAX_LIGHTS] = {0};
 #pragma omp for schedule(dynamic, 16)
     for (long long p = (long long)y0 * W; p < (long long)y1 * W; p++) {
       const int x = (int)(p % W), y = (int)(p / W);
@@ -558,6 +661,40 @@ void g64_trace(const g64_lens* L, int W, int H, int y0, int y1, int spp, const u
             else if (r.dead == 3) c[4]++;
             else c[5]++;
             if (r.dead && !r.fragile) continue;
+            if (n_lights > 0) {
+              /* the list: every light tests the ray at its own exit point r.o along r.d; contributions add */
+              const vec dn = normalise(r.d);
+              for (int k = 0; k < n_lights; k++) {
+                double shade = 1.0; /* a fragile ray that could not be followed: bound by its weight, for every light */
+                int edge = 0, in = 1;
+                if (r.fragile != 2) {
+                  if (g64_light_kind[k] == G64_AREA) {
+                    in = area_lit(g64_light_geom[k], r.o, dn, L->eps_cos, &edge);
+                    if (!in && !edge) continue;
+                  } else {
+                    const vec s = g64_light_kind[k] == G64_POINT
+                                      ? normalise(sub(V(g64_light_geom[k][0], g64_light_geom[k][1], g64_light_geom[k][2]), r.o))
+                                      : to_light[k];
+                    const double qq = (1.0 - dotp(dn, s)) * lobe_of[k];
+                    if (!(qq < 1.0)) continue;
+                    shade = (1.0 - qq) * (1.0 - qq);
+                  }
+                }
+                if (!r.dead && in && r.w * shade > 0.0) { c[6]++; if (c == counted) lit_k[k]++; }
+                if (!r.dead && edge && r.w > 0.0) { c[8]++; if (c == counted) edge_k[k]++; }
+                for (int ch = 0; ch < 3; ch++) {
+                  const double colour = g64_light_rad[k][ch] * L->lambda_rgb[lam][ch];
+                  if (!r.dead && in) sum[ch] += r.w * shade * colour;
+                  if (r.fragile) fsum[ch] += r.w_pot * shade * colour;
+                  else if (edge) fsum[ch] += r.w * colour; /* whichever way float64 decided */
+                  if (r.slope > 0.0) fsum[ch] += r.slope * shade * colour;
+                  if (r.fragile && g64_cause)
+                    for (int b = 0; b < 4; b++)
+                      if (r.cause & (1 << b)) g64_cause[4 * (size_t)p + b] += r.w_pot * shade * colour / spp;
+                }
+              }
+              continue;
+            }
             double shade = 1.0; /* a fragile ray that could not be followed: bound by its weight */
             if (r.fragile != 2) {
               const double qq = (1.0 - dotp(normalise(r.d), sun)) * lobe;
@@ -583,9 +720,57 @@ void g64_trace(const g64_lens* L, int W, int H, int y0, int y1, int spp, const u
       }
     }
 #pragma omp critical
-    for (int k = 0; k < 8; k++) total[k] += counted[k];
+    {
+      for (int k = 0; k < 9; k++) total[k] += counted[k];
+      for (int k = 0; k < G64_MAX_LIGHTS; k++) { g64_pairs_lit[k] += lit_k[k]; g64_pairs_edge[k] += edge_k[k]; }
+    }
   }
-  if (counters) memcpy(counters, total, sizeof(total));
+  if (counters) memcpy(counters, total, 8 * sizeof(total[0]));
+  g64_edge_pairs_last = total[8];
+}
+
+/* How far a float32 march's exit ray lies from this tracer's (what G64_EPS_EXIT / G64_EPS_DIR are measured with).
+ * The sample rays of a W x H x spp frame, each start ray rounded to float32 and handed both to `f32` -- the float32
+ * oracle's single-ray entry (geo_trace_ray of lf_geo_oracle.c, passed in by the caller with its own lens record:
+ * nothing here links against it) -- and to follow(), along every listed path and wavelength.  Rays this tracer flags
+ * fragile are skipped, and so are rays either side loses.  out = {largest |delta exit point| (mm, max norm), largest
+ * |delta unit exit direction| (max norm), rays compared, rays whose fates differ although not fragile} */
+typedef int (*g64_f32_ray_fn)(const void* L32, int lam, int i, int j, float p[3], float d[3], float* w, const float* mask,
+                              int mw, int mh, int* n_events);
+void g64_exit_deviation(const g64_lens* L, const void* L32, g64_f32_ray_fn f32, int W, int H, int spp, const uint32_t key[2],
+                        int sub_bits, const int* pairs, int n_pairs, const float* mask, int mw, int mh, int n_threads,
+                        double out[4]) {
+  g64_system S;
+  lay_out(L, &S);
+  double worst_p = 0.0, worst_d = 0.0, n_cmp = 0.0, n_fate = 0.0;
+  if (n_threads < 1) n_threads = 1;
+#pragma omp parallel for schedule(dynamic, 16) num_threads(n_threads) reduction(max : worst_p, worst_d) reduction(+ : n_cmp, n_fate)
+  for (long long p = 0; p < (long long)H * W; p++) {
+    const int x = (int)(p % W), y = (int)(p / W);
+    for (int s = 0; s < spp; s++) {
+      vec o, d;
+      sample_ray(L, &S, W, H, x, y, s, spp, sub_bits, key, &o, &d);
+      const float o32[3] = {(float)o.x, (float)o.y, (float)o.z}, d32[3] = {(float)d.x, (float)d.y, (float)d.z};
+      for (int lam = 0; lam < L->n_lambda; lam++)
+        for (int q = 0; q < n_pairs; q++) {
+          g64_ray r = {V(o32[0], o32[1], o32[2]), V(d32[0], d32[1], d32[2]), 1.0, 1.0, 0, 0, 0};
+          follow(L, &S, lam, pairs[2 * q], pairs[2 * q + 1], mask, mw, mh, &r);
+          if (r.fragile) continue;
+          float pf[3] = {o32[0], o32[1], o32[2]}, df[3] = {d32[0], d32[1], d32[2]}, wf = 1.0f;
+          int ev;
+          const int st = f32(L32, lam, pairs[2 * q], pairs[2 * q + 1], pf, df, &wf, mask, mw, mh, &ev);
+          if ((st != 0) != (r.dead != 0)) { n_fate += 1.0; continue; }
+          if (st != 0) continue;
+          const vec d64 = normalise(r.d), d32n = normalise(V(df[0], df[1], df[2]));
+          const double ep = fmax(fabs(pf[0] - r.o.x), fmax(fabs(pf[1] - r.o.y), fabs(pf[2] - r.o.z)));
+          const double ed = fmax(fabs(d32n.x - d64.x), fmax(fabs(d32n.y - d64.y), fabs(d32n.z - d64.z)));
+          if (ep > worst_p) worst_p = ep;
+          if (ed > worst_d) worst_d = ed;
+          n_cmp += 1.0;
+        }
+    }
+  }
+  out[0] = worst_p; out[1] = worst_d; out[2] = n_cmp; out[3] = n_fate;
 }
 
 /* The lens camera of the scene term (lf_set_lens_camera): the primary path of sample s = 0 .. ns-1 of the

@@ -667,21 +667,25 @@ def g64_lens(lens, sun_dir=(0, 0, -1), sun_radiance=(1, 1, 1), sun_angular_radiu
 
 
 G64_COUNTERS = ("rays_launched", "surface_events", "rays_clipped_stop", "rays_vignetted", "rays_tir",
-                "rays_reached_scene", "rays_hit_light", "rays_fragile")
+                "rays_reached_scene", "rays_hit_light", "rays_fragile", "light_edge_pairs")
 
 
 g64_last_causes = None
+g64_last_light_pairs = None      # per light of the last g64_trace(lights=...): (lit (ray, light) pairs, those in its edge band)
 G64_CAUSES = ("aperture_rim", "mask_texel_edge", "critical_angle", "grazing_miss")
 
 
 def g64_trace(lens, W, H, y0, y1, spp, key, pairs, include_primary, mask, sun_dir, sun_radiance,
-              sun_angular_radius, n_threads=8, lambda_rgb=None, sub_bits=6, cull=None, causes=False, **eps):
+              sun_angular_radius, n_threads=8, lambda_rgb=None, sub_bits=6, cull=None, causes=False, lights=None, **eps):
     """-> (image, frag, counters): image / frag are H x W x 3; a faithful float32 evaluation of the
     same estimator satisfies |pixel32 - image| <= tol * image + frag (see lf_geo_f64.c).  cull: a table from
     LensFlare.cull_table() -- the image stays the full enumeration's, the counters count the rays the device starts.
     causes=True: g64_last_causes = H x W x 4, the fragile weight per pixel (summed over the channels) by cause --
-    aperture rim, mask texel edge, critical angle, grazing miss of a sphere."""
-    global g64_last_causes
+    aperture rim, mask texel edge, critical angle, grazing miss of a sphere.
+    lights: a list of (kind, geom12 -- or its first three floats --, radiance, angular_radius) as LensFlare.lights_geom()
+    reports them (g64_set_lights, cleared again afterwards); the sun_* arguments are then ignored.  rays_hit_light
+    counts (ray, light) pairs, light_edge_pairs those in the edge band of a rectangle."""
+    global g64_last_causes, g64_last_light_pairs
     L = g64_lens(lens, sun_dir, sun_radiance, sun_angular_radius, lambda_rgb, **eps)
     table = _device_cull(cull, W, H, spp) if cull is not None else None
     if pairs is None:
@@ -694,7 +698,7 @@ def g64_trace(lens, W, H, y0, y1, spp, key, pairs, include_primary, mask, sun_di
     mask = np.ascontiguousarray(mask, np.float32)
     image = np.zeros((H, W, 3), np.float64)
     frag = np.zeros((H, W, 3), np.float64)
-    cnt = (C.c_uint64 * 8)()
+    cnt = (C.c_uint64 * 8)()      # (the C call fills eight; the ninth, light_edge_pairs, has its own getter)
     k = (C.c_uint32 * 2)(key & 0xffffffff, (key >> 32) & 0xffffffff)
     if table is not None:
         table, block_px = table
@@ -702,13 +706,71 @@ def g64_trace(lens, W, H, y0, y1, spp, key, pairs, include_primary, mask, sun_di
     g64_last_causes = np.zeros((H, W, 4), np.float64) if causes else None
     lib().g64_set_cause_buffer(_p(g64_last_causes, C.c_double) if causes else None)
     try:
+        if lights is not None:
+            g64_set_lights(lights)
         lib().g64_trace(C.byref(L), W, H, y0, y1, spp, k, int(sub_bits), _p(pairs, C.c_int), len(pairs),
                         _p(mask, C.c_float), mask.shape[1], mask.shape[0], _p(image, C.c_double),
                         _p(frag, C.c_double), cnt, n_threads)
     finally:
         lib().g64_set_cull(None, 0, 0, 0, 64)
         lib().g64_set_cause_buffer(None)
-    return image, frag, dict(zip(G64_COUNTERS, (int(v) for v in cnt)))
+        if lights is not None:
+            g64_set_lights(None)
+    g64_last_light_pairs = None
+    if lights is not None:
+        lit_k, edge_k = (C.c_uint64 * 8)(), (C.c_uint64 * 8)()
+        lib().g64_light_pairs(lit_k, edge_k)
+        g64_last_light_pairs = [(int(lit_k[i]), int(edge_k[i])) for i in range(len(lights))]
+    lib().g64_light_edge_pairs.restype = C.c_uint64
+    return image, frag, dict(zip(G64_COUNTERS, [int(v) for v in cnt] + [int(lib().g64_light_edge_pairs())]))
+
+
+def g64_set_lights(lights=None):
+    """The float64 tracer's light list: (kind, geom, radiance, angular_radius) per light -- kind 0 directional (geom: the
+    direction to it), 1 point (its position, lens millimetres), 2 area (centre, direction, e1, e2) -- every number
+    rounded through float32, as the device stores it (feed it LensFlare.lights_geom()); None or [] restores the single
+    sun of the sun_* arguments.  A process-global setting: use it in try ... finally (g64_trace(lights=...) does)."""
+    if not lights:
+        lib().g64_set_lights(0, None, None, None, None)
+        return
+    n = len(lights)
+    kinds = np.ascontiguousarray([int(l[0]) for l in lights], np.int32)
+    geom = np.zeros((n, 12), np.float64)
+    for i, l in enumerate(lights):
+        g = np.asarray(l[1], np.float32).ravel()
+        geom[i, :len(g)] = g
+    rad = np.ascontiguousarray(np.asarray([l[2] for l in lights], np.float32).reshape(n, 3), np.float64)
+    alpha = np.ascontiguousarray(np.asarray([l[3] for l in lights], np.float32).reshape(n), np.float64)
+    assert n <= 8 and set(kinds.tolist()) <= {0, 1, 2}
+    lib().g64_set_lights(n, _p(kinds, C.c_int), _p(geom, C.c_double), _p(rad, C.c_double), _p(alpha, C.c_double))
+
+
+def lights_of(ctx):
+    """LensFlare.lights_geom() -- (kinds, geoms, radiances, angular radii) -- as the list g64_trace(lights=...) takes"""
+    kinds, geoms, rads, ars = ctx.lights_geom()
+    return [(int(k), np.array(g), np.array(r), float(a)) for k, g, r, a in zip(kinds, geoms, rads, ars)]
+
+
+def g64_light_eps():
+    """(eps_exit mm, eps_dir, eps_test): the terms of a rectangle's edge band, eps_exit + t eps_dir + eps_test |P - C|"""
+    out = (C.c_double * 3)()
+    lib().g64_light_eps(out)
+    return tuple(out)
+
+
+def g64_exit_deviation(lens, W, H, spp, key, mask, pairs=None, sub_bits=6, n_threads=8, **eps):
+    """The float32 oracle's exit ray (geo_trace_ray) against the float64 tracer's over the tracer's own sample rays of a
+    W x H x spp frame, the primary path and every pair (default), every wavelength; fragile rays skipped.
+    -> (largest |delta exit point| mm, largest |delta unit direction|, rays compared, non-fragile rays whose fates differ)"""
+    L, L32 = g64_lens(lens, **eps), geo_lens(lens)
+    pairs = np.ascontiguousarray(all_pairs(lens, True) if pairs is None else pairs, np.int32).reshape(-1, 2)
+    mask = np.ascontiguousarray(mask, np.float32)
+    k = (C.c_uint32 * 2)(key & 0xffffffff, (key >> 32) & 0xffffffff)
+    out = (C.c_double * 4)()
+    lib().g64_exit_deviation(C.byref(L), C.byref(L32), C.cast(lib().geo_trace_ray, C.c_void_p), int(W), int(H), int(spp), k,
+                             int(sub_bits), _p(pairs, C.c_int), len(pairs), _p(mask, C.c_float), mask.shape[1], mask.shape[0],
+                             int(n_threads), out)
+    return out[0], out[1], int(out[2]), int(out[3])
 
 
 def g64_glass_event(lens_struct, lam, k, mirror, p, d, w=1.0):

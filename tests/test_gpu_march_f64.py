@@ -48,7 +48,9 @@ def _gpu_frame(pkg, lf, lens, W, H, spp, key, mask, sun, rad, alpha, sub_bits=No
     return img, cnt
 
 
-def _check_against_f64(img, cnt, ref, frag, c64, min_lit, median_bar=2e-6, culled=False):
+def _check_against_f64(img, cnt, ref, frag, c64, min_lit, median_bar=2e-6, culled=False, hit_light_slack=0):
+    """hit_light_slack: (ray, light) pairs whose lit-or-unlit decision the tracer calls undecidable at float32 accuracy beside the
+    fragile rays -- the edge band of a rectangle (light_edge_pairs, tests/test_gpu_lights_f64.py) -- allowed on rays_hit_light only"""
     assert c64["rays_launched"] == cnt["rays_launched"]
     lit = ref >= FLOOR
     assert lit.sum() >= min_lit, "the test frame must have converged pixels above the floor"
@@ -84,7 +86,7 @@ def _check_against_f64(img, cnt, ref, frag, c64, min_lit, median_bar=2e-6, culle
     # that pass near an edge of something, so there they are a larger part of what is counted: 1.3 % on the c3 band)
     assert n_frag < (5e-2 if culled else 1e-2) * c64["rays_launched"]
     for name in ("rays_clipped_stop", "rays_vignetted", "rays_tir", "rays_reached_scene", "rays_hit_light"):
-        assert abs(c64[name] - cnt[name]) <= n_frag, (name, c64[name], cnt[name])
+        assert abs(c64[name] - cnt[name]) <= n_frag + (hit_light_slack if name == "rays_hit_light" else 0), (name, c64[name], cnt[name])
     assert abs(c64["surface_events"] - cnt["surface_events"]) <= 30 * n_frag
     return rel
 
