@@ -43,6 +43,7 @@ ABI_SYMBOLS = [
     "lf_ghost_shadow_reach_geom", "lf_area_light_cull_cone", "lf_set_lights_from_scene_ex",
     "lf_set_ghost_occlusion", "lf_get_ghost_occlusion", "lf_get_ghost_occlusion_stats", "lf_ghost_ray_visibility",
     "lf_set_ghost_occlusion_reach", "lf_get_ghost_occlusion_reach", "lf_ghost_shadow_reach", "lf_ghost_ray_light_visibility",
+    "lf_set_flare_occlusion", "lf_get_flare_occlusion", "lf_get_flare_visibility", "lf_flare_shadow_samples", "lf_flare_shadow_rays",
     "lf_set_sun_from_flares", "lf_paraxial_efl", "lf_paraxial_image_scale", "lf_set_ghost_pairs", "lf_set_pupil_subcells", "lf_set_tile_stride", "lf_trace_ghosts", "lf_set_march_culling", "lf_get_cull_info", "lf_get_cull_table", "lf_get_cull_started_fraction", "lf_get_cull_reason", "lf_set_cull_audit", "lf_get_cull_audit", "lf_test_knob", "lf_comm_share_cull", "lf_set_cull_share", "lf_cull_prepare", "lf_cull_table_view", "lf_cull_commit", "lf_get_march_fix_bits", "lf_generate_lens_rays", "lf_get_counters", "lf_reset_counters", "lf_get_executed_events", "lf_get_march_stats", "lf_native_sqrt", "lf_native_rcp", "lf_set_starburst_spectrum", "lf_load_collada", "lf_march_tables",
     "lf_timing_enable", "lf_timing_reset", "lf_timing_get",
     "lf_clear_ghost_buffer", "lf_draw_ghost", "lf_rasterize_textured_triangle", "lf_fill_textured_pixel",
@@ -344,6 +345,58 @@ def ghost_shadow_reach(kind, vec, rays, world_per_mm):
         if st != 0:
             raise LensFlareError(st, "lf_ghost_shadow_reach")
         out[i] = t.value
+    return out
+
+
+# where the shadow rays of flare occlusion start (lf_set_flare_occlusion): at the camera position, or on the front element's
+# vertex plane in lens millimetres (needs a lens and the scale world_per_mm)
+FLARE_ORIGIN_CAMERA, FLARE_ORIGIN_FRONT_ELEMENT = 0, 1
+MAX_FLARES = 8   # LF_MAX_FLARES
+
+
+def _flare_occlusion_args(who, rays_per_light, angular_radius, origin, world_per_mm=None):
+    """the setter's validation, before anything reaches the library"""
+    R = rays_per_light
+    if isinstance(R, bool) or not isinstance(R, (int, np.integer)) or not 64 <= int(R) <= 4096 or int(R) % 64:
+        raise ValueError(f"{who}: rays_per_light must be a multiple of 64 in [64, 4096]")
+    a = float(angular_radius)
+    if not (np.isfinite(a) and 0.0 <= a <= 0.5):
+        raise ValueError(f"{who}: angular_radius must be finite and in [0, 0.5]")
+    if isinstance(origin, bool) or not isinstance(origin, (int, np.integer)) or int(origin) not in (FLARE_ORIGIN_CAMERA, FLARE_ORIGIN_FRONT_ELEMENT):
+        raise ValueError(f"{who}: origin must be FLARE_ORIGIN_CAMERA (0) or FLARE_ORIGIN_FRONT_ELEMENT (1)")
+    if world_per_mm is not None and int(origin) == FLARE_ORIGIN_FRONT_ELEMENT:
+        w = float(world_per_mm)
+        if not (w > 0.0 and np.isfinite(w)):
+            raise ValueError(f"{who}: world_per_mm must be > 0 and finite under FLARE_ORIGIN_FRONT_ELEMENT")
+    return int(R), a, int(origin)
+
+
+def flare_shadow_samples(rays_per_light):
+    """R x 4 float32 (a, b, c, d): the point of the unit aperture disc and of the light's unit disc of each shadow ray
+    (lf_flare_shadow_samples, host only: the definition of the resident table)"""
+    R, _, _ = _flare_occlusion_args("flare_shadow_samples", rays_per_light, 0.0, FLARE_ORIGIN_CAMERA)
+    out = np.zeros((R, 4), np.float32)
+    st = load_library().lf_flare_shadow_samples(R, _fp(out, C.c_float))
+    if st != 0:
+        raise LensFlareError(st, "lf_flare_shadow_samples")
+    return out
+
+
+def flare_shadow_rays(rays_per_light, flare_origin, hfov_deg, vfov_deg, angular_radius, origin, front_semi_aperture=0.0):
+    """R x 6 float32 {origin xyz in lens mm, direction xyz}: the shadow rays of the flare stored at screen position
+    flare_origin (lf_flare_shadow_rays, host only: the definition the visibility kernel reproduces bit for bit)"""
+    R, a, origin = _flare_occlusion_args("flare_shadow_rays", rays_per_light, angular_radius, origin)
+    o = np.ascontiguousarray(flare_origin, np.float64).reshape(2)
+    if not np.isfinite(o).all() or not (0.0 < float(hfov_deg) < 180.0 and 0.0 < float(vfov_deg) < 180.0):
+        raise ValueError("flare_shadow_rays: the flare origin must be finite, the fields of view inside (0, 180)")
+    h0 = float(front_semi_aperture)
+    if origin == FLARE_ORIGIN_FRONT_ELEMENT and not (h0 > 0.0 and np.isfinite(h0)):
+        raise ValueError("flare_shadow_rays: front_semi_aperture must be > 0 under FLARE_ORIGIN_FRONT_ELEMENT")
+    out = np.zeros((R, 6), np.float32)
+    st = load_library().lf_flare_shadow_rays(R, _fp(o, C.c_double), C.c_double(float(hfov_deg)), C.c_double(float(vfov_deg)),
+                                             C.c_float(a), origin, C.c_float(h0), _fp(out, C.c_float))
+    if st != 0:
+        raise LensFlareError(st, "lf_flare_shadow_rays")
     return out
 
 
@@ -1090,6 +1143,32 @@ class LensFlare:
         self._ck(self.lib.lf_ghost_ray_visibility(self.ctx, C.c_size_t(len(r)), _fp(r, C.c_float),
                                                   vis.ctypes.data_as(C.POINTER(C.c_ubyte))))
         return vis.astype(bool)
+
+    # ---- flare occlusion (lf_set_flare_occlusion): the starburst, the falloff and the paraxial quads of a blocked light
+    def set_flare_occlusion(self, on=True, rays_per_light=1024, angular_radius=0.00465, origin=FLARE_ORIGIN_CAMERA,
+                            world_per_mm=0.001):
+        """On: render_flare_layer, irradiance_falloff and generate_ghost_buffer scale each flare by the fraction of its
+        rays_per_light shadow rays (over the light's disc of angular_radius, from the camera position or over the front
+        element) that the resident scene does not block.  Off (the default): the launches are the ones they always were.
+        While on, those calls need set_camera and a scene (and a lens under FLARE_ORIGIN_FRONT_ELEMENT)."""
+        if not bool(on):
+            self._ck(self.lib.lf_set_flare_occlusion(self.ctx, 0, 0, C.c_float(0.0), 0, C.c_double(0.0)))
+            return
+        R, a, origin = _flare_occlusion_args("set_flare_occlusion", rays_per_light, angular_radius, origin, world_per_mm)
+        self._ck(self.lib.lf_set_flare_occlusion(self.ctx, 1, R, C.c_float(a), origin, C.c_double(float(world_per_mm))))
+
+    def get_flare_occlusion(self):
+        """dict(on, rays_per_light, angular_radius, origin, world_per_mm)"""
+        on, R, a, o, w = C.c_int(0), C.c_int(0), C.c_float(0.0), C.c_int(0), C.c_double(0.0)
+        self._ck(self.lib.lf_get_flare_occlusion(self.ctx, C.byref(on), C.byref(R), C.byref(a), C.byref(o), C.byref(w)))
+        return dict(on=bool(on.value), rays_per_light=R.value, angular_radius=a.value, origin=o.value, world_per_mm=w.value)
+
+    def flare_visibility(self):
+        """dict(n, visibility float64[n], visible_rays uint64[n]) of the flare state installed, computed now"""
+        n = C.c_int(0)
+        vis, cnt = np.zeros(MAX_FLARES, np.float64), np.zeros(MAX_FLARES, np.uint64)
+        self._ck(self.lib.lf_get_flare_visibility(self.ctx, C.byref(n), _fp(vis, C.c_double), _fp(cnt, C.c_uint64)))
+        return dict(n=n.value, visibility=vis[:n.value].copy(), visible_rays=cnt[:n.value].copy())
 
     def set_ghost_occlusion_reach(self, reach):
         """Where the shadow ray of a POINT light ends: OCCLUSION_REACH_SKY (the default: the ray runs on to the sky, and occlusion

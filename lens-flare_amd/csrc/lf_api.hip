@@ -74,7 +74,7 @@ namespace {
 
 const char* kKernelNames[LFK_COUNT] = {"march", "flare_layer", "ghost_raster", "dft",
                                        "frame_setup", "tonemap", "exchange", "scene_term", "cull_prepass", "cull_audit",
-                                       "cull_cache_build"};
+                                       "cull_cache_build", "flare_visibility"};
 
 // the reference's hard-coded prescription (pathtracer.cpp:541-556); literals narrowed to float
 // where the reference narrows them
@@ -524,6 +524,7 @@ lf_status lf_destroy(lf_ctx* ctx) {
   if (ctx->comm_stage) (void)hipFree(ctx->comm_stage);
   free_frame_buffers(ctx);
   lf_cull_cache_free(ctx);
+  lf_flare_occlusion_free(ctx);
   for (auto& t : ctx->timed) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
   for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
   for (int s = 0; s < 2; s++) {
@@ -753,6 +754,7 @@ lf_status lf_find_sun_pos(lf_ctx* ctx, const double* lights, int n_lights) {
     lf_status st = lfk_frame_setup(ctx, nullptr, ctx->sun_lights_dev, n_lights, true);
     if (st != LF_OK) return st;
   }
+  ctx->flares_n_host = -1;   // (counted by the kernel)
   ctx->flares_valid = true;
   ctx->ghost_valid = false;
   return LF_OK;
@@ -774,6 +776,7 @@ lf_status lf_set_flares(lf_ctx* ctx, int n, const double* origins, const double*
   f.axis_ray[0] = axis_ray[0]; f.axis_ray[1] = axis_ray[1];
   LF_HIP(ctx, hipMemcpyAsync(ctx->flares, &f, sizeof(f), hipMemcpyHostToDevice, ctx->stream));
   LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  ctx->flares_n_host = n;
   ctx->flares_valid = true;
   ctx->ghost_valid = false;
   return LF_OK;
@@ -875,7 +878,10 @@ lf_status lf_generate_ghost_buffer(lf_ctx* ctx) {
   LF_HIP(ctx, hipSetDevice(ctx->device));
   lf_status st;
   if ((st = lfk_frame_setup(ctx, nullptr, nullptr, 0, false)) != LF_OK) return st;
-  if ((st = lfk_ghost_raster(ctx)) != LF_OK) return st;
+  // (lf_set_flare_occlusion: the quads' colours times the visibility of the flare that supplied axis_ray; off: the list itself)
+  const LfGhostList* gl = nullptr;
+  if ((st = lf_flare_occlusion_update(ctx, "lf_generate_ghost_buffer", nullptr, &gl)) != LF_OK) return st;
+  if ((st = lfk_ghost_raster(ctx, gl)) != LF_OK) return st;
   ctx->ghost_valid = true;
   return LF_OK;
 }
@@ -890,7 +896,10 @@ lf_status lf_render_flare_layer(lf_ctx* ctx) {
     return lf_fail(ctx, LF_ERR_STATE, "MT19937 jitter selected but no table (frame was resized?)");
   LF_HIP(ctx, hipSetDevice(ctx->device));
   lf_status st;
-  if ((st = lfk_flare_layer(ctx)) != LF_OK) return st;
+  // (lf_set_flare_occlusion: the effective flare record, radiance times visibility; off: the installed one)
+  const LfFlares* fl = nullptr;
+  if ((st = lf_flare_occlusion_update(ctx, "lf_render_flare_layer", &fl, nullptr)) != LF_OK) return st;
+  if ((st = lfk_flare_layer(ctx, fl)) != LF_OK) return st;
   ctx->sample_valid = true;
   ctx->rgba_y0 = ctx->rgba_y1 = 0;  // the tonemapped copy is stale
   return LF_OK;
@@ -2133,7 +2142,10 @@ lf_status lf_irradiance_falloff(lf_ctx* ctx, int x, int y, double radius, double
   if (ctx->jitter_mode == 0 && !ctx->jitter_table_valid)
     return lf_fail(ctx, LF_ERR_STATE, "MT19937 jitter selected but no table (frame was resized?)");
   LF_HIP(ctx, hipSetDevice(ctx->device));
-  return lfk_irradiance_falloff(ctx, x, y, radius, rgb);
+  const LfFlares* fl = nullptr;
+  const lf_status st = lf_flare_occlusion_update(ctx, "lf_irradiance_falloff", &fl, nullptr);
+  if (st != LF_OK) return st;
+  return lfk_irradiance_falloff(ctx, x, y, radius, rgb, fl);
 }
 
 // ---------------------------------------------------------------- stop-mask filter --------------

@@ -710,12 +710,13 @@ lf_status lfk_frame_setup(lf_ctx* ctx, const LfSunLightArgs* lights_arg, const d
   return LF_OK;
 }
 
-lf_status lfk_ghost_raster(lf_ctx* ctx) {
+lf_status lfk_ghost_raster(lf_ctx* ctx, const LfGhostList* gl) {
+  if (!gl) gl = ctx->ghosts;
   if (ctx->y1 <= ctx->y0) return LF_OK;  // empty band
   const LfApertureDev& g = ctx->ap[LF_APERTURE_GHOST];
   dim3 grid((ctx->W + kTileW - 1) / kTileW, (ctx->y1 - ctx->y0 + kTileH - 1) / kTileH);
   hipEvent_t ev = lf_timing_begin(ctx, LFK_GHOST_RASTER);
-  hipLaunchKernelGGL(k_ghost_raster, grid, dim3(256), 0, ctx->stream, ctx->ghosts, g.texels, g.w,
+  hipLaunchKernelGGL(k_ghost_raster, grid, dim3(256), 0, ctx->stream, gl, g.texels, g.w,
                      g.h, ctx->W, ctx->y0, ctx->y1, 0, ctx->ghost);
   lf_timing_end(ctx, LFK_GHOST_RASTER, ev);
   LF_HIP(ctx, hipGetLastError());
@@ -798,24 +799,26 @@ lf_status lfk_compute_phase(lf_ctx* ctx, int flare, double u, double v, double o
   });
 }
 
-lf_status lfk_irradiance_falloff(lf_ctx* ctx, int x, int y, double radius, double out[3]) {
+lf_status lfk_irradiance_falloff(lf_ctx* ctx, int x, int y, double radius, double out[3], const LfFlares* fl) {
+  if (!fl) fl = ctx->flares;
   return probe_doubles(ctx, 3, out, [&](double* d) {
     if (lf_flare_exact(ctx))
-      hipLaunchKernelGGL(k_one_falloff<true>, dim3(1), dim3(64), 0, ctx->stream, ctx->flares, x, y, radius, ctx->W,
+      hipLaunchKernelGGL(k_one_falloff<true>, dim3(1), dim3(64), 0, ctx->stream, fl, x, y, radius, ctx->W,
                          ctx->H, ctx->jitter_raw, ctx->jitter_mode, ctx->jitter_key, d);
     else
-      hipLaunchKernelGGL(k_one_falloff<false>, dim3(1), dim3(64), 0, ctx->stream, ctx->flares, x, y, radius, ctx->W,
+      hipLaunchKernelGGL(k_one_falloff<false>, dim3(1), dim3(64), 0, ctx->stream, fl, x, y, radius, ctx->W,
                          ctx->H, ctx->jitter_raw, ctx->jitter_mode, ctx->jitter_key, d);
   });
 }
 
-lf_status lfk_flare_layer(lf_ctx* ctx) {
+lf_status lfk_flare_layer(lf_ctx* ctx, const LfFlares* fl) {
+  if (!fl) fl = ctx->flares;
   size_t n = (size_t)(ctx->y1 - ctx->y0) * ctx->W;
   if (n == 0) return LF_OK;  // empty band: nothing to render (a 0-block launch is an error)
   hipEvent_t ev = lf_timing_begin(ctx, LFK_FLARE_LAYER);
 #define LF_LAUNCH_FLARE(EXACT)                                                                      \
   hipLaunchKernelGGL(k_flare_layer<EXACT>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, \
-                     ctx->flares, ctx->ap[LF_APERTURE_STARBURST].stats, ctx->spectrum, ctx->ghost,     \
+                     fl, ctx->ap[LF_APERTURE_STARBURST].stats, ctx->spectrum, ctx->ghost,              \
                      ctx->scene, ctx->jitter_raw, ctx->jitter_mode, ctx->jitter_key, ctx->W, ctx->H,   \
                      ctx->y0, ctx->y1, lf_deal_of(ctx), ctx->ns_aa, ctx->flare_radius,                   \
                      ctx->flare_intensity, ctx->star_spec, ctx->sample, ctx->star)

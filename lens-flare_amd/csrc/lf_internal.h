@@ -50,6 +50,13 @@ struct LfGhostList {
   LfGhostTri tri[kMaxGhostTris];
 };
 
+// flare occlusion (lf_flare_occlusion.hip): per flare of the flare state the shadow rays that met nothing, and that count
+// over the rays per light
+struct LfFlareVisDev {
+  unsigned long long count[LF_MAX_FLARES];
+  double visibility[LF_MAX_FLARES];
+};
+
 // Paraxial prescription (globals of pathtracer.cpp:541-556 + constants of :619-633, :737)
 struct LfParaxialLens {
   int n, stop;
@@ -428,7 +435,7 @@ constexpr int kSceneCounters = 4;
 
 // ---- timing ---------------------------------------------------------------------------------
 enum LfKernelId { LFK_MARCH = 0, LFK_FLARE_LAYER, LFK_GHOST_RASTER, LFK_DFT, LFK_FRAME_SETUP,
-                  LFK_TONEMAP, LFK_EXCHANGE, LFK_SCENE, LFK_CULL, LFK_CULL_AUDIT, LFK_CULL_CACHE_BUILD, LFK_COUNT };
+                  LFK_TONEMAP, LFK_EXCHANGE, LFK_SCENE, LFK_CULL, LFK_CULL_AUDIT, LFK_CULL_CACHE_BUILD, LFK_FLARE_VIS, LFK_COUNT };
 
 struct LfTimedLaunch { int kernel; hipEvent_t start, stop; };
 
@@ -464,6 +471,17 @@ struct lf_ctx {
   LfGhostList* ghosts = nullptr;   // device
   LfParaxialLens* pl_dev = nullptr;
   bool flares_valid = false;
+  int flares_n_host = 0;           // n_flares of the device record as the host knows it; -1: counted on the device (lf_find_sun_pos)
+  // flare occlusion (lf_set_flare_occlusion, a setting of the context: nothing clears it; lf_flare_occlusion.hip)
+  bool flare_occl = false;
+  int flare_occl_rays = 0, flare_occl_origin = LF_FLARE_ORIGIN_CAMERA;
+  float flare_occl_alpha = 0.0f;
+  double flare_occl_wpm = 0.001;
+  float* flare_samples_dev = nullptr;      // 4 floats per ray (lf_flare_shadow_samples), resident per setting
+  int flare_samples_n = 0;                 // ... rays it holds
+  LfFlareVisDev* flare_vis_dev = nullptr;
+  LfFlares* flares_eff = nullptr;          // the EFFECTIVE flare record: radiance times visibility
+  LfGhostList* ghosts_eff = nullptr;       // ... and quad list: colours times the axis flare's visibility
   double* sun_lights_dev = nullptr;  // staging for more than kMaxSunLightArgs directional lights
   size_t sun_lights_cap = 0;
 
@@ -723,15 +741,20 @@ lf_status lfk_aperture_stats(lf_ctx* ctx, int slot);
 lf_status lfk_build_spectrum(lf_ctx* ctx);
 lf_status lfk_frame_setup(lf_ctx* ctx, const LfSunLightArgs* lights_arg, const double* lights_dev,
                           int n_lights, bool project);
-lf_status lfk_ghost_raster(lf_ctx* ctx);
+lf_status lfk_ghost_raster(lf_ctx* ctx, const LfGhostList* gl = nullptr);   // (gl, fl: null = the installed records)
 // single-shot forms of the reference's public helper members (lf_draw_ghost ... lf_irradiance_falloff)
 lf_status lfk_draw_ghost(lf_ctx* ctx, int channel, float r1, float r2, int bbox[4]);
 lf_status lfk_raster_triangle(lf_ctx* ctx, const float v[12], const double colour[3], int bbox[4]);
 lf_status lfk_fill_pixel(lf_ctx* ctx, const float v[12], int x, int y, const double colour[3]);
 lf_status lfk_shift_vertex(lf_ctx* ctx, float x, float y, float scale, float shift_amount, double out[2]);
 lf_status lfk_compute_phase(lf_ctx* ctx, int flare, double u, double v, double out[4]);
-lf_status lfk_irradiance_falloff(lf_ctx* ctx, int x, int y, double radius, double out[3]);
-lf_status lfk_flare_layer(lf_ctx* ctx);
+lf_status lfk_irradiance_falloff(lf_ctx* ctx, int x, int y, double radius, double out[3], const LfFlares* fl = nullptr);
+lf_status lfk_flare_layer(lf_ctx* ctx, const LfFlares* fl = nullptr);
+// lf_flare_occlusion.hip: the records a consuming call renders from -- the installed ones while lf_set_flare_occlusion is off
+// (nothing is launched), else the effective ones, behind the two visibility kernels on the context's stream (`who` names
+// the caller in the refusal, LF_ERR_STATE, of a state that lacks a camera, a scene or, for the front element's rays, a lens)
+lf_status lf_flare_occlusion_update(lf_ctx* ctx, const char* who, const LfFlares** fl, const LfGhostList** gl);
+void lf_flare_occlusion_free(lf_ctx* ctx);   // lf_destroy
 lf_status lfk_tonemap(lf_ctx* ctx, int ya, int yb);
 lf_status lfk_flip_rows(lf_ctx* ctx, uint32_t* out_dev);
 // lf_march.hip

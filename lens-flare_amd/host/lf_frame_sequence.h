@@ -45,7 +45,12 @@ typedef struct lf_frame_plan {
   float sun_angular_radius;
   int geo_spp;
   uint64_t geo_key;
-  int ghost_occlusion;            // 0 = off.  Else, with LF_FRAME_GHOSTS_MARCH: the scene hides the march's ghosts
+  int flare_occlusion;            // 0 = off.  Else the scene hides the starburst, the falloff and the paraxial quads of a blocked
+                                  // flare (lf_set_flare_occlusion with sun_angular_radius and world_per_mm: needs a camera and
+                                  // a resident scene) ...
+  int flare_occlusion_rays;       // ... with this many shadow rays per flare (a multiple of 64 in [64, 4096]) ...
+  int flare_occlusion_origin;     // ... from the camera position or over the front element (lf_flare_origin)
+  int ghost_occlusion;           // 0 = off.  Else, with LF_FRAME_GHOSTS_MARCH: the scene hides the march's ghosts
                                   // (lf_set_ghost_occlusion(1, world_per_mm): needs a camera and a resident scene)
 } lf_frame_plan;
 
@@ -69,6 +74,8 @@ static inline lf_status lf_run_frame(lf_ctx* ctx, const lf_frame_plan* p, const 
   if (p->scene == LF_FRAME_SCENE_DEVICE) LF_FRAME_STEP(lf_render_scene_term(ctx));
   else if (p->scene == LF_FRAME_SCENE_NONE) LF_FRAME_STEP(lf_set_scene_term(ctx, NULL));
   // generate_ghost_buffer (pathtracer.cpp:714-817)
+  LF_FRAME_STEP(lf_set_flare_occlusion(ctx, p->flare_occlusion ? 1 : 0, p->flare_occlusion_rays, p->sun_angular_radius,
+                                       p->flare_occlusion_origin, p->world_per_mm));
   LF_FRAME_STEP(lf_set_ghost_occlusion(ctx, (p->ghost_occlusion && p->ghosts == LF_FRAME_GHOSTS_MARCH) ? 1 : 0,
                                        p->world_per_mm));
   if (p->ghosts == LF_FRAME_GHOSTS_MARCH) {

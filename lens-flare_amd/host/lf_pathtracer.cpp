@@ -227,6 +227,14 @@ void PathTracer::use_ghost_occlusion_reach(int reach) {
   frame_ready_ = false;
 }
 
+void PathTracer::use_flare_occlusion(bool on, int rays) {
+  if (on && (rays < 64 || rays > 4096 || rays % 64 != 0))
+    throw std::runtime_error("use_flare_occlusion: rays must be a multiple of 64 in [64, 4096]");
+  flare_occlusion_ = on;
+  if (on) flare_occlusion_rays_ = rays;
+  frame_ready_ = false;
+}
+
 void PathTracer::set_scene(int n_spheres, const double* spheres, const int* sphere_material,
                            int n_triangles, const double* tri_positions, const double* tri_normals,
                            const int* tri_material, int n_materials, const double* materials,
@@ -258,7 +266,7 @@ void PathTracer::generate_ghost_buffer() {
   // (same place in the frame: main thread, before the workers start) and raytrace_pixel reads it.
   if (!camera) throw std::runtime_error("generate_ghost_buffer: camera not set");
   upload_textures();
-  if (ghost_occlusion_ || lights_from_scene_) {
+  if (ghost_occlusion_ || lights_from_scene_ || flare_occlusion_) {
     // the ghosts' shadow rays leave from -- and the scene's point lights are mapped through -- the camera's pose as it
     // stands at this frame (find_sun_pos may never have run)
     double pos[3] = {camera->pos.x, camera->pos.y, camera->pos.z};
@@ -295,6 +303,10 @@ void PathTracer::generate_ghost_buffer() {
   plan.lens_camera_mode = geometric_ ? lens_camera_mode : 0;
   plan.world_per_mm = lens_world_per_mm; plan.exposure = 0.0;
   plan.ghost_occlusion = ghost_occlusion_ ? 1 : 0;   // (use_ghost_occlusion; its scale is lens_world_per_mm)
+  // (use_flare_occlusion: over the front element once a lens is installed, else from the camera position)
+  plan.flare_occlusion = flare_occlusion_ ? 1 : 0;
+  plan.flare_occlusion_rays = flare_occlusion_rays_;
+  plan.flare_occlusion_origin = geometric_ ? LF_FLARE_ORIGIN_FRONT_ELEMENT : LF_FLARE_ORIGIN_CAMERA;
   if (plan.lens_camera_mode) plan.jitter = LF_FRAME_JITTER_COUNTER;   // the lens camera's samples are the march's
   if (scene_radiance) {
     // a scene term the HOST evaluates (est_radiance_global_illumination on the CPU, a callback): handed

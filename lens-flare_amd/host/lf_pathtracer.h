@@ -149,6 +149,12 @@ class PathTracer {
   // hidden by what stands between the lens and it, and by nothing behind it.  A setting of the context, installed at once
   // (lf_set_ghost_occlusion_reach): it does not travel in the frame's plan.
   void use_ghost_occlusion_reach(int reach);
+  // the scene hides the starburst, the falloff and the paraxial quads of a flare it blocks (lf_set_flare_occlusion at every
+  // generate_ghost_buffer: `rays` shadow rays per flare over a disc of the plan's angular radius -- use_lights_from_flares' /
+  // use_lights_from_scene's, 0.05 rad by default -- from the camera position, or over the front element once
+  // use_geometric_ghosts has installed a lens).  Independent of use_geometric_ghosts.  Needs a device scene (set_scene / load_collada) and the
+  // camera at the frame.  Off by default: the frames are those of a mirror without this call.
+  void use_flare_occlusion(bool on, int rays = 1024);
   // replaces PathTracer::bvh / scene (pathtracer.h:116-124): hand the static scene to the device
   // so that the sample loop of raytrace_pixel (BVH closest hit + direct lighting) runs there too;
   // argument layout as lf_set_scene (include/lensflare.h)
@@ -176,6 +182,8 @@ class PathTracer {
   int geo_spp_ = 0;
   bool lights_from_flares_ = false, lights_from_scene_ = false, area_lights_from_scene_ = false;
   bool ghost_occlusion_ = false;
+  bool flare_occlusion_ = false;
+  int flare_occlusion_rays_ = 1024;
   float lights_radius_ = 0.05f;
   std::vector<double> star_;    // host mirror of raytrace_starburst for every pixel
   std::vector<double> sample_;  // host mirror of the composed sensor buffer

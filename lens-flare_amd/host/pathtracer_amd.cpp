@@ -414,7 +414,8 @@ void PathTracer::generate_ghost_buffer() {                         // pathtracer
   }
   plan.scene = LF_FRAME_SCENE_DEVICE;
   plan.ghosts = LF_FRAME_GHOSTS_PARAXIAL;   // the reference's paraxial quads
-  plan.ghost_occlusion = 0;                 // the reference's ghosts know no occluder: the drop-in's frames stay the reference's
+  plan.flare_occlusion = 0;                 // ... nor do its starburst and quads
+  plan.ghost_occlusion = 0;                // the reference's ghosts know no occluder: the drop-in's frames stay the reference's
   if (!lens_file.empty()) {
     // the geometric march: every ghost pair of the prescription + the primary path, per sensor sample
     if (s.lens_loaded != lens_file || s.lens_w != W || s.lens_h != H) {

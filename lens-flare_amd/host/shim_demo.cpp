@@ -301,7 +301,85 @@ static int geolamp_main(int argc, char** argv) {
   return 0;
 }
 
+// shim_demo flarewall <aperture.f32> <aw> <ah> <ghost.f32> <gw> <gh> <W> <H> <hFov> <vFov> <flare ox oy> <outprefix>
+//                     <wall: 0 none, 1 hides the sun, 2 its left half> [rays per flare]
+// A wall in front of the sun, for the flare layer: the starburst, the falloff and the paraxial quads under
+// PathTracer::use_flare_occlusion (no prescription: the shadow rays leave from the camera position, over a disc of the
+// mirror's default angular radius, 0.05 rad).  One flare of radiance
+// (1, 0.9, 0.5) at the normalised screen position <ox oy>; the wall is geowall's, a 2 m x 2 m quad 5 m from the camera
+// (identity pose at the origin), square to the flare's direction and centred on it (1) or shifted so that its edge crosses
+// it (2).  Dumps the sample, ghost and starburst buffers and prints the flare's visibility.
+static int flarewall_main(int argc, char** argv) {
+  if (argc < 16) return 1;
+  const size_t aw = atoi(argv[3]), ah = atoi(argv[4]), gw = atoi(argv[6]), gh = atoi(argv[7]), W = atoi(argv[8]), H = atoi(argv[9]);
+  const double hfov = atof(argv[10]), vfov = atof(argv[11]), ox = atof(argv[12]), oy = atof(argv[13]);
+  const std::string out = argv[14];
+  const int wall = atoi(argv[15]), rays = argc > 16 ? atoi(argv[16]) : 1024;
+  try {
+    PathTracer pt(0);
+    Camera cam;
+    cam.hFov = hfov; cam.vFov = vfov;
+    CameraApertureTexture ap, gh_tex;
+    ap.init_from_texels(read_f32(argv[2], aw * ah).data(), aw, ah);
+    gh_tex.init_from_texels(read_f32(argv[5], gw * gh).data(), gw, gh);
+    cam.aperture_texture = &ap;
+    cam.ghost_aperture_texture = &gh_tex;
+    pt.clear();
+    pt.set_frame_size(W, H);
+    pt.camera = &cam;
+    pt.counter_jitter = true;
+    pt.flare_radiance.emplace_back(1.0, 0.9, 0.5);
+    pt.flare_origins.emplace_back(ox, oy);
+    pt.axis_ray = Vector2D(ox, oy);
+    pt.angle_to_sun = (float)std::atan(oy / ox);
+    // the flare's direction s from the camera, two unit vectors u, v square to it
+    const double PI_ = 3.14159265358979323;
+    double s[3] = {(2.0 * ox - 1.0) * std::tan(0.5 * hfov * PI_ / 180.0), (2.0 * oy - 1.0) * std::tan(0.5 * vfov * PI_ / 180.0), -1.0};
+    const double sl = std::sqrt(s[0] * s[0] + s[1] * s[1] + s[2] * s[2]);
+    for (int a = 0; a < 3; a++) s[a] /= sl;
+    double u[3] = {-s[2], 0.0, s[0]};
+    const double ul = std::sqrt(u[0] * u[0] + u[2] * u[2]);
+    u[0] /= ul; u[2] /= ul;
+    const double v[3] = {s[1] * u[2] - s[2] * u[1], s[2] * u[0] - s[0] * u[2], s[0] * u[1] - s[1] * u[0]};
+    const double mats[4] = {0.0, 0.5, 0.5, 0.5};                     // diffuse grey
+    if (wall) {
+      const double shift = wall == 2 ? -1.0 : 0.0, dist = 5.0;
+      double c[4][3];
+      const double cu[4] = {-1.0 + shift, 1.0 + shift, 1.0 + shift, -1.0 + shift}, cv[4] = {-1.0, -1.0, 1.0, 1.0};
+      for (int i = 0; i < 4; i++)
+        for (int a = 0; a < 3; a++) c[i][a] = dist * s[a] + cu[i] * u[a] + cv[i] * v[a];
+      double pos[18], nrm[18];
+      const int idx[6] = {0, 1, 2, 0, 2, 3};
+      for (int i = 0; i < 6; i++)
+        for (int a = 0; a < 3; a++) { pos[3 * i + a] = c[idx[i]][a]; nrm[3 * i + a] = -s[a]; }
+      const int tri_mat[2] = {0, 0};
+      pt.set_scene(0, nullptr, nullptr, 2, pos, nrm, tri_mat, 1, mats, 0, nullptr);
+      pt.use_flare_occlusion(true, rays);
+    }
+    pt.generate_ghost_buffer();
+    std::vector<double> sample(W * H * 3), star(W * H * 3);
+    if (lf_read_tile(pt.context(), 0, 0, 0, (int)W, (int)H, sample.data(), 3) != LF_OK ||
+        lf_read_tile(pt.context(), 2, 0, 0, (int)W, (int)H, star.data(), 3) != LF_OK)
+      throw std::runtime_error(pt.last_error());
+    dump(out + ".sample.f64", sample.data(), sample.size());
+    dump(out + ".star.f64", star.data(), star.size());
+    dump(out + ".ghost.f64", &pt.ghost_buffer.data[0].x, W * H * 3);
+    if (wall) {
+      int n = 0;
+      double vis[LF_MAX_FLARES];
+      uint64_t cnt[LF_MAX_FLARES];
+      if (lf_get_flare_visibility(pt.context(), &n, vis, cnt) != LF_OK) throw std::runtime_error(pt.last_error());
+      for (int k = 0; k < n; k++) printf("flare %d visibility %.17g visible rays %llu of %d\n", k, vis[k], (unsigned long long)cnt[k], rays);
+    }
+  } catch (const std::exception& e) {
+    fprintf(stderr, "shim_demo flarewall: %s\n", e.what());
+    return 3;
+  }
+  return 0;
+}
+
 int main(int argc, char** argv) {
+  if (argc > 1 && std::string(argv[1]) == "flarewall") return flarewall_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "geo") return geo_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "geolamp") return geolamp_main(argc, argv);
   if (argc > 1 && std::string(argv[1]) == "geowall") return geowall_main(argc, argv);
