@@ -47,6 +47,14 @@
  * + 2.4e-7 |P - C| millimetres of it (or whose ray grazes the plane's horizon, |d.dir| < eps_cos) is decided as
  * float64 decides, its weight goes into `frag` whichever way that was, and a ninth counter (light_edge_pairs) counts
  * it -- read with g64_light_edge_pairs(): the array handed to g64_trace keeps the eight slots older callers allocate.
+ *
+ * The occluder list (lf_set_ghost_occlusion, lf_set_ghost_occlusion_reach): a process-global setting, off by default
+ * (g64_set_occlusion) -- with no primitive every result is bit for bit what it was.  With one, every (ray, light) pair that
+ * would contribute is mapped to the world as the contract states it and tested by brute force over [0, reach of that light]
+ * (textbook ray-sphere and ray-triangle, each light on its own); a blocked pair adds nothing and is not counted as lit.  An
+ * occluder's outline is a hard edge like a rectangle's: a pair whose shadow ray passes within eps(t) = (eps_exit + t_mm
+ * eps_dir) wpm of an outline, or whose root lies within it of an end of the segment, and which no primitive blocks firmly,
+ * puts its weight into `frag` whichever way float64 decided, and is counted (g64_occlusion_pairs: tested, blocked, edge).
  */
 #define _GNU_SOURCE
 #include <complex.h>
@@ -584,6 +592,151 @@ static int area_lit(const double* g, vec P, vec d, double eps_cos, int* edge) {
   return inside;
 }
 
+/* ---- the occluder list (lf_set_ghost_occlusion / lf_set_ghost_occlusion_reach) ------------------------------------------------
+ * A process-global setting, off by default: without a primitive every result is bit for bit what it was before the list
+ * existed.  It acts under a light list only, as the device's occlusion does (kVarOccl comes with kVarLights).  Spheres
+ * (cx, cy, cz, r) and triangles (three vertices) are WORLD coordinates; the pose (row-major c2w, pos), world_per_mm and z_ref
+ * are the lens camera's.  Everything below is written from DESIGN.md section 4 ("Ghost occlusion", "The reach of a shadow
+ * ray", "Area lights: occlusion") and the textbook in plain double; it shares no expression with the device's walk: no
+ * tree, no boxes, no reuse of one light's answer for another. */
+enum { G64_REACH_SKY = 0, G64_REACH_LIGHT = 1 };
+static int g64_occl_ns = 0, g64_occl_nt = 0, g64_occl_reach = G64_REACH_SKY;
+static double *g64_occl_sph = NULL, *g64_occl_tri = NULL;
+static double g64_occl_c2w[9], g64_occl_pos[3], g64_occl_wpm = 1.0, g64_occl_zref = 0.0;
+void g64_set_occlusion(int n_spheres, const double* spheres, int n_tris, const double* tris, const double c2w[9],
+                       const double pos[3], double world_per_mm, double z_ref_mm, int reach_mode) {
+  free(g64_occl_sph); free(g64_occl_tri);
+  g64_occl_sph = g64_occl_tri = NULL;
+  g64_occl_ns = g64_occl_nt = 0;
+  if (n_spheres < 0 || n_tris < 0 || n_spheres + n_tris == 0) return;
+  if (n_spheres) { g64_occl_sph = (double*)malloc(sizeof(double) * 4 * (size_t)n_spheres); memcpy(g64_occl_sph, spheres, sizeof(double) * 4 * (size_t)n_spheres); }
+  if (n_tris) { g64_occl_tri = (double*)malloc(sizeof(double) * 9 * (size_t)n_tris); memcpy(g64_occl_tri, tris, sizeof(double) * 9 * (size_t)n_tris); }
+  memcpy(g64_occl_c2w, c2w, sizeof(g64_occl_c2w));
+  memcpy(g64_occl_pos, pos, sizeof(g64_occl_pos));
+  g64_occl_wpm = world_per_mm; g64_occl_zref = z_ref_mm;
+  g64_occl_reach = reach_mode == G64_REACH_LIGHT ? G64_REACH_LIGHT : G64_REACH_SKY;
+  g64_occl_ns = n_spheres; g64_occl_nt = n_tris;
+}
+/* the contract's mapping: the exit point P (lens mm, z absolute in the prescription's coordinates) and the unit direction d
+ * to the world: oc = (px wpm, py wpm, (z - z_ref) wpm), origin = pos + c2w oc, direction = c2w d */
+static vec rotate(const double* m, vec v) {
+  return V(m[0] * v.x + m[1] * v.y + m[2] * v.z, m[3] * v.x + m[4] * v.y + m[5] * v.z, m[6] * v.x + m[7] * v.y + m[8] * v.z);
+}
+static void occl_map(vec P, vec d, vec* O, vec* D) {
+  const vec oc = V(P.x * g64_occl_wpm, P.y * g64_occl_wpm, (P.z - g64_occl_zref) * g64_occl_wpm);
+  *O = add(V(g64_occl_pos[0], g64_occl_pos[1], g64_occl_pos[2]), rotate(g64_occl_c2w, oc));
+  *D = rotate(g64_occl_c2w, d);
+}
+/* where light k's shadow ray ends, world units along the unit direction: +inf under the sky's reach and for a directional
+ * light; the point of the ray nearest a lamp; just before a rectangle's plane ((double)0.00001f: the reference's EPS_F) */
+static double occl_reach(int k, vec P, vec d) {
+  if (g64_occl_reach != G64_REACH_LIGHT || k < 0 || g64_light_kind[k] == G64_DIRECTIONAL) return INFINITY;
+  const double* g = g64_light_geom[k];
+  double reach;
+  if (g64_light_kind[k] == G64_POINT) {
+    reach = g64_occl_wpm * dotp(sub(V(g[0], g[1], g[2]), P), d);
+  } else {
+    const vec e1 = V(g[6], g[7], g[8]), e2 = V(g[9], g[10], g[11]);
+    const vec n = V(e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x);
+    reach = g64_occl_wpm * (dotp(n, sub(V(g[0], g[1], g[2]), P)) / dotp(n, d)) - (double)0.00001f;
+  }
+  return reach > 0.0 ? reach : 0.0;
+}
+/* how far (world units) the float32 march's shadow ray can lie from this one at ray parameter t: the two measured constants */
+static double occl_eps(double t) { return (G64_EPS_EXIT + (fmax(t, 0.0) / g64_occl_wpm) * G64_EPS_DIR) * g64_occl_wpm; }
+/* does the ray (O, unit D) over [0, reach] pass within eps(t) of the segment [a, b]?  The closest points of the two lines
+ * (the textbook's 2 x 2 system), the segment's parameter clamped to [0, 1], the ray's then taken again and clamped to t >= 0 */
+static int passes_segment(vec O, vec D, double reach, vec a, vec b) {
+  const vec u = sub(b, a), w0 = sub(O, a);
+  const double B = dotp(D, u), C = dotp(u, u), d = dotp(D, w0), e = dotp(u, w0);
+  const double denom = C - B * B;                             /* (D.D = 1) */
+  double s = denom > 1e-14 * C ? (e - B * d) / denom : 0.0;   /* parallel: any point of the segment */
+  s = s < 0.0 ? 0.0 : s > 1.0 ? 1.0 : s;
+  double t = s * B - d;
+  if (t < 0.0) t = 0.0;
+  const double eps = occl_eps(t);
+  if (t > reach + eps) return 0;
+  const vec off = sub(add(w0, scale(D, t)), scale(u, s));
+  return sqrt(dotp(off, off)) < eps;
+}
+/* Is something within [0, reach] of the world ray (O, unit D)?  Brute force, every primitive.  A primitive answers
+ * 0 (misses), 1 (blocks, but float32 could see it miss: `near`) or 2 (blocks FIRMLY: its root lies more than eps inside
+ * [0, reach] and the ray passes more than eps inside its outline).  `near` is also raised by a primitive that misses although
+ * the ray passes within eps(t) of its outline -- a sphere's silhouette | |closest approach| - r | < eps, a triangle's three
+ * edge segments (the distance between the ray and the segment in space: never more than the distance in the triangle's plane,
+ * and the same at normal incidence, as area_lit's) -- or has its root within eps of an end of the
+ * segment.  *edge: the answer is one float32 may take the other way = some primitive is `near` and none blocks firmly (a ray
+ * across the shared edge of two triangles of one wall is blocked firmly by neither, and is in the band; one across a mesh's
+ * inner edge behind a wall that blocks it firmly is not). */
+static int occl_any_hit(vec O, vec D, double reach, int* edge) {
+  int blocked = 0, firm = 0, near = 0;
+  for (int i = 0; i < g64_occl_ns; i++) {
+    const double* s = g64_occl_sph + 4 * i;
+    const vec oc = sub(O, V(s[0], s[1], s[2]));
+    const double r = s[3], b = dotp(oc, D), c = dotp(oc, oc) - r * r, disc = b * b - c;
+    const double t_ca = -b;                                   /* the ray parameter of the closest approach */
+    if (c > 0.0 && t_ca < -r) continue;                       /* wholly behind the origin */
+    const double approach = sqrt(fmax(dotp(oc, oc) - b * b, 0.0));
+    const int silhouette = fabs(approach - r) < occl_eps(t_ca) && t_ca - r <= reach + occl_eps(t_ca);
+    if (silhouette) near = 1;
+    if (disc < 0.0) continue;
+    const double sq = sqrt(disc), t1 = -b - sq, t2 = -b + sq;
+    const double t = t1 >= 0.0 ? t1 : t2;                     /* the nearer root, the farther one from inside */
+    const double eps = occl_eps(t);
+    const int at_end = fabs(t - reach) < eps || fabs(t) < eps || (t1 < 0.0 && fabs(t1) < eps);
+    if (at_end) near = 1;
+    if (t >= 0.0 && t <= reach) { blocked = 1; if (!silhouette && !at_end) firm = 1; }
+  }
+  for (int i = 0; i < g64_occl_nt; i++) {
+    const double* p = g64_occl_tri + 9 * i;
+    const vec a = V(p[0], p[1], p[2]), bb = V(p[3], p[4], p[5]), cc = V(p[6], p[7], p[8]);
+    const vec e1 = sub(bb, a), e2 = sub(cc, a);
+    const vec n = V(e1.y * e2.z - e1.z * e2.y, e1.z * e2.x - e1.x * e2.z, e1.x * e2.y - e1.y * e2.x);
+    const double nn = sqrt(dotp(n, n)), denom = dotp(n, D);
+    if (!(fabs(denom) > 1e-12 * nn)) continue;                /* parallel to the plane (or a degenerate triangle) */
+    const int on_outline = passes_segment(O, D, reach, a, bb) || passes_segment(O, D, reach, bb, cc) || passes_segment(O, D, reach, cc, a);
+    if (on_outline) near = 1;
+    const double t = dotp(n, sub(a, O)) / denom, eps = occl_eps(t);
+    if (t < -eps || t > reach + eps) continue;
+    const vec q = add(O, scale(D, t)), w = sub(q, a);
+    /* barycentric coordinates from the normal equations of (e1, e2) */
+    const double g11 = dotp(e1, e1), g12 = dotp(e1, e2), g22 = dotp(e2, e2), b1 = dotp(w, e1), b2 = dotp(w, e2);
+    const double det = g11 * g22 - g12 * g12;
+    const double u = (g22 * b1 - g12 * b2) / det, v = (g11 * b2 - g12 * b1) / det;
+    const int inside = u >= 0.0 && v >= 0.0 && u + v <= 1.0;
+    const int at_end = fabs(t - reach) < eps || fabs(t) < eps;
+    if (on_outline || (inside && at_end)) near = 1;
+    if (inside && t >= 0.0 && t <= reach) { blocked = 1; if (!on_outline && !at_end) firm = 1; }
+  }
+  *edge = near && !firm;
+  return blocked;
+}
+/* per light of the list, of the last g64_trace under occlusion: the (ray, light) pairs tested (those that would contribute),
+ * of those blocked, and those in the occluders' edge band; total[3] the sums */
+static uint64_t g64_occl_tested[G64_MAX_LIGHTS], g64_occl_blocked[G64_MAX_LIGHTS], g64_occl_edge[G64_MAX_LIGHTS];
+void g64_occlusion_pairs(uint64_t total[3], uint64_t tested[G64_MAX_LIGHTS], uint64_t blocked[G64_MAX_LIGHTS],
+                         uint64_t edge[G64_MAX_LIGHTS]) {
+  total[0] = total[1] = total[2] = 0;
+  for (int k = 0; k < G64_MAX_LIGHTS; k++) {
+    total[0] += g64_occl_tested[k]; total[1] += g64_occl_blocked[k]; total[2] += g64_occl_edge[k];
+    if (tested) tested[k] = g64_occl_tested[k];
+    if (blocked) blocked[k] = g64_occl_blocked[k];
+    if (edge) edge[k] = g64_occl_edge[k];
+  }
+}
+/* for the anchors: one exit ray (P lens mm, d any length) against the installed occluders, for light k of the installed list
+ * (k < 0: the sky's reach).  out = {world origin xyz, world direction xyz, reach, in the edge band}; returns blocked */
+int g64_occlusion_ray(const double p[3], const double d[3], int k, double out[8]) {
+  const vec P = V(p[0], p[1], p[2]), dn = normalise(V(d[0], d[1], d[2]));
+  vec O, D;
+  int edge = 0;
+  occl_map(P, dn, &O, &D);
+  const double reach = occl_reach(k < g64_n_lights ? k : -1, P, dn);
+  const int blocked = (g64_occl_ns + g64_occl_nt) ? occl_any_hit(O, D, reach, &edge) : 0;
+  out[0] = O.x; out[1] = O.y; out[2] = O.z; out[3] = D.x; out[4] = D.y; out[5] = D.z; out[6] = reach; out[7] = (double)edge;
+  return blocked;
+}
+
 /* image, frag: W*H*3 doubles (rows [y0, y1) are written); counters: launched, events, clipped at
  * the stop, vignetted, totally reflected, reached the scene, hit the light ((ray, light) pairs under a list),
  * fragile rays.  The array a caller passes keeps its EIGHT slots -- a binding written before the light list existed
@@ -609,6 +762,10 @@ void g64_trace(const g64_lens* L, int W, int H, int y0, int y1, int spp, const u
   uint64_t total[9] = {0};
   memset(g64_pairs_lit, 0, sizeof(g64_pairs_lit));
   memset(g64_pairs_edge, 0, sizeof(g64_pairs_edge));
+  memset(g64_occl_tested, 0, sizeof(g64_occl_tested));
+  memset(g64_occl_blocked, 0, sizeof(g64_occl_blocked));
+  memset(g64_occl_edge, 0, sizeof(g64_occl_edge));
+  const int occluders = g64_occl_ns + g64_occl_nt > 0;
   if (n_threads < 1) n_threads = 1;
   int G = (int)floor(sqrt((double)spp));
   while ((G + 1) * (G + 1) <= spp) G++;
@@ -617,6 +774,7 @@ void g64_trace(const g64_lens* L, int W, int H, int y0, int y1, int spp, const u
 #pragma omp parallel num_threads(n_threads)
   {
     uint64_t counted[9] = {0}, skipped[9] = {0}, lit_k[G64_MAX_LIGHTS] = {0}, edge_k[G64_MAX_LIGHTS] = {0};
+    uint64_t tested_k[G64_MAX_LIGHTS] = {0}, blocked_k[G64_MAX_LIGHTS] = {0}, oedge_k[G64_MAX_LIGHTS] = {0};
 #pragma omp for schedule(dynamic, 16)
     for (long long p = (long long)y0 * W; p < (long long)y1 * W; p++) {
       const int x = (int)(p % W), y = (int)(p / W);
@@ -680,13 +838,21 @@ void g64_trace(const g64_lens* L, int W, int H, int y0, int y1, int spp, const u
                     shade = (1.0 - qq) * (1.0 - qq);
                   }
                 }
-                if (!r.dead && in && r.w * shade > 0.0) { c[6]++; if (c == counted) lit_k[k]++; }
+                /* the occluders: a pair that would contribute is tested over [0, reach_k], each light on its own */
+                int blocked = 0, occl_edge = 0;
+                if (occluders && !r.dead && in && r.w * shade > 0.0) {
+                  vec O, D;
+                  occl_map(r.o, dn, &O, &D);
+                  blocked = occl_any_hit(O, D, occl_reach(k, r.o, dn), &occl_edge);
+                  if (c == counted) { tested_k[k]++; blocked_k[k] += (uint64_t)blocked; oedge_k[k] += (uint64_t)occl_edge; }
+                }
+                if (!r.dead && in && !blocked && r.w * shade > 0.0) { c[6]++; if (c == counted) lit_k[k]++; }
                 if (!r.dead && edge && r.w > 0.0) { c[8]++; if (c == counted) edge_k[k]++; }
                 for (int ch = 0; ch < 3; ch++) {
                   const double colour = g64_light_rad[k][ch] * L->lambda_rgb[lam][ch];
-                  if (!r.dead && in) sum[ch] += r.w * shade * colour;
+                  if (!r.dead && in && !blocked) sum[ch] += r.w * shade * colour;
                   if (r.fragile) fsum[ch] += r.w_pot * shade * colour;
-                  else if (edge) fsum[ch] += r.w * colour; /* whichever way float64 decided */
+                  else if (edge || occl_edge) fsum[ch] += r.w * colour; /* whichever way float64 decided */
                   if (r.slope > 0.0) fsum[ch] += r.slope * shade * colour;
                   if (r.fragile && g64_cause)
                     for (int b = 0; b < 4; b++)
@@ -723,6 +889,9 @@ void g64_trace(const g64_lens* L, int W, int H, int y0, int y1, int spp, const u
     {
       for (int k = 0; k < 9; k++) total[k] += counted[k];
       for (int k = 0; k < G64_MAX_LIGHTS; k++) { g64_pairs_lit[k] += lit_k[k]; g64_pairs_edge[k] += edge_k[k]; }
+      for (int k = 0; k < G64_MAX_LIGHTS; k++) {
+        g64_occl_tested[k] += tested_k[k]; g64_occl_blocked[k] += blocked_k[k]; g64_occl_edge[k] += oedge_k[k];
+      }
     }
   }
   if (counters) memcpy(counters, total, 8 * sizeof(total[0]));

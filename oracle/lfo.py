@@ -672,11 +672,13 @@ G64_COUNTERS = ("rays_launched", "surface_events", "rays_clipped_stop", "rays_vi
 
 g64_last_causes = None
 g64_last_light_pairs = None      # per light of the last g64_trace(lights=...): (lit (ray, light) pairs, those in its edge band)
+g64_last_occlusion_pairs = None  # of the last g64_trace(occlusion=...): g64_occlusion_pairs()
 G64_CAUSES = ("aperture_rim", "mask_texel_edge", "critical_angle", "grazing_miss")
 
 
 def g64_trace(lens, W, H, y0, y1, spp, key, pairs, include_primary, mask, sun_dir, sun_radiance,
-              sun_angular_radius, n_threads=8, lambda_rgb=None, sub_bits=6, cull=None, causes=False, lights=None, **eps):
+              sun_angular_radius, n_threads=8, lambda_rgb=None, sub_bits=6, cull=None, causes=False, lights=None,
+              occlusion=None, **eps):
     """-> (image, frag, counters): image / frag are H x W x 3; a faithful float32 evaluation of the
     same estimator satisfies |pixel32 - image| <= tol * image + frag (see lf_geo_f64.c).  cull: a table from
     LensFlare.cull_table() -- the image stays the full enumeration's, the counters count the rays the device starts.
@@ -684,8 +686,11 @@ def g64_trace(lens, W, H, y0, y1, spp, key, pairs, include_primary, mask, sun_di
     aperture rim, mask texel edge, critical angle, grazing miss of a sphere.
     lights: a list of (kind, geom12 -- or its first three floats --, radiance, angular_radius) as LensFlare.lights_geom()
     reports them (g64_set_lights, cleared again afterwards); the sun_* arguments are then ignored.  rays_hit_light
-    counts (ray, light) pairs, light_edge_pairs those in the edge band of a rectangle."""
-    global g64_last_causes, g64_last_light_pairs
+    counts (ray, light) pairs, light_edge_pairs those in the edge band of a rectangle.
+    occlusion: the keyword arguments of g64_set_occlusion (set for this call, cleared again afterwards; needs `lights`): a pair
+    the occluders block adds nothing and is not counted in rays_hit_light; g64_last_occlusion_pairs = g64_occlusion_pairs()."""
+    global g64_last_causes, g64_last_light_pairs, g64_last_occlusion_pairs
+    assert occlusion is None or lights is not None, "occlusion acts under a light list, as the device's does"
     L = g64_lens(lens, sun_dir, sun_radiance, sun_angular_radius, lambda_rgb, **eps)
     table = _device_cull(cull, W, H, spp) if cull is not None else None
     if pairs is None:
@@ -708,12 +713,16 @@ def g64_trace(lens, W, H, y0, y1, spp, key, pairs, include_primary, mask, sun_di
     try:
         if lights is not None:
             g64_set_lights(lights)
+        if occlusion is not None:
+            g64_set_occlusion(**occlusion)
         lib().g64_trace(C.byref(L), W, H, y0, y1, spp, k, int(sub_bits), _p(pairs, C.c_int), len(pairs),
                         _p(mask, C.c_float), mask.shape[1], mask.shape[0], _p(image, C.c_double),
                         _p(frag, C.c_double), cnt, n_threads)
     finally:
         lib().g64_set_cull(None, 0, 0, 0, 64)
         lib().g64_set_cause_buffer(None)
+        if occlusion is not None:
+            g64_set_occlusion()
         if lights is not None:
             g64_set_lights(None)
     g64_last_light_pairs = None
@@ -721,6 +730,9 @@ def g64_trace(lens, W, H, y0, y1, spp, key, pairs, include_primary, mask, sun_di
         lit_k, edge_k = (C.c_uint64 * 8)(), (C.c_uint64 * 8)()
         lib().g64_light_pairs(lit_k, edge_k)
         g64_last_light_pairs = [(int(lit_k[i]), int(edge_k[i])) for i in range(len(lights))]
+    g64_last_occlusion_pairs = None
+    if occlusion is not None:
+        g64_last_occlusion_pairs = g64_occlusion_pairs(len(lights))
     lib().g64_light_edge_pairs.restype = C.c_uint64
     return image, frag, dict(zip(G64_COUNTERS, [int(v) for v in cnt] + [int(lib().g64_light_edge_pairs())]))
 
@@ -743,6 +755,47 @@ def g64_set_lights(lights=None):
     alpha = np.ascontiguousarray(np.asarray([l[3] for l in lights], np.float32).reshape(n), np.float64)
     assert n <= 8 and set(kinds.tolist()) <= {0, 1, 2}
     lib().g64_set_lights(n, _p(kinds, C.c_int), _p(geom, C.c_double), _p(rad, C.c_double), _p(alpha, C.c_double))
+
+
+REACH_SKY, REACH_LIGHT = 0, 1
+
+
+def g64_set_occlusion(spheres=(), triangles=(), c2w=None, pos=(0.0, 0.0, 0.0), world_per_mm=0.001, z_ref_mm=0.0, reach=REACH_SKY):
+    """The float64 tracer's occluder list (lf_set_ghost_occlusion / lf_set_ghost_occlusion_reach): spheres (cx, cy, cz, r) and
+    triangles (nine numbers: three vertices) in WORLD coordinates, the pose (row-major c2w, pos), world_per_mm and z_ref_mm
+    of the lens camera's mapping, and the reach of a shadow ray (REACH_SKY: +inf; REACH_LIGHT: up to the light).  No primitive
+    = off: the tracer is then bit for bit what it is without the list.  A process-global setting: use it in try ... finally
+    (g64_trace(occlusion=dict(...)) does)."""
+    sp = np.ascontiguousarray(np.asarray(spheres, np.float64).reshape(-1, 4))
+    tr = np.ascontiguousarray(np.asarray(triangles, np.float64).reshape(-1, 9))
+    m = np.ascontiguousarray(np.eye(3) if c2w is None else np.asarray(c2w, np.float64).reshape(3, 3)).reshape(-1)
+    p = np.ascontiguousarray(pos, np.float64).reshape(3)
+    assert reach in (REACH_SKY, REACH_LIGHT) and (len(sp) + len(tr) == 0 or world_per_mm > 0)
+    lib().g64_set_occlusion(len(sp), _p(sp, C.c_double), len(tr), _p(tr, C.c_double), _p(m, C.c_double), _p(p, C.c_double),
+                            C.c_double(world_per_mm), C.c_double(z_ref_mm), int(reach))
+
+
+def g64_occlusion_pairs(n_lights=8):
+    """of the last g64_trace under occlusion: dict(tested, blocked, edge, per_light=[(tested, blocked, edge) per light]) --
+    the (ray, light) pairs that would contribute, of those blocked, and those in the occluders' edge band"""
+    tot, t, b, e = (C.c_uint64 * 3)(), (C.c_uint64 * 8)(), (C.c_uint64 * 8)(), (C.c_uint64 * 8)()
+    lib().g64_occlusion_pairs(tot, t, b, e)
+    return dict(tested=int(tot[0]), blocked=int(tot[1]), edge=int(tot[2]),
+                per_light=[(int(t[i]), int(b[i]), int(e[i])) for i in range(n_lights)])
+
+
+def g64_occlusion_rays(p, d, light=-1):
+    """n exit rays (p lens mm, d any length) against the installed occluders, for light `light` of the installed list (-1: the
+    sky's reach) -> (blocked n, edge n, world origins n x 3, world unit directions n x 3, reach n)"""
+    p = np.ascontiguousarray(p, np.float64).reshape(-1, 3)
+    d = np.ascontiguousarray(d, np.float64).reshape(-1, 3)
+    out = np.zeros((len(p), 8), np.float64)
+    blocked = np.zeros(len(p), bool)
+    row = (C.c_double * 8)()
+    for i in range(len(p)):
+        blocked[i] = bool(lib().g64_occlusion_ray((C.c_double * 3)(*p[i]), (C.c_double * 3)(*d[i]), int(light), row))
+        out[i] = list(row)
+    return blocked, out[:, 7] != 0, out[:, 0:3], out[:, 3:6], out[:, 6]
 
 
 def lights_of(ctx):

@@ -9,7 +9,8 @@ shares no expression with the device.  The tracer is fed from ctx.lights_geom():
 A rectangle's outline is a hard edge: the (ray, light) pairs whose hit point lies in its edge band (lf_geo_f64.c area_lit) are
 counted in light_edge_pairs, their weight is in `frag`, and they must stay below 1 % of that light's lit pairs.  Each test prints
 the lit values, those needing the allowance, the largest raw deviation, the median, and the edge pairs with their share
-(record: profiles/lights_f64_parity.txt).  Occlusion and coating stacks stay out: the tracer knows neither."""
+(record: profiles/lights_f64_parity.txt).  Occluded frames are held to the same bar in tests/test_gpu_occlusion_f64.py (the tracer's
+occluder list); coating stacks stay out: the tracer does not know them."""
 import numpy as np
 import pytest
 
