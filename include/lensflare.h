@@ -27,6 +27,7 @@ extern "C" {
 #define LF_MAX_SURFACES 16   /* interfaces per prescription (incl. the stop) */
 #define LF_MAX_LAMBDA 8      /* wavelengths per prescription */
 #define LF_MAX_COAT_LAYERS 6 /* layers of a coating stack on one interface (lf_set_lens_coating_stacks) */
+#define LF_MAX_ASPH_COEF 6   /* even coefficients A4 .. A14 of an aspheric interface (lf_set_lens_aspheres) */
 #define LF_MAX_FLARES 8      /* in-frame directional lights */
 #define LF_MAX_LIGHTS 8      /* lights one launch of the geometric march follows (lf_set_lights) */
 #define LF_MAX_PAIRS 128     /* ghost pairs per trace call */
@@ -39,7 +40,8 @@ typedef enum {
   LF_ERR_NO_DEVICE = 2, /* no gfx950 device / device index out of range */
   LF_ERR_HIP = 3,       /* a HIP runtime call failed; see lf_last_error */
   LF_ERR_STATE = 4,     /* call order violated (e.g. render before set_frame) */
-  LF_ERR_OOM = 5
+  LF_ERR_OOM = 5,
+  LF_ERR_UNSUPPORTED = 6 /* the call is valid but not built for the installed state (e.g. the lens camera on an aspheric lens) */
 } lf_status;
 
 typedef enum { LF_APERTURE_STARBURST = 0, LF_APERTURE_GHOST = 1 } lf_aperture_slot;
@@ -419,7 +421,8 @@ lf_status lf_group_share_cull(lf_group* g, int spp);
 lf_status lf_group_set_block_deal(lf_group* g, int on);
 
 /* ---------------------------------------------------------------- geometric lens --------- */
-/* The north-star path: real ray march through spherical interfaces.  The reference has no
+/* The north-star path: real ray march through spherical interfaces -- or, with lf_set_lens_aspheres, through
+ * conic and even-polynomial aspheres on the same vertex curvatures.  The reference has no
  * counterpart (its lens is paraxial, pathtracer.cpp:511-689; Camera::generate_ray_for_thin_lens
  * is a stub, camera_lens.cpp:22-30), so this replaces `generate_ghost_buffer` when selected.
  *   radius[k]      signed radius of curvature in mm (0 = flat; the stop is flat)
@@ -492,6 +495,57 @@ lf_status lf_coating_stack_reflectance(float n_in, int n_layers, const float* n_
  * cos_in (in [0, 1]) of its angle of incidence; thickness 0 gives the bare interface, total reflection 1 */
 lf_status lf_coating_reflectance(float n_in, float n_film, float n_out, float thickness_nm,
                                  float lambda_nm, float cos_in, float out[3]);
+/* ASPHERIC INTERFACES (no reference counterpart).  Interface k of the installed lens becomes the surface of revolution
+ *   z(r^2) = c r^2 / (1 + sqrt(1 - (1 + kappa) c^2 r^2)) + r^4 (A4 + r^2 (A6 + r^2 (... A14)))
+ * with c = 1 / radius[k] as lf_set_lens holds it (c = 0 with coefficients: a corrector plate), z along the axis from
+ * the interface's vertex, r the distance from the axis in mm.
+ *   conic[k]              kappa of interface k (0: a sphere, -1: a paraboloid)
+ *   coef[m*n + k]         A(4 + 2 m) of interface k in mm^(1 - (4 + 2 m)), m = 0 .. n_coef - 1, n_coef in 0 .. LF_MAX_ASPH_COEF
+ * There is NO r^2 coefficient: the vertex curvature stays 1 / radius, so everything paraxial is unchanged --
+ * lf_paraxial_efl, lf_paraxial_image_scale, lf_paraxial_exit_pupil / _entrance_pupil, lf_focus_lens,
+ * lf_aim_at_exit_pupil and the sun hand-over of lf_set_sun_from_flares; lf_get_lens_info keeps its meaning.
+ * conic == NULL clears the aspheres.  A record of all zeros is no record: a lens whose records are all zero has no
+ * aspheres and launches exactly the kernels it launched before.  lf_set_lens clears the aspheres (they belong to the
+ * prescription); lf_focus_lens keeps them.  Refused with LF_ERR_INVALID and a message that names the interface: a
+ * value that is not finite, a record on the stop, n_coef outside 0 .. LF_MAX_ASPH_COEF, an interface whose
+ * 1 - (1 + kappa) c^2 h^2 is not positive in float at its own semi-aperture h (the conic ends inside the clear aperture).
+ * A lens file carries them as `asphere k kappa [A4 [A6 ...]]` lines (lf_load_lens_file).
+ * A lens with an asphere is marched by a kernel of its own (k_march_asph: every path alone from the sensor, a fixed
+ * number of Newton steps from the base sphere's intersection on the aspheric rows, the unchanged spherical event on all
+ * others); no cull table is built for it (lf_get_cull_reason: LF_CULL_ASPHERIC).  Films and stacks, every kind of light,
+ * ghost occlusion, bands and deals work as on any lens.  The lens camera's scene image (lf_set_lens_camera,
+ * lf_render_scene_term) refuses an aspheric lens with LF_ERR_UNSUPPORTED, and so does lf_get_lens_camera while a
+ * lens-camera mode is on (it would calibrate that image); lf_generate_lens_rays works. */
+lf_status lf_set_lens_aspheres(lf_ctx* ctx, int n_surfaces, const float* conic, int n_coef, const float* coef);
+/* what is installed (any pointer may be NULL): conic[n_surfaces], coef[LF_MAX_ASPH_COEF * n_surfaces] laid out as the
+ * setter's with n_coef = LF_MAX_ASPH_COEF, n_aspheric = the interfaces whose record is not all zero */
+lf_status lf_get_lens_aspheres(lf_ctx* ctx, int n_surfaces, float* conic, float* coef, int* n_aspheric);
+/* host arithmetic, no device: the sag z (mm) and dz / d(r^2) (1 / mm) of such a surface at r2 = r^2, in the float32
+ * arithmetic of the march (every multiply-add fused, IEEE root and division).  LF_ERR_INVALID beyond the conic's domain. */
+lf_status lf_asphere_sag(float curvature, float conic, int n_coef, const float* coef, float r2, float* z, float* dz_dr2);
+/* host arithmetic, no device: ONE event of ONE ray on such an interface, the definition the kernels run (bit for bit:
+ * lf_asphere_events is its device twin).  The interface: curvature, conic, coef[n_coef], semi_aperture, the index n_in of
+ * the medium the ray arrives in and n_out of the one behind the interface along the ray (a mirror event's too: its ct);
+ * reflect 0 / 1; forward 1: the ray travels +z (towards the sensor), 0: -z.  ray_in = {x, y, z, Kx, Ky, Kz}: the
+ * position relative to the vertex of the interface the ray sits on, which lies dzv = (its vertex z) - (this interface's
+ * vertex z) from this one's, and the OPTICAL direction K = n_in d.  ray_out: the same six at the hit, relative to this
+ * interface's vertex, K' in the medium the ray leaves in.  sq = n_in |cos(incidence)|, ct = n_out cos(refraction): what
+ * the Fresnel code of the march takes.  fate: 0 alive, 1 missed (beyond the conic's domain, or the iteration did not
+ * converge), 2 outside the clear aperture, 3 totally reflected (a refraction only).  Any pointer of sq, ct may be NULL. */
+lf_status lf_asphere_event(float curvature, float conic, int n_coef, const float* coef, float semi_aperture, float n_in,
+                           float n_out, int reflect, int forward, float dzv, const float ray_in[6], float ray_out[6],
+                           float* sq, float* ct, int* fate);
+/* the same event for n rays on the device: rays n x 6 as ray_in, out n x 8 = {ray_out, sq, ct}, fates n ints */
+lf_status lf_asphere_events(lf_ctx* ctx, float curvature, float conic, int n_coef, const float* coef, float semi_aperture,
+                            float n_in, float n_out, int reflect, int forward, float dzv, size_t n, const float* rays,
+                            float* out, int* fates);
+/* lf_generate_lens_rays generalised to the ghost path of pair (i, j): the ray of sensor point / pupil sample k is
+ * marched along the pair's event sequence -- towards the scene down to interface i, mirrored there, back up to j > i,
+ * mirrored again, out through the front element -- with the march's own events and weight (films, stacks, the stop
+ * mask under the installed filter, aspheres).  i = j = -1: the primary path.  out: n x 8 floats as
+ * lf_generate_lens_rays defines them.  Works for any lens; on an aspheric one lf_generate_lens_rays routes through it. */
+lf_status lf_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, size_t n, const float* sensor_xy_mm,
+                             const float* pupil_uv, float* out);
 /* what lf_set_lens / lf_load_lens_file installed (any pointer may be NULL); efl_mm = lf_paraxial_efl at
  * the middle wavelength (0 for an afocal prescription) */
 lf_status lf_get_lens_info(lf_ctx* ctx, int* n_surfaces, int* stop_index, int* n_lambda, float* sensor_width_mm,
@@ -940,8 +994,10 @@ typedef enum {
   LF_CULL_BLOCK_TOO_LARGE = 5,      /* even a block of 16 x 16 pixels is more than 1.8 mm on this sensor */
   LF_CULL_TABLE_TOO_FULL = 6,       /* the table starts more than 0.10 + 1.6 / paths of everything: the path tree is faster */
   LF_CULL_AUDIT_REFUTED = 7,        /* an audit ray of a dropped box reached the light: the table was not used (see below) */
-  LF_CULL_DISPERSION = 8            /* the index columns are not monotonic in the wavelength: the two ends of the spectrum
+  LF_CULL_DISPERSION = 8,           /* the index columns are not monotonic in the wavelength: the two ends of the spectrum
                                        do not bracket what lies between, the pre-pass's dispersion bound does not hold */
+  LF_CULL_ASPHERIC = 9              /* the lens has an aspheric interface (lf_set_lens_aspheres): the pre-pass's bounds were found
+                                       on spherical designs, no table is built and neither pre-pass nor audit launches */
 } lf_cull_reason;
 lf_status lf_get_cull_reason(lf_ctx* ctx, int* reason);
 /* THE AUDIT.  The pre-pass's bounds are second-order estimates from 15 rays per box: conservative on every
@@ -977,6 +1033,8 @@ lf_status lf_get_cull_audit(lf_ctx* ctx, uint64_t* rays, uint64_t* lit, int* lau
  *   "march_tail_tiles" n, "march_tail_groups" g   the culled march splits its LAST n wave tiles over g workgroups each so that a
  *                               launch ends on short workgroups (-1 / -1: the default, half a round of resident workgroups x 4;
  *                               0 / 1: no split); same pixels and counters whatever the values
+ *   "asph_force" 0/1            launch the aspheric lens's kernel (k_march_asph) on a lens WITHOUT aspheres: every curved glass row
+ *                               takes the Newton path with a zero record -- what lets the float64 oracle judge that kernel
  * Unknown names are refused.  ctx == NULL: the value becomes the default of every context created afterwards (a
  * test that cannot reach the contexts a helper creates); 0 takes the default away. */
 lf_status lf_test_knob(lf_ctx* ctx, const char* name, double value);
@@ -1049,7 +1107,11 @@ lf_status lf_set_flare_arithmetic(lf_ctx* ctx, int mode);
  * interface table follow later changes of the lens, the stop mask and the pupil target.
  * Needs lf_set_lens / lf_load_lens_file, the stop mask (LF_APERTURE_STARBURST slot), lf_set_camera
  * and the counter RNG (MT19937 parity mode is refused: its table has no pupil draws).
- * lf_get_lens_camera: the settings in force (after calibration) and the entrance pupil's z (mm). */
+ * lf_get_lens_camera: the settings in force (after calibration) and the entrance pupil's z (mm).  With a mode other
+ * than 0 it brings table and calibration up to date first, as lf_render_scene_term does, and so fails as that call
+ * would: on an aspheric lens (lf_set_lens_aspheres) both return LF_ERR_UNSUPPORTED -- the calibration belongs to a
+ * scene image that is not built for such a lens, and the getter reports no figure that no frame would use.  With
+ * mode 0 it succeeds on any lens. */
 lf_status lf_set_lens_camera(lf_ctx* ctx, int mode, double world_per_mm, double exposure);
 lf_status lf_get_lens_camera(lf_ctx* ctx, int* mode, double* world_per_mm, double* exposure,
                              double* entrance_pupil_z_mm);

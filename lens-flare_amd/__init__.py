@@ -19,7 +19,7 @@ LIB_PATH = os.environ.get("LF_LIB") or os.path.join(HERE, "liblensflare_hip.so")
 DATA = os.path.join(HERE, "data")
 
 STATUS = {0: "LF_OK", 1: "LF_ERR_INVALID", 2: "LF_ERR_NO_DEVICE", 3: "LF_ERR_HIP",
-          4: "LF_ERR_STATE", 5: "LF_ERR_OOM"}
+          4: "LF_ERR_STATE", 5: "LF_ERR_OOM", 6: "LF_ERR_UNSUPPORTED"}
 APERTURE_STARBURST, APERTURE_GHOST = 0, 1
 MAX_LIGHTS = 8   # LF_MAX_LIGHTS: lights one launch of the geometric march follows (set_lights)
 SAMPLE_BUFFER, GHOST_BUFFER, STARBURST_BUFFER, SCENE_BUFFER = 0, 1, 2, 3
@@ -50,6 +50,7 @@ ABI_SYMBOLS = [
     "lf_shift_vertex", "lf_compute_phase", "lf_irradiance_falloff", "lf_scene_trace_ray", "lf_scene_shade",
     "lf_load_lens_file", "lf_get_lens_info", "lf_set_lens_coatings", "lf_get_lens_coatings", "lf_coating_reflectance",
     "lf_set_lens_coating_stacks", "lf_get_lens_coating_stacks", "lf_coating_stack_reflectance",
+    "lf_set_lens_aspheres", "lf_get_lens_aspheres", "lf_asphere_sag", "lf_asphere_event", "lf_asphere_events", "lf_march_path_rays",
     "lf_set_mask_filter", "lf_get_mask_filter", "lf_mask_lookup",
     "lf_set_pupil_target", "lf_get_pupil_target", "lf_aim_at_exit_pupil", "lf_paraxial_exit_pupil", "lf_set_ghost_accumulate",
     "lf_set_lens_camera", "lf_get_lens_camera", "lf_set_lens_camera_aim", "lf_paraxial_entrance_pupil", "lf_focus_lens", "lf_focus_lens_from_pupil",
@@ -167,7 +168,7 @@ def load_lens_file(path):
     """Parse a .lens prescription (see data/dgauss11.lens) -> dict of float32 arrays."""
     if not os.path.isabs(path) and not os.path.exists(path):
         path = os.path.join(DATA, path)
-    rows, sensor_w, lambda_nm, coats, layers = [], 36.0, None, [], []
+    rows, sensor_w, lambda_nm, coats, layers, asphs = [], 36.0, None, [], [], []
     for line in open(path):
         line = line.split("#")[0].strip()
         if not line:
@@ -185,6 +186,11 @@ def load_lens_file(path):
         if t[0] == "layer":          # layer k thickness_nm m_1 .. m_L | m  (appends to interface k's stack, scene side first)
             layers.append((int(t[1]), float(t[2]), [float(v) for v in t[3:]]))
             continue
+        if t[0] == "asphere":        # asphere k kappa [A4 [A6 .. A14]]  (lf_set_lens_aspheres)
+            if len(t) < 3 or len(t) > 3 + MAX_ASPH_COEF:
+                raise ValueError(f"{path}: an asphere line is `asphere k kappa [A4 [A6 .. A14]]`")
+            asphs.append((int(t[1]), float(t[2]), [float(v) for v in t[3:]]))
+            continue
         rows.append([float(v) for v in t])
     rows = np.array(rows, np.float64)
     n = len(rows)
@@ -195,6 +201,17 @@ def load_lens_file(path):
     lens = dict(n=n, stop=stop[0] if stop else -1, radius=rows[:, 0].astype(np.float32),
                 thickness=rows[:, 1].astype(np.float32), ior=ior.astype(np.float32),
                 semi_aperture=rows[:, -1].astype(np.float32), sensor_width_mm=float(sensor_w))
+    if asphs:
+        conic = np.zeros(n, np.float32)
+        coef = np.zeros((MAX_ASPH_COEF, n), np.float32)
+        seen = set()
+        for k, kappa, a in asphs:
+            if not 0 <= k < n or k in seen:
+                raise ValueError(f"{path}: bad asphere line for interface {k}")
+            seen.add(k)
+            conic[k] = kappa
+            coef[:len(a), k] = a
+        lens["aspheres"] = dict(conic=conic, coef=coef)
     if lambda_nm is not None:
         if len(lambda_nm) != ior.shape[0]:
             raise ValueError(f"{path}: lambda_nm lists {len(lambda_nm)} wavelengths for {ior.shape[0]} index columns")
@@ -239,6 +256,41 @@ def load_lens_file(path):
 
 
 MAX_COAT_LAYERS = 6      # LF_MAX_COAT_LAYERS
+MAX_ASPH_COEF = 6        # LF_MAX_ASPH_COEF
+CULL_ASPHERIC = 9        # LF_CULL_ASPHERIC
+ASPH_ALIVE, ASPH_MISSED, ASPH_APERTURE, ASPH_TIR = 0, 1, 2, 3   # the fates of lf_asphere_event
+
+
+def asphere_sag(curvature, conic, coef, r2):
+    """(z, dz/dr2) of an aspheric surface at r2 = r^2 in the march's float32 arithmetic (lf_asphere_sag, host only)."""
+    a = np.ascontiguousarray(coef, np.float32).ravel()
+    z, zp = C.c_float(), C.c_float()
+    st = load_library().lf_asphere_sag(C.c_float(curvature), C.c_float(conic), len(a), _fp(a, C.c_float), C.c_float(r2),
+                                       C.byref(z), C.byref(zp))
+    if st != 0:
+        raise LensFlareError(st, "lf_asphere_sag")
+    return z.value, zp.value
+
+
+def asphere_event(curvature, conic, coef, semi_aperture, n_in, n_out, reflect, forward, dzv, rays):
+    """One event on an aspheric interface for each of the n x 6 rays {x, y, z, Kx, Ky, Kz}, host arithmetic
+    (lf_asphere_event): (out n x 8 = {ray, sq, ct}, fates n)."""
+    a = np.ascontiguousarray(coef, np.float32).ravel()
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    out = np.zeros((len(rays), 8), np.float32)
+    fates = np.zeros(len(rays), np.int32)
+    fn = load_library().lf_asphere_event
+    ro = (C.c_float * 6)()
+    sq, ct, fate = C.c_float(), C.c_float(), C.c_int()
+    consts = (C.c_float(curvature), C.c_float(conic), len(a), _fp(a, C.c_float), C.c_float(semi_aperture), C.c_float(n_in),
+              C.c_float(n_out), int(bool(reflect)), int(bool(forward)), C.c_float(dzv))
+    for i in range(len(rays)):
+        st = fn(*consts, _fp(rays[i], C.c_float), ro, C.byref(sq), C.byref(ct), C.byref(fate))
+        if st != 0:
+            raise LensFlareError(st, "lf_asphere_event")
+        out[i, :6] = ro[:]
+        out[i, 6], out[i, 7], fates[i] = sq.value, ct.value, fate.value
+    return out, fates
 
 
 def coating_stack_reflectance(n_in, n_film, thickness_nm, n_out, lambda_nm, cos_in):
@@ -923,6 +975,52 @@ class LensFlare:
         if "coating_stacks" in lens:
             c = lens["coating_stacks"]
             self.set_lens_coating_stacks(c["lambda_nm"], c["n_layers"], c["thickness_nm"], c["index"])
+        if "aspheres" in lens:
+            self.set_lens_aspheres(lens["aspheres"]["conic"], lens["aspheres"]["coef"])
+
+    def set_lens_aspheres(self, conic=None, coef=None):
+        """Conic constants conic[k] and even coefficients coef[m, k] (A4, A6, ... of interface k; up to MAX_ASPH_COEF rows)
+        on the installed lens.  conic None clears the aspheres."""
+        if conic is None:
+            self._ck(self.lib.lf_set_lens_aspheres(self.ctx, 0, None, 0, None))
+            return
+        kap = np.ascontiguousarray(conic, np.float32).ravel()
+        a = np.zeros((0, len(kap)), np.float32) if coef is None else np.atleast_2d(np.asarray(coef, np.float32))
+        if a.shape[1:] != (len(kap),):
+            raise ValueError("coef is (n_coef, n_surfaces)")
+        a = np.ascontiguousarray(a)
+        self._ck(self.lib.lf_set_lens_aspheres(self.ctx, len(kap), _fp(kap, C.c_float), int(a.shape[0]),
+                                               _fp(a, C.c_float) if a.shape[0] else None))
+
+    def lens_aspheres(self):
+        """dict(conic (n), coef (MAX_ASPH_COEF x n), n_aspheric) of the installed lens."""
+        n = self.lens_info()["n"]
+        kap = np.zeros(n, np.float32)
+        a = np.zeros((MAX_ASPH_COEF, n), np.float32)
+        cnt = C.c_int()
+        self._ck(self.lib.lf_get_lens_aspheres(self.ctx, n, _fp(kap, C.c_float), _fp(a, C.c_float), C.byref(cnt)))
+        return dict(conic=kap, coef=a, n_aspheric=cnt.value)
+
+    def asphere_events(self, curvature, conic, coef, semi_aperture, n_in, n_out, reflect, forward, dzv, rays):
+        """asphere_event on the device (lf_asphere_events): the same (out, fates), bit for bit."""
+        a = np.ascontiguousarray(coef, np.float32).ravel()
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        out = np.zeros((len(rays), 8), np.float32)
+        fates = np.zeros(len(rays), np.int32)
+        self._ck(self.lib.lf_asphere_events(self.ctx, C.c_float(curvature), C.c_float(conic), len(a), _fp(a, C.c_float),
+                                            C.c_float(semi_aperture), C.c_float(n_in), C.c_float(n_out), int(bool(reflect)),
+                                            int(bool(forward)), C.c_float(dzv), C.c_size_t(len(rays)), _fp(rays, C.c_float),
+                                            _fp(out, C.c_float), _fp(fates, C.c_int)))
+        return out, fates
+
+    def march_path_rays(self, lam, i, j, sensor_xy_mm, pupil_uv):
+        """generate_lens_rays along the ghost path of pair (i, j) ((-1, -1): the primary path): n x 8."""
+        xy = np.ascontiguousarray(sensor_xy_mm, np.float32).reshape(-1, 2)
+        uv = np.ascontiguousarray(pupil_uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(xy), 8), np.float32)
+        self._ck(self.lib.lf_march_path_rays(self.ctx, int(lam), int(i), int(j), C.c_size_t(len(xy)), _fp(xy, C.c_float),
+                                             _fp(uv, C.c_float), _fp(out, C.c_float)))
+        return out
 
     def set_lens_coating_stacks(self, lambda_nm, n_layers=None, thickness_nm=None, index=None):
         """Stacks of layers on the installed lens: lambda_nm[l], n_layers[k] (0 = bare), thickness_nm[j, k] and
@@ -1230,7 +1328,7 @@ class LensFlare:
                     reason=self.cull_reason())
 
     CULL_REASONS = ("applied", "off", "no_stop", "too_many_paths", "too_many_samples", "block_too_large", "table_too_full",
-                    "audit_refuted", "dispersion_not_monotonic")
+                    "audit_refuted", "dispersion_not_monotonic", "aspheric")
 
     def cull_reason(self):
         """why the last trace_ghosts did (not) cull: one of CULL_REASONS (lf_cull_reason)"""

@@ -10,6 +10,7 @@
 
 #include "lf_internal.h"
 #include "lf_march_events.h"
+#include "lf_asphere.h"
 #include "../host/lf_collada.h"
 
 lf_status lf_fail(const lf_ctx* ctx, lf_status st, const std::string& msg) {
@@ -1012,6 +1013,7 @@ lf_status lf_set_lens(lf_ctx* ctx, int n_surfaces, int stop_index, int n_lambda,
   // starts from the default disc, the rear element's clear aperture; so do its coatings: a new lens is bare
   ctx->pupil_target_h = 0.0f; ctx->pupil_target_z = 0.0f;
   ctx->coat = LfCoatings{};
+  ctx->asph = LfAspheres{};      // (and its aspheres: a new lens is one of spheres)
   ctx->lenscam_dirty = true;
   lf_derive_lens(ctx, n_surfaces, stop_index, n_lambda, radius, thickness, ior, semi_aperture,
                  sensor_width_mm);
@@ -1724,6 +1726,7 @@ lf_status lf_test_knob(lf_ctx* ctx, const char* name, double value) {
   if (n == "cull_force") { ctx->cull_force = iv != 0; return LF_OK; }
   if (n == "cull_weights_first") { ctx->cull_weights_first = iv != 0; return LF_OK; }
   if (n == "cull_no_prefix") { ctx->cull_no_prefix = iv != 0; return LF_OK; }
+  if (n == "asph_force") { ctx->asph_force = iv != 0; ctx->events_dirty = true; return LF_OK; }
   if (n == "cull_ignore_light") { ctx->cull_ignore_light = iv; return LF_OK; }      // (-1: off; k: the cull table is built WITHOUT light k -- the audit's test)
   if (n == "cull_no_widening") { ctx->cull_no_widening = iv != 0; return LF_OK; }    // (1: a point light enters the cull table with a directional light's radius -- wrong by construction)
   if (n == "cull_cache") { ctx->cull_cache_on = iv != 0; return LF_OK; }            // (0: the pre-pass marches its boxes at every build)
@@ -1915,6 +1918,8 @@ lf_status lf_generate_lens_rays(lf_ctx* ctx, int lambda, size_t n, const float* 
   if (lambda < 0 || lambda >= ctx->lens.n_lambda || n > 0x7fffffffull)
     return lf_fail(ctx, LF_ERR_INVALID, "lf_generate_lens_rays: wavelength index / count out of range");
   if (n == 0) return LF_OK;
+  // (an aspheric lens: the primary table knows spheres only -- the same ray along the primary path's own sequence)
+  if (ctx->asph.n > 0) return lf_march_path_rays(ctx, lambda, -1, -1, n, sensor_xy_mm, pupil_uv, out);
   LF_HIP(ctx, hipSetDevice(ctx->device));
   float *d_xy = nullptr, *d_uv = nullptr, *d_out = nullptr;
   hipError_t e = hipMalloc((void**)&d_xy, n * 2 * sizeof(float));
@@ -2401,6 +2406,173 @@ lf_status lf_coating_reflectance(float n_in, float n_film, float n_out, float th
   return LF_OK;
 }
 
+// ---------------------------------------------------------------- aspheres ----------------------
+static lfm::LfAsphRec asph_record(float conic, int n_coef, const float* coef, int stride, int k) {
+  lfm::LfAsphRec r{};
+  r.kappa = conic;
+  for (int m = 0; m < n_coef && m < LF_MAX_ASPH_COEF; m++) r.a[m] = coef ? coef[(size_t)m * stride + k] : 0.0f;
+  return r;
+}
+
+lf_status lf_set_lens_aspheres(lf_ctx* ctx, int n_surfaces, const float* conic, int n_coef, const float* coef) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lens_aspheres before lf_set_lens");
+  if (!conic) {   // every interface a sphere
+    ctx->asph = LfAspheres{};
+    ctx->events_dirty = true;
+    ctx->lenscam_dirty = true;
+    return LF_OK;
+  }
+  if (n_surfaces != ctx->raw_n) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_aspheres: n_surfaces differs from the installed lens");
+  if (n_coef < 0 || n_coef > LF_MAX_ASPH_COEF || (n_coef > 0 && !coef))
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_aspheres: n_coef must be 0 .. LF_MAX_ASPH_COEF (with its array)");
+  LfAspheres A;
+  for (int k = 0; k < n_surfaces; k++) {
+    const std::string who = "lf_set_lens_aspheres: interface " + std::to_string(k);
+    bool any = conic[k] != 0.0f, finite = std::isfinite(conic[k]);
+    for (int m = 0; m < n_coef; m++) {
+      const float a = coef[(size_t)m * n_surfaces + k];
+      any = any || a != 0.0f;
+      finite = finite && std::isfinite(a);
+    }
+    if (!finite) return lf_fail(ctx, LF_ERR_INVALID, who + ": a value is not finite");
+    if (!any) continue;
+    if (k == ctx->raw_stop) return lf_fail(ctx, LF_ERR_INVALID, who + ": the stop cannot carry an aspheric record");
+    // the conic must cover the clear aperture: 1 - (1 + kappa) c^2 h^2 > 0 in the float arithmetic of the sag
+    const LfSurfaceDev& s = ctx->lens.surf[k];
+    const float kc2 = (1.0f + conic[k]) * (s.curv * s.curv);
+    if (!(fmaf(-kc2, s.h2, 1.0f) > 0.0f))
+      return lf_fail(ctx, LF_ERR_INVALID, who + ": 1 - (1 + kappa) c^2 h^2 is not positive at its semi-aperture (the conic ends inside the clear aperture)");
+    A.kappa[k] = conic[k];
+    for (int m = 0; m < n_coef; m++) A.coef[(size_t)m * n_surfaces + k] = coef[(size_t)m * n_surfaces + k];
+    A.n++;
+  }
+  ctx->asph = A;
+  ctx->events_dirty = true;
+  ctx->lenscam_dirty = true;
+  return LF_OK;
+}
+
+lf_status lf_get_lens_aspheres(lf_ctx* ctx, int n_surfaces, float* conic, float* coef, int* n_aspheric) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_get_lens_aspheres before lf_set_lens");
+  if (n_surfaces != ctx->raw_n) return lf_fail(ctx, LF_ERR_INVALID, "lf_get_lens_aspheres: n_surfaces differs from the installed lens");
+  const LfAspheres& A = ctx->asph;
+  if (conic) for (int k = 0; k < n_surfaces; k++) conic[k] = A.kappa[k];
+  if (coef) for (size_t i = 0; i < (size_t)LF_MAX_ASPH_COEF * n_surfaces; i++) coef[i] = A.coef[i];
+  if (n_aspheric) *n_aspheric = A.n;
+  return LF_OK;
+}
+
+static bool asph_args_ok(float curvature, float conic, int n_coef, const float* coef) {
+  if (n_coef < 0 || n_coef > LF_MAX_ASPH_COEF || (n_coef > 0 && !coef)) return false;
+  bool finite = std::isfinite(curvature) && std::isfinite(conic);
+  for (int m = 0; m < n_coef; m++) finite = finite && std::isfinite(coef[m]);
+  return finite;
+}
+
+lf_status lf_asphere_sag(float curvature, float conic, int n_coef, const float* coef, float r2, float* z, float* dz_dr2) {
+  if (!asph_args_ok(curvature, conic, n_coef, coef) || !(r2 >= 0.0f)) return LF_ERR_INVALID;
+  const lfm::LfAsphRec rec = asph_record(conic, n_coef, coef, 1, 0);
+  float zz, zp;
+  if (!lfm::lf_asph_sag(curvature, rec, r2, zz, zp)) return LF_ERR_INVALID;
+  if (z) *z = zz;
+  if (dz_dr2) *dz_dr2 = zp;
+  return LF_OK;
+}
+
+// the sixteen constants of one event as the host twin and the kernel take them: {c, delta, h2, sgn, dzv, 0, 0, 0, record}
+static bool asph_event_consts(float curvature, float conic, int n_coef, const float* coef, float semi_aperture, float n_in,
+                              float n_out, int reflect, int forward, float dzv, float out[16]) {
+  if (!asph_args_ok(curvature, conic, n_coef, coef) || !(semi_aperture > 0.0f) || !std::isfinite(semi_aperture) ||
+      !(n_in >= 1.0f) || !(n_out >= 1.0f) || !std::isfinite(n_in) || !std::isfinite(n_out) || !std::isfinite(dzv))
+    return false;
+  const lfm::LfAsphRec rec = asph_record(conic, n_coef, coef, 1, 0);
+  // (float products of the indices, as pack_program forms a row's delta -- a mirror row's too: its ct is the Fresnel code's)
+  const float n_in2 = n_in * n_in, n_out2 = n_out * n_out;
+  out[0] = curvature; out[1] = n_out2 - n_in2; out[2] = semi_aperture * semi_aperture; out[3] = forward ? 1.0f : -1.0f;
+  out[4] = dzv; out[5] = out[6] = out[7] = 0.0f;
+  std::memcpy(out + 8, &rec, sizeof(rec));
+  return true;
+}
+
+lf_status lf_asphere_event(float curvature, float conic, int n_coef, const float* coef, float semi_aperture, float n_in,
+                           float n_out, int reflect, int forward, float dzv, const float ray_in[6], float ray_out[6],
+                           float* sq, float* ct, int* fate) {
+  float k[16];
+  if (!ray_in || !ray_out || !fate || !asph_event_consts(curvature, conic, n_coef, coef, semi_aperture, n_in, n_out, reflect, forward, dzv, k))
+    return LF_ERR_INVALID;
+  lfm::LfAsphRec rec;
+  std::memcpy(&rec, k + 8, sizeof(rec));
+  float px = ray_in[0], py = ray_in[1], hz = ray_in[2], dx = ray_in[3], dy = ray_in[4], dz = ray_in[5], r2;
+  const lfm::AsphHit h = lfm::lf_asph_event(px, py, hz, r2, dx, dy, dz, k[4], k[0], rec, k[1], k[2], reflect != 0, k[3]);
+  ray_out[0] = px; ray_out[1] = py; ray_out[2] = hz; ray_out[3] = dx; ray_out[4] = dy; ray_out[5] = dz;
+  if (sq) *sq = h.sq;
+  if (ct) *ct = h.ct;
+  *fate = h.fate;
+  return LF_OK;
+}
+
+lf_status lf_asphere_events(lf_ctx* ctx, float curvature, float conic, int n_coef, const float* coef, float semi_aperture,
+                            float n_in, float n_out, int reflect, int forward, float dzv, size_t n, const float* rays,
+                            float* out, int* fates) {
+  if (!ctx || (n > 0 && (!rays || !out || !fates))) return LF_ERR_INVALID;
+  float k[16];
+  if (n > 0x7fffffffull / 8 || !asph_event_consts(curvature, conic, n_coef, coef, semi_aperture, n_in, n_out, reflect, forward, dzv, k))
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_asphere_events: constants not finite / out of range, or too many rays for one call");
+  if (n == 0) return LF_OK;
+  LF_HIP(ctx, hipSetDevice(ctx->device));
+  float *d_rays = nullptr, *d_out = nullptr;
+  int* d_fates = nullptr;
+  hipError_t e = hipMalloc((void**)&d_rays, n * 6 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, n * 8 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_fates, n * sizeof(int));
+  if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * 6 * sizeof(float), hipMemcpyHostToDevice);
+  lf_status st = LF_OK;
+  if (e == hipSuccess) st = lfk_asphere_events(ctx, k, reflect, forward, n, d_rays, d_out, d_fates);
+  if (e == hipSuccess && st == LF_OK) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && st == LF_OK) e = hipMemcpy(out, d_out, n * 8 * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && st == LF_OK) e = hipMemcpy(fates, d_fates, n * sizeof(int), hipMemcpyDeviceToHost);
+  if (d_rays) (void)hipFree(d_rays);
+  if (d_out) (void)hipFree(d_out);
+  if (d_fates) (void)hipFree(d_fates);
+  if (st != LF_OK) return st;
+  LF_HIP(ctx, e);
+  return LF_OK;
+}
+
+lf_status lf_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, size_t n, const float* sensor_xy_mm,
+                             const float* pupil_uv, float* out) {
+  if (!ctx || !sensor_xy_mm || !pupil_uv || !out) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_march_path_rays before lf_set_lens");
+  if (!ctx->ap[LF_APERTURE_STARBURST].valid)
+    return lf_fail(ctx, LF_ERR_STATE, "aperture mask (LF_APERTURE_STARBURST slot) not set");
+  if (lambda < 0 || lambda >= ctx->lens.n_lambda || n > 0x7fffffffull / 8)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_march_path_rays: wavelength index / count out of range");
+  const int N = ctx->lens.n_surf, stop = ctx->lens.stop;
+  const bool primary = i == -1 && j == -1;
+  if (!primary && !(i >= 0 && i < j && j < N && i != stop && j != stop))
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_march_path_rays: a pair is two glass interfaces 0 <= i < j < n_surfaces (-1, -1: the primary path)");
+  if (n == 0) return LF_OK;
+  LF_HIP(ctx, hipSetDevice(ctx->device));
+  float *d_xy = nullptr, *d_uv = nullptr, *d_out = nullptr;
+  hipError_t e = hipMalloc((void**)&d_xy, n * 2 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_uv, n * 2 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, n * 8 * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d_xy, sensor_xy_mm, n * 2 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_uv, pupil_uv, n * 2 * sizeof(float), hipMemcpyHostToDevice);
+  lf_status st = LF_OK;
+  if (e == hipSuccess) st = lfk_march_path_rays(ctx, lambda, i, j, (int)n, d_xy, d_uv, d_out);
+  if (e == hipSuccess && st == LF_OK) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && st == LF_OK) e = hipMemcpy(out, d_out, n * 8 * sizeof(float), hipMemcpyDeviceToHost);
+  if (d_xy) (void)hipFree(d_xy);
+  if (d_uv) (void)hipFree(d_uv);
+  if (d_out) (void)hipFree(d_out);
+  if (st != LF_OK) return st;
+  LF_HIP(ctx, e);
+  return LF_OK;
+}
+
 // ---------------------------------------------------------------- lens file ---------------------
 lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
   if (!ctx || !path) return LF_ERR_INVALID;
@@ -2411,7 +2583,8 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
   // `coating k thickness_nm m_1 .. m_L | m` (a film on interface k: lf_set_lens_coatings; needs lambda_nm)
   // `layer k thickness_nm m_1 .. m_L | m` (appends a layer to interface k's stack, scene side first:
   // lf_set_lens_coating_stacks; needs lambda_nm; not on an interface with a `coating` line)
-  std::vector<std::vector<double>> rows, coats, layers;
+  // `asphere k kappa [A4 [A6 ...]]` (interface k's conic constant and even coefficients: lf_set_lens_aspheres)
+  std::vector<std::vector<double>> rows, coats, layers, asphs;
   std::vector<double> lambdas;
   bool lambda_line = false, lambda_bad = false;
   double sensor_w = 36.0;
@@ -2421,7 +2594,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (char* h = std::strchr(line, '#')) *h = 0;
     std::vector<double> v;
     char* p = line;
-    int keyword = 0;   // 1 sensor_width_mm, 2 lambda_nm, 3 coating, 4 layer
+    int keyword = 0;   // 1 sensor_width_mm, 2 lambda_nm, 3 coating, 4 layer, 5 asphere
     while (*p) {
       while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') p++;
       if (!*p) break;
@@ -2429,6 +2602,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
       if (v.empty() && !keyword && std::strncmp(p, "lambda_nm", 9) == 0) { keyword = 2; p += 9; continue; }
       if (v.empty() && !keyword && std::strncmp(p, "coating", 7) == 0) { keyword = 3; p += 7; continue; }
       if (v.empty() && !keyword && std::strncmp(p, "layer", 5) == 0) { keyword = 4; p += 5; continue; }
+      if (v.empty() && !keyword && std::strncmp(p, "asphere", 7) == 0) { keyword = 5; p += 7; continue; }
       char* e = nullptr;
       const double d = std::strtod(p, &e);
       if (e == p) {
@@ -2443,6 +2617,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (keyword == 2) { lambda_line = true; lambdas = v; continue; }
     if (keyword == 3) { coats.push_back(v); continue; }
     if (keyword == 4) { layers.push_back(v); continue; }
+    if (keyword == 5) { asphs.push_back(v); continue; }
     if (keyword == 1) { if (v.size() != 1) { bad = true; break; } sensor_w = v[0]; continue; }
     if (!v.empty()) rows.push_back(v);
   }
@@ -2494,7 +2669,24 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
         lth[(size_t)k] = cth[k];
         for (int l = 0; l < nl; l++) lidx[(size_t)l * n + k] = cidx[l * n + k];
       }
+  float akappa[LF_MAX_SURFACES] = {}, acoef[LF_MAX_ASPH_COEF * LF_MAX_SURFACES] = {};
+  bool has_asph[LF_MAX_SURFACES] = {};
+  for (const auto& c : asphs) {
+    const int k = c.size() >= 2 ? (int)c[0] : -1;
+    if (k < 0 || k >= n || (double)k != c[0] || (int)c.size() > 2 + LF_MAX_ASPH_COEF || has_asph[k])
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_load_lens_file: an asphere line is `asphere k kappa [A4 [A6 .. A14]]` (once per interface)");
+    has_asph[k] = true;
+    akappa[k] = (float)c[1];
+    for (size_t m = 2; m < c.size(); m++) acoef[(m - 2) * (size_t)n + k] = (float)c[m];
+  }
   lf_status st = lf_set_lens(ctx, n, stop, nl, radius, thick, ior, semi, (float)sensor_w);
+  if (st == LF_OK && !asphs.empty()) {
+    st = lf_set_lens_aspheres(ctx, n, akappa, LF_MAX_ASPH_COEF, acoef);
+    if (st != LF_OK) {   // the lens stays, one of spheres
+      const std::string why = ctx->err;
+      return lf_fail(ctx, st, "lf_load_lens_file: " + why);
+    }
+  }
   if (st != LF_OK || (coats.empty() && layers.empty())) return st;
   st = layers.empty() ? lf_set_lens_coatings(ctx, n, nl, lam, cth, cidx)
                       : lf_set_lens_coating_stacks(ctx, n, nl, lam, nlay.data(), lth.data(), lidx.data());

@@ -201,6 +201,17 @@ struct alignas(32) LfEventRow {
   int pad[5];
 };
 enum { LF_EV_REFLECT = 1, LF_EV_STOP = 2, LF_EV_FLAT = 4 };
+// ... and, only in the kind bits of a pair-sequence dword (pack_program) of a lens with aspheres (lf_set_lens_aspheres): the row's
+// interface has an aspheric record -- k_march_asph takes asphere_event there (lf_asphere.h).  Never set for any other lens: the
+// kernels that compare the kind against the three bits above never see it.
+enum { LF_EV_ASPH = 8 };
+// the conic constants and even coefficients of the prescription's interfaces (host; lf_set_lens_aspheres): coef[m * n_surfaces + k]
+// multiplies r^(4 + 2 m) on interface k.  n = interfaces whose record is not all zero (0: a lens of spheres).
+struct LfAspheres {
+  int n = 0;
+  float kappa[LF_MAX_SURFACES] = {};
+  float coef[LF_MAX_ASPH_COEF * LF_MAX_SURFACES] = {};
+};
 // A program row as the device walks it: the interface once, the index ratios of the up to three
 // wavelengths that march it together (lf_march.hip, k_march<K>); one 64-byte scalar load.
 // (The program is stored in two levels: a 16-byte header per row -- what is particular to the row --
@@ -545,6 +556,8 @@ struct lf_ctx {
   float raw_semi_ap[LF_MAX_SURFACES] = {};
   float pupil_target_h = 0.0f, pupil_target_z = 0.0f;   // lf_set_pupil_target; h <= 0: the rear element
   LfCoatings coat;                                        // lf_set_lens_coatings / lf_set_lens_coating_stacks (cleared by lf_set_lens)
+  LfAspheres asph;                                        // lf_set_lens_aspheres (cleared by lf_set_lens, kept by lf_focus_lens)
+  bool asph_force = false;                                // lf_test_knob("asph_force"): k_march_asph on a lens of spheres, zero records
   int mask_filter = LF_MASK_NEAREST;                      // lf_set_mask_filter (a setting of the context: nothing clears it)
   std::vector<float> mask_host;                           // the STARBURST slot's texels (occupancy / open radius follow the filter)
   bool ghost_accumulate = false;                          // lf_set_ghost_accumulate
@@ -562,6 +575,7 @@ struct lf_ctx {
   int march_tail_tiles = -1, march_tail_groups = -1;   // lf_test_knob: the tail's size (-1: one round of resident workgroups) / split
   unsigned char* prog_dev = nullptr;           // the packed program: headers, then records (lf_march.hip pack_program)
   size_t prog_cap = 0, prog_rec_off = 0, prog_wrec_off = 0, prog_seq_off = 0;   // bytes; offsets of the records / weight records / pair sequences
+  size_t prog_asph_off = 0;                    // ... of the aspheric records, one per program record (0: the lens has none; lf_march_asph.hip)
   // path culling (lf_cull_prepass.hip, lf_cull.hip): 0 = off (k_march walks every path of every sample), 1 = on, the table is reused
   // while its inputs (lens, pairs, sun, frame, pupil disc, mask, strata) are unchanged, 2 = on, rebuilt at every launch
   int march_cull = 1;
@@ -796,6 +810,13 @@ namespace lfm { struct MarchArgs; }
 lf_status lfk_march_culled(lf_ctx* ctx, const lfm::MarchArgs& a, size_t blocks, size_t dyn_lds);
 // lf_march.hip
 lf_status lfk_cull_prepare(lf_ctx* ctx, int spp);
+// lf_march_asph.hip: the march of a lens with aspheres (or of any lens under lf_test_knob("asph_force")), every path alone;
+// the batched single event; one explicit ray per lane along the sequence of pair (i, j)
+inline bool lf_march_aspheric(const lf_ctx* ctx) { return ctx->asph.n > 0 || ctx->asph_force; }
+lf_status lfk_march_asph(lf_ctx* ctx, const lfm::MarchArgs& a, size_t blocks);
+lf_status lfk_asphere_events(lf_ctx* ctx, const float* consts16, int reflect, int forward, size_t n, const float* d_rays,
+                             float* d_out, int* d_fates);
+lf_status lfk_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, int n, const float* d_xy, const float* d_uv, float* d_out);
 // lf_group.hip: in-place all-gather of equal slabs of u64 on the communicator's stream, ordered after what the main
 // stream has queued and before what it queues next
 lf_status lf_comm_allgather_u64_inplace(lf_ctx* ctx, unsigned long long* base, size_t count_per_rank);

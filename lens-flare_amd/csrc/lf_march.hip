@@ -45,6 +45,7 @@
 #include "lf_internal.h"
 #include "lf_march_events.h"
 #include "lf_march_common.h"
+#include "lf_asphere.h"
 
 namespace {
 
@@ -1169,8 +1170,34 @@ static void pack_program(lf_ctx* ctx, const std::vector<LfEventRow>& rows, const
   for (int k = 0; k < n_recs; k++)
     if (stacked(k)) stack_bytes += (size_t)n_groups * 3 * sizeof(float) * kStackDwords(C.n_layers[surf_of(k)]);
   const size_t stack_off = coat_off + (size_t)n_groups * n_coated * 3 * sizeof(LfCoatK);
-  out.assign(n_coated || stack_bytes ? stack_off + stack_bytes
-                                     : *seq_off + ((size_t)P.total_events + 1) * sizeof(int), 0);
+  size_t prog_bytes = n_coated || stack_bytes ? stack_off + stack_bytes : *seq_off + ((size_t)P.total_events + 1) * sizeof(int);
+  // ... and, only for a lens with aspheres (lf_set_lens_aspheres; or under lf_test_knob("asph_force")), behind everything else:
+  // one LfAsphRec per program record -- kappa, A4 .. A14 of the record's interface, the same for both directions of travel and
+  // every wavelength -- at asph_off + 32 * record.  Any other lens: the buffer is what it always was.
+  const LfAspheres& A = ctx->asph;
+  const bool aspheric = lf_march_aspheric(ctx);
+  auto asph_row = [&](int k) {      // does record k take the Newton path?
+    const int surf = surf_of(k);
+    const LfEventRow& r = row_at(0, first_row[(size_t)k]);
+    if (r.flags & LF_EV_STOP) return false;
+    bool any = A.kappa[surf] != 0.0f;
+    for (int m = 0; m < LF_MAX_ASPH_COEF; m++) any = any || A.coef[(size_t)m * ctx->raw_n + surf] != 0.0f;
+    return A.n > 0 ? any : (ctx->asph_force && r.curv != 0.0f);
+  };
+  const size_t asph_off = (prog_bytes + 63) & ~(size_t)63;
+  ctx->prog_asph_off = aspheric ? asph_off : 0;
+  if (aspheric) prog_bytes = asph_off + (size_t)n_recs * sizeof(lfm::LfAsphRec);
+  out.assign(prog_bytes, 0);
+  if (aspheric)
+    for (int k = 0; k < n_recs; k++) {
+      lfm::LfAsphRec rec{};
+      if (A.n > 0 && asph_row(k)) {
+        const int surf = surf_of(k);
+        rec.kappa = A.kappa[surf];
+        for (int m = 0; m < LF_MAX_ASPH_COEF; m++) rec.a[m] = A.coef[(size_t)m * ctx->raw_n + surf];
+      }
+      std::memcpy(out.data() + asph_off + (size_t)k * sizeof(rec), &rec, sizeof(rec));
+    }
   size_t next_stack = stack_off;
   // the per-pair sequences (read by the weight re-march): one dword per event, record | kind << 16;
   // every (interface, direction) a pair crosses is in the program, so its record exists
@@ -1183,6 +1210,7 @@ static void pack_program(lf_ctx* ctx, const std::vector<LfEventRow>& rows, const
         if (same_record(row_at(0, first_row[k]), r)) id = k;
       if (id < 0) { *ok = false; return; }
       seq[e] = id * (int)sizeof(LfProgRow) | ((r.flags & (LF_EV_REFLECT | LF_EV_STOP | LF_EV_FLAT)) << 16);
+      if (aspheric && asph_row(id)) seq[e] |= LF_EV_ASPH << 16;
     }
   }
   LfProgHdr* hdrs = reinterpret_cast<LfProgHdr*>(out.data());
@@ -1475,6 +1503,12 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
   // the paths a pre-pass found able to reach the light (lf_cull_prepass.hip, lf_cull.hip) -- or every path of every sample
   ctx->cull_reason = lf_cull_reason_of(ctx, a.G);
   ctx->last_march_culled = ctx->cull_reason == LF_CULL_APPLIED;
+  // a lens with aspheres (lf_set_lens_aspheres): its own kernel, every path alone, no table (lf_march_asph.hip)
+  const bool aspheric = lf_march_aspheric(ctx);
+  if (aspheric) {
+    const lf_status st = lfk_march_asph(ctx, a, blocks);
+    if (st != LF_OK) return st;
+  }
   if (ctx->last_march_culled) {
     lf_status st = lfk_cull_prepass(ctx, a.G, spp);
     if (st != LF_OK) return st;
@@ -1491,7 +1525,7 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
   if (ctx->last_march_culled) {
     lf_status st = lfk_march_culled(ctx, a, blocks, dyn_lds);
     if (st != LF_OK) return st;
-  } else {
+  } else if (!aspheric) {
   hipEvent_t ev = lf_timing_begin(ctx, LFK_MARCH);
 #define LF_LAUNCH_MARCH(KK)  do { switch (lf_march_variant(ctx)) { case kVarCoatFilt: LF_LAUNCH_MARCH2(KK, kVarCoatFilt); break; case kVarFilt: LF_LAUNCH_MARCH2(KK, kVarFilt); break; \
                                    case kVarCoat: LF_LAUNCH_MARCH2(KK, kVarCoat); break; case kVarBare: LF_LAUNCH_MARCH2(KK, kVarBare); break; \
