@@ -508,7 +508,8 @@ lf_status lf_coating_reflectance(float n_in, float n_film, float n_out, float th
  * aspheres and launches exactly the kernels it launched before.  lf_set_lens clears the aspheres (they belong to the
  * prescription); lf_focus_lens keeps them.  Refused with LF_ERR_INVALID and a message that names the interface: a
  * value that is not finite, a record on the stop, n_coef outside 0 .. LF_MAX_ASPH_COEF, an interface whose
- * 1 - (1 + kappa) c^2 h^2 is not positive in float at its own semi-aperture h (the conic ends inside the clear aperture).
+ * 1 - (1 + kappa) c^2 h^2 is not positive in float at its own semi-aperture h (the conic ends inside the clear aperture),
+ * a non-zero record on an interface that carries a biconic record (lf_set_lens_biconics).
  * A lens file carries them as `asphere k kappa [A4 [A6 ...]]` lines (lf_load_lens_file).
  * A lens with an asphere is marched by a kernel of its own (k_march_asph: every path alone from the sensor, a fixed
  * number of Newton steps from the base sphere's intersection on the aspheric rows, the unchanged spherical event on all
@@ -546,6 +547,55 @@ lf_status lf_asphere_events(lf_ctx* ctx, float curvature, float conic, int n_coe
  * lf_generate_lens_rays defines them.  Works for any lens; on an aspheric one lf_generate_lens_rays routes through it. */
 lf_status lf_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, size_t n, const float* sensor_xy_mm,
                              const float* pupil_uv, float* out);
+/* BICONIC INTERFACES: cylinders, toroids, the anamorphic flare (no reference counterpart).  Interface k of the installed
+ * lens becomes
+ *   z(x, y) = (cx x^2 + cy y^2) / (1 + sqrt(1 - (1 + kx) cx^2 x^2 - (1 + ky) cy^2 y^2))
+ * x and y the sensor's axes (no rotation angle, no polynomial terms), cy = 1 / radius[k] as lf_set_lens holds it (the y
+ * meridian; 0 for a plane) and
+ *   on[k]        != 0: interface k carries a record
+ *   radius_x[k]  Rx, the x meridian's signed radius of curvature in mm (0 = flat in x), cx = 1 / Rx
+ *   conic_x[k], conic_y[k]   the two conic constants (NULL: zeros)
+ * A circular cylinder with power in x is a flat row with a record Rx != 0; one with power in y a curved row with the
+ * record Rx = 0 -- which is why `on` says where a record is: a record of zeros is one.  So is a record whose 1 / Rx equals
+ * cy with kx = ky = 0, a sphere: it takes the biconic route (the same surface through another event).
+ * Everything paraxial keeps meaning the Y MERIDIAN and changes no bit: lf_paraxial_efl, lf_paraxial_image_scale, the
+ * pupils, lf_focus_lens, lf_aim_at_exit_pupil, lf_get_lens_info's efl_mm; ghost occlusion keeps mapping its shadow rays
+ * through the y-meridian entrance pupil.  The one exception is the hand-over of a flare to a light (lf_set_sun_from_flares,
+ * lf_set_lights_from_flares, lf_set_lights_from_scene): with efl_mm <= 0 the x component of the direction takes the image
+ * scale of the x meridian (lf_get_lens_meridian_scales); a caller's efl_mm > 0 serves both, as for any lens.
+ * on == NULL clears the records; lf_set_lens clears them, lf_focus_lens keeps them.  Refused with LF_ERR_INVALID and a
+ * message that names the interface: a value that is not finite, a record on the stop, a record on an interface with a
+ * non-zero aspheric record (lf_set_lens_aspheres refuses the converse; different interfaces of one lens may carry either
+ * kind), a meridian whose 1 - (1 + k) c^2 h^2 is not positive in float at the semi-aperture h.
+ * A lens file carries them as `biconic k Rx [kx [ky]]` lines (lf_load_lens_file; data/dgauss11_anamorphic.lens).
+ * Such a lens is marched by the aspheric lens's kernel with one more branch (k_march_asph<VAR, true>: a fixed number of
+ * Newton steps from the root of a start quadric, lf_biconic.h); no cull table is built (LF_CULL_ANAMORPHIC); lights, films,
+ * stacks, occlusion, bands and deals work as on any lens; lf_march_path_rays and lf_generate_lens_rays follow the
+ * records; the lens camera's scene image, and lf_get_lens_camera under a lens-camera mode, refuse the lens with
+ * LF_ERR_UNSUPPORTED as they do an aspheric one. */
+lf_status lf_set_lens_biconics(lf_ctx* ctx, int n_surfaces, const int* on, const float* radius_x, const float* conic_x,
+                               const float* conic_y);
+/* what is installed (any pointer may be NULL): arrays of n_surfaces, n_biconic = the interfaces with a record */
+lf_status lf_get_lens_biconics(lf_ctx* ctx, int n_surfaces, int* on, float* radius_x, float* conic_x, float* conic_y,
+                               int* n_biconic);
+/* the paraxial image scales (mm per radian of field angle, lf_paraxial_image_scale at the middle wavelength) of the two
+ * meridians of the installed lens: scale_y of the prescription as lf_set_lens holds it, scale_x of the one with Rx in
+ * place of the radius wherever a biconic record is on (equal for a lens without records).  Either pointer may be NULL. */
+lf_status lf_get_lens_meridian_scales(lf_ctx* ctx, double* scale_x, double* scale_y);
+/* host arithmetic, no device: the sag z (mm) and its slopes dz/dx, dz/dy of such a surface at (x, y), in the float32
+ * arithmetic of the march.  LF_ERR_INVALID beyond the conic's domain. */
+lf_status lf_biconic_sag(float curvature_x, float curvature_y, float conic_x, float conic_y, float x, float y, float* z,
+                         float* dz_dx, float* dz_dy);
+/* host arithmetic, no device: ONE event of ONE ray on a biconic interface, the definition the kernels run (bit for bit:
+ * lf_biconic_events is its device twin).  curvature_x = 1 / Rx (0: flat in x), curvature_y the row's; every other
+ * argument, the ray's conventions, sq, ct and the fates as lf_asphere_event's. */
+lf_status lf_biconic_event(float curvature_x, float curvature_y, float conic_x, float conic_y, float semi_aperture, float n_in,
+                           float n_out, int reflect, int forward, float dzv, const float ray_in[6], float ray_out[6],
+                           float* sq, float* ct, int* fate);
+/* the same event for n rays on the device: rays n x 6 as ray_in, out n x 8 = {ray_out, sq, ct}, fates n ints */
+lf_status lf_biconic_events(lf_ctx* ctx, float curvature_x, float curvature_y, float conic_x, float conic_y, float semi_aperture,
+                            float n_in, float n_out, int reflect, int forward, float dzv, size_t n, const float* rays,
+                            float* out, int* fates);
 /* what lf_set_lens / lf_load_lens_file installed (any pointer may be NULL); efl_mm = lf_paraxial_efl at
  * the middle wavelength (0 for an afocal prescription) */
 lf_status lf_get_lens_info(lf_ctx* ctx, int* n_surfaces, int* stop_index, int* n_lambda, float* sensor_width_mm,
@@ -996,8 +1046,10 @@ typedef enum {
   LF_CULL_AUDIT_REFUTED = 7,        /* an audit ray of a dropped box reached the light: the table was not used (see below) */
   LF_CULL_DISPERSION = 8,           /* the index columns are not monotonic in the wavelength: the two ends of the spectrum
                                        do not bracket what lies between, the pre-pass's dispersion bound does not hold */
-  LF_CULL_ASPHERIC = 9              /* the lens has an aspheric interface (lf_set_lens_aspheres): the pre-pass's bounds were found
+  LF_CULL_ASPHERIC = 9,             /* the lens has an aspheric interface (lf_set_lens_aspheres): the pre-pass's bounds were found
                                        on spherical designs, no table is built and neither pre-pass nor audit launches */
+  LF_CULL_ANAMORPHIC = 10           /* the lens has a biconic interface (lf_set_lens_biconics): likewise, and the pre-pass's boxes
+                                       assume surfaces of revolution */
 } lf_cull_reason;
 lf_status lf_get_cull_reason(lf_ctx* ctx, int* reason);
 /* THE AUDIT.  The pre-pass's bounds are second-order estimates from 15 rays per box: conservative on every
@@ -1109,7 +1161,7 @@ lf_status lf_set_flare_arithmetic(lf_ctx* ctx, int mode);
  * and the counter RNG (MT19937 parity mode is refused: its table has no pupil draws).
  * lf_get_lens_camera: the settings in force (after calibration) and the entrance pupil's z (mm).  With a mode other
  * than 0 it brings table and calibration up to date first, as lf_render_scene_term does, and so fails as that call
- * would: on an aspheric lens (lf_set_lens_aspheres) both return LF_ERR_UNSUPPORTED -- the calibration belongs to a
+ * would: on an aspheric lens (lf_set_lens_aspheres) or one with biconic interfaces (lf_set_lens_biconics) both return LF_ERR_UNSUPPORTED -- the calibration belongs to a
  * scene image that is not built for such a lens, and the getter reports no figure that no frame would use.  With
  * mode 0 it succeeds on any lens. */
 lf_status lf_set_lens_camera(lf_ctx* ctx, int mode, double world_per_mm, double exposure);

@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "lf_load_lens_file", "lf_get_lens_info", "lf_set_lens_coatings", "lf_get_lens_coatings", "lf_coating_reflectance",
     "lf_set_lens_coating_stacks", "lf_get_lens_coating_stacks", "lf_coating_stack_reflectance",
     "lf_set_lens_aspheres", "lf_get_lens_aspheres", "lf_asphere_sag", "lf_asphere_event", "lf_asphere_events", "lf_march_path_rays",
+    "lf_set_lens_biconics", "lf_get_lens_biconics", "lf_get_lens_meridian_scales", "lf_biconic_sag", "lf_biconic_event", "lf_biconic_events",
     "lf_set_mask_filter", "lf_get_mask_filter", "lf_mask_lookup",
     "lf_set_pupil_target", "lf_get_pupil_target", "lf_aim_at_exit_pupil", "lf_paraxial_exit_pupil", "lf_set_ghost_accumulate",
     "lf_set_lens_camera", "lf_get_lens_camera", "lf_set_lens_camera_aim", "lf_paraxial_entrance_pupil", "lf_focus_lens", "lf_focus_lens_from_pupil",
@@ -168,7 +169,7 @@ def load_lens_file(path):
     """Parse a .lens prescription (see data/dgauss11.lens) -> dict of float32 arrays."""
     if not os.path.isabs(path) and not os.path.exists(path):
         path = os.path.join(DATA, path)
-    rows, sensor_w, lambda_nm, coats, layers, asphs = [], 36.0, None, [], [], []
+    rows, sensor_w, lambda_nm, coats, layers, asphs, bics = [], 36.0, None, [], [], [], []
     for line in open(path):
         line = line.split("#")[0].strip()
         if not line:
@@ -191,6 +192,11 @@ def load_lens_file(path):
                 raise ValueError(f"{path}: an asphere line is `asphere k kappa [A4 [A6 .. A14]]`")
             asphs.append((int(t[1]), float(t[2]), [float(v) for v in t[3:]]))
             continue
+        if t[0] == "biconic":        # biconic k Rx [kx [ky]]  (lf_set_lens_biconics; Rx = 0: flat in x)
+            if len(t) < 3 or len(t) > 5:
+                raise ValueError(f"{path}: a biconic line is `biconic k Rx [kx [ky]]`")
+            bics.append((int(t[1]), [float(v) for v in t[2:]]))
+            continue
         rows.append([float(v) for v in t])
     rows = np.array(rows, np.float64)
     n = len(rows)
@@ -212,6 +218,19 @@ def load_lens_file(path):
             conic[k] = kappa
             coef[:len(a), k] = a
         lens["aspheres"] = dict(conic=conic, coef=coef)
+    if bics:
+        on = np.zeros(n, np.int32)
+        rec = np.zeros((3, n), np.float32)       # Rx, kx, ky
+        for k, v in bics:
+            if not 0 <= k < n or on[k]:
+                raise ValueError(f"{path}: bad biconic line for interface {k}")
+            if k == lens["stop"]:
+                raise ValueError(f"{path}: a biconic line on the stop (interface {k})")
+            if "aspheres" in lens and (lens["aspheres"]["conic"][k] != 0 or lens["aspheres"]["coef"][:, k].any()):
+                raise ValueError(f"{path}: interface {k} has an asphere line and a biconic line")
+            on[k] = 1
+            rec[:len(v), k] = v
+        lens["biconics"] = dict(on=on, radius_x=rec[0].copy(), conic_x=rec[1].copy(), conic_y=rec[2].copy())
     if lambda_nm is not None:
         if len(lambda_nm) != ior.shape[0]:
             raise ValueError(f"{path}: lambda_nm lists {len(lambda_nm)} wavelengths for {ior.shape[0]} index columns")
@@ -259,6 +278,37 @@ MAX_COAT_LAYERS = 6      # LF_MAX_COAT_LAYERS
 MAX_ASPH_COEF = 6        # LF_MAX_ASPH_COEF
 CULL_ASPHERIC = 9        # LF_CULL_ASPHERIC
 ASPH_ALIVE, ASPH_MISSED, ASPH_APERTURE, ASPH_TIR = 0, 1, 2, 3   # the fates of lf_asphere_event
+CULL_ANAMORPHIC = 10     # LF_CULL_ANAMORPHIC
+
+
+def biconic_sag(curvature_x, curvature_y, conic_x, conic_y, x, y):
+    """(z, dz/dx, dz/dy) of a biconic surface at (x, y) in the march's float32 arithmetic (lf_biconic_sag, host only)."""
+    z, zx, zy = C.c_float(), C.c_float(), C.c_float()
+    st = load_library().lf_biconic_sag(C.c_float(curvature_x), C.c_float(curvature_y), C.c_float(conic_x), C.c_float(conic_y),
+                                       C.c_float(x), C.c_float(y), C.byref(z), C.byref(zx), C.byref(zy))
+    if st != 0:
+        raise LensFlareError(st, "lf_biconic_sag")
+    return z.value, zx.value, zy.value
+
+
+def biconic_event(curvature_x, curvature_y, conic_x, conic_y, semi_aperture, n_in, n_out, reflect, forward, dzv, rays):
+    """One event on a biconic interface for each of the n x 6 rays {x, y, z, Kx, Ky, Kz}, host arithmetic
+    (lf_biconic_event): (out n x 8 = {ray, sq, ct}, fates n)."""
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    out = np.zeros((len(rays), 8), np.float32)
+    fates = np.zeros(len(rays), np.int32)
+    fn = load_library().lf_biconic_event
+    ro = (C.c_float * 6)()
+    sq, ct, fate = C.c_float(), C.c_float(), C.c_int()
+    consts = (C.c_float(curvature_x), C.c_float(curvature_y), C.c_float(conic_x), C.c_float(conic_y), C.c_float(semi_aperture),
+              C.c_float(n_in), C.c_float(n_out), int(bool(reflect)), int(bool(forward)), C.c_float(dzv))
+    for i in range(len(rays)):
+        st = fn(*consts, _fp(rays[i], C.c_float), ro, C.byref(sq), C.byref(ct), C.byref(fate))
+        if st != 0:
+            raise LensFlareError(st, "lf_biconic_event")
+        out[i, :6] = ro[:]
+        out[i, 6], out[i, 7], fates[i] = sq.value, ct.value, fate.value
+    return out, fates
 
 
 def asphere_sag(curvature, conic, coef, r2):
@@ -977,6 +1027,50 @@ class LensFlare:
             self.set_lens_coating_stacks(c["lambda_nm"], c["n_layers"], c["thickness_nm"], c["index"])
         if "aspheres" in lens:
             self.set_lens_aspheres(lens["aspheres"]["conic"], lens["aspheres"]["coef"])
+        if "biconics" in lens:
+            b = lens["biconics"]
+            self.set_lens_biconics(b["on"], b["radius_x"], b["conic_x"], b["conic_y"])
+
+    def set_lens_biconics(self, on=None, radius_x=None, conic_x=None, conic_y=None):
+        """Biconic records on the installed lens: on[k] != 0 marks interface k, radius_x[k] its x-meridian radius (0: flat in
+        x), conic_x[k] / conic_y[k] its conic constants (None: zeros).  on None clears the records."""
+        if on is None:
+            self._ck(self.lib.lf_set_lens_biconics(self.ctx, 0, None, None, None, None))
+            return
+        on = np.ascontiguousarray(on, np.int32).ravel()
+        arr = lambda v: np.zeros(len(on), np.float32) if v is None else np.ascontiguousarray(v, np.float32).ravel()
+        rx, kx, ky = arr(radius_x), arr(conic_x), arr(conic_y)
+        if not (len(rx) == len(kx) == len(ky) == len(on)):
+            raise ValueError("on, radius_x, conic_x and conic_y hold one value per interface")
+        self._ck(self.lib.lf_set_lens_biconics(self.ctx, len(on), _fp(on, C.c_int), _fp(rx, C.c_float), _fp(kx, C.c_float),
+                                               _fp(ky, C.c_float)))
+
+    def lens_biconics(self):
+        """dict(on, radius_x, conic_x, conic_y (n each), n_biconic) of the installed lens."""
+        n = self.lens_info()["n"]
+        on = np.zeros(n, np.int32)
+        rx, kx, ky = (np.zeros(n, np.float32) for _ in range(3))
+        cnt = C.c_int()
+        self._ck(self.lib.lf_get_lens_biconics(self.ctx, n, _fp(on, C.c_int), _fp(rx, C.c_float), _fp(kx, C.c_float),
+                                               _fp(ky, C.c_float), C.byref(cnt)))
+        return dict(on=on, radius_x=rx, conic_x=kx, conic_y=ky, n_biconic=cnt.value)
+
+    def lens_meridian_scales(self):
+        """(scale_x, scale_y): the paraxial image scales of the x and the y meridian (lf_get_lens_meridian_scales)."""
+        sx, sy = C.c_double(), C.c_double()
+        self._ck(self.lib.lf_get_lens_meridian_scales(self.ctx, C.byref(sx), C.byref(sy)))
+        return sx.value, sy.value
+
+    def biconic_events(self, curvature_x, curvature_y, conic_x, conic_y, semi_aperture, n_in, n_out, reflect, forward, dzv, rays):
+        """biconic_event on the device (lf_biconic_events): the same (out, fates), bit for bit."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        out = np.zeros((len(rays), 8), np.float32)
+        fates = np.zeros(len(rays), np.int32)
+        self._ck(self.lib.lf_biconic_events(self.ctx, C.c_float(curvature_x), C.c_float(curvature_y), C.c_float(conic_x),
+                                            C.c_float(conic_y), C.c_float(semi_aperture), C.c_float(n_in), C.c_float(n_out),
+                                            int(bool(reflect)), int(bool(forward)), C.c_float(dzv), C.c_size_t(len(rays)),
+                                            _fp(rays, C.c_float), _fp(out, C.c_float), _fp(fates, C.c_int)))
+        return out, fates
 
     def set_lens_aspheres(self, conic=None, coef=None):
         """Conic constants conic[k] and even coefficients coef[m, k] (A4, A6, ... of interface k; up to MAX_ASPH_COEF rows)
@@ -1328,7 +1422,7 @@ class LensFlare:
                     reason=self.cull_reason())
 
     CULL_REASONS = ("applied", "off", "no_stop", "too_many_paths", "too_many_samples", "block_too_large", "table_too_full",
-                    "audit_refuted", "dispersion_not_monotonic", "aspheric")
+                    "audit_refuted", "dispersion_not_monotonic", "aspheric", "anamorphic")
 
     def cull_reason(self):
         """why the last trace_ghosts did (not) cull: one of CULL_REASONS (lf_cull_reason)"""

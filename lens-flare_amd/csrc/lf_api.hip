@@ -11,6 +11,7 @@
 #include "lf_internal.h"
 #include "lf_march_events.h"
 #include "lf_asphere.h"
+#include "lf_biconic.h"
 #include "../host/lf_collada.h"
 
 lf_status lf_fail(const lf_ctx* ctx, lf_status st, const std::string& msg) {
@@ -1014,6 +1015,7 @@ lf_status lf_set_lens(lf_ctx* ctx, int n_surfaces, int stop_index, int n_lambda,
   ctx->pupil_target_h = 0.0f; ctx->pupil_target_z = 0.0f;
   ctx->coat = LfCoatings{};
   ctx->asph = LfAspheres{};      // (and its aspheres: a new lens is one of spheres)
+  ctx->bic = LfBiconics{};       // (and its biconic records)
   ctx->lenscam_dirty = true;
   lf_derive_lens(ctx, n_surfaces, stop_index, n_lambda, radius, thickness, ior, semi_aperture,
                  sensor_width_mm);
@@ -1383,7 +1385,23 @@ lf_status lf_paraxial_image_scale(int n, int stop, const float* radius, const fl
 }
 
 // the light flare `flare` of the flare state stands for: its direction through the image scale, its radiance
-static lf_status light_of_flare(lf_ctx* ctx, const char* who, const LfFlares& f, int flare, double* efl_mm, float dir[3], float rad[3]) {
+// the x-meridian prescription of a lens with biconic records (lf_set_lens_biconics): Rx where a record is on, the row's
+// radius elsewhere
+static void meridian_x_radii(const lf_ctx* ctx, float rx[LF_MAX_SURFACES]) {
+  for (int k = 0; k < ctx->raw_n; k++) rx[k] = ctx->bic.on[k] ? ctx->bic.rx[k] : ctx->raw_radius[k];
+}
+
+// (efl_x_mm: the image scale of the x meridian -- *efl_mm's value unless the lens has biconic records and the caller left
+// the scale to the prescription, efl_mm <= 0: then the paraxial scale of the x-radii prescription)
+static lf_status light_of_flare(lf_ctx* ctx, const char* who, const LfFlares& f, int flare, double* efl_mm, double* efl_x_mm,
+                                float dir[3], float rad[3]) {
+  if (!(*efl_mm > 0.0) && ctx->bic.n > 0) {
+    float rx[LF_MAX_SURFACES];
+    meridian_x_radii(ctx, rx);
+    if (!paraxial_image_scale(ctx->raw_n, ctx->raw_stop, rx, ctx->raw_thickness,
+                              ctx->raw_ior + (size_t)(ctx->lens.n_lambda / 2) * ctx->raw_n, efl_x_mm) || !(*efl_x_mm > 0.0))
+      return lf_fail(ctx, LF_ERR_INVALID, std::string(who) + ": the prescription's x meridian images no distant point on its sensor");
+  }
   if (!(*efl_mm > 0.0)) {
     // the image scale of THIS sensor position: the focal length when the sensor sits in the focal plane (the
     // shipped prescriptions), the chief ray's landing height per unit field angle when lf_focus_lens has moved it
@@ -1391,8 +1409,9 @@ static lf_status light_of_flare(lf_ctx* ctx, const char* who, const LfFlares& f,
                               ctx->raw_ior + (size_t)(ctx->lens.n_lambda / 2) * ctx->raw_n, efl_mm) || !(*efl_mm > 0.0))
       return lf_fail(ctx, LF_ERR_INVALID, std::string(who) + ": the prescription images no distant point on its sensor");
   }
+  if (!(*efl_x_mm > 0.0)) *efl_x_mm = *efl_mm;
   const double sw = ctx->sensor_w_mm, sh = sw * (double)ctx->H / (double)ctx->W;
-  dir[0] = (float)((f.origin[flare][0] - 0.5) * sw / *efl_mm);
+  dir[0] = (float)((f.origin[flare][0] - 0.5) * sw / *efl_x_mm);
   dir[1] = (float)((f.origin[flare][1] - 0.5) * sh / *efl_mm);
   dir[2] = -1.0f;
   for (int c = 0; c < 3; c++) rad[c] = (float)f.radiance[flare][c];
@@ -1410,7 +1429,8 @@ lf_status lf_set_sun_from_flares(lf_ctx* ctx, int flare, double efl_mm, float an
   LF_HIP(ctx, hipMemcpy(&f, ctx->flares, sizeof(f), hipMemcpyDeviceToHost));
   if (flare >= f.n_flares) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_sun_from_flares: no such flare in the frame");
   float dir[3], rad[3];
-  const lf_status st = light_of_flare(ctx, "lf_set_sun_from_flares", f, flare, &efl_mm, dir, rad);
+  double efl_x_mm = efl_mm > 0.0 ? efl_mm : 0.0;
+  const lf_status st = light_of_flare(ctx, "lf_set_sun_from_flares", f, flare, &efl_mm, &efl_x_mm, dir, rad);
   if (st != LF_OK) return st;
   return lf_set_sun(ctx, dir, rad, angular_radius);
 }
@@ -1431,8 +1451,9 @@ lf_status lf_set_lights_from_flares(lf_ctx* ctx, double efl_mm, float angular_ra
     return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lights_from_flares: " + std::to_string(std::max(f.n_flares, f.n_in_frame)) + " flares in the frame, one launch marches at most LF_MAX_LIGHTS = " +
                                             std::to_string(LF_MAX_LIGHTS) + " lights (compose launches with lf_set_ghost_accumulate)");
   float dir[3 * LF_MAX_LIGHTS], rad[3 * LF_MAX_LIGHTS], ar[LF_MAX_LIGHTS];
+  double efl_x_mm = efl_mm > 0.0 ? efl_mm : 0.0;
   for (int k = 0; k < f.n_flares; k++) {
-    const lf_status st = light_of_flare(ctx, "lf_set_lights_from_flares", f, k, &efl_mm, dir + 3 * k, rad + 3 * k);
+    const lf_status st = light_of_flare(ctx, "lf_set_lights_from_flares", f, k, &efl_mm, &efl_x_mm, dir + 3 * k, rad + 3 * k);
     if (st != LF_OK) return st;
     ar[k] = angular_radius;
   }
@@ -1471,8 +1492,9 @@ static lf_status set_lights_from_scene(lf_ctx* ctx, const std::string& who, bool
     LfFlares f;
     LF_HIP(ctx, hipMemcpy(&f, ctx->flares, sizeof(f), hipMemcpyDeviceToHost));
     if (f.n_flares > LF_MAX_LIGHTS || f.n_in_frame > LF_MAX_LIGHTS) return lf_fail(ctx, LF_ERR_INVALID, too_many);
+    double efl_x_mm = efl_mm > 0.0 ? efl_mm : 0.0;
     for (int k = 0; k < f.n_flares; k++) {
-      const lf_status st = light_of_flare(ctx, who.c_str(), f, k, &efl_mm, vec + GF * n, rad + 3 * n);
+      const lf_status st = light_of_flare(ctx, who.c_str(), f, k, &efl_mm, &efl_x_mm, vec + GF * n, rad + 3 * n);
       if (st != LF_OK) return st;
       kind[n] = LF_LIGHT_DIRECTIONAL; ar[n] = angular_radius;
       n++; n_dir++;
@@ -1919,7 +1941,7 @@ lf_status lf_generate_lens_rays(lf_ctx* ctx, int lambda, size_t n, const float* 
     return lf_fail(ctx, LF_ERR_INVALID, "lf_generate_lens_rays: wavelength index / count out of range");
   if (n == 0) return LF_OK;
   // (an aspheric lens: the primary table knows spheres only -- the same ray along the primary path's own sequence)
-  if (ctx->asph.n > 0) return lf_march_path_rays(ctx, lambda, -1, -1, n, sensor_xy_mm, pupil_uv, out);
+  if (ctx->asph.n > 0 || ctx->bic.n > 0) return lf_march_path_rays(ctx, lambda, -1, -1, n, sensor_xy_mm, pupil_uv, out);
   LF_HIP(ctx, hipSetDevice(ctx->device));
   float *d_xy = nullptr, *d_uv = nullptr, *d_out = nullptr;
   hipError_t e = hipMalloc((void**)&d_xy, n * 2 * sizeof(float));
@@ -2438,6 +2460,7 @@ lf_status lf_set_lens_aspheres(lf_ctx* ctx, int n_surfaces, const float* conic, 
     if (!finite) return lf_fail(ctx, LF_ERR_INVALID, who + ": a value is not finite");
     if (!any) continue;
     if (k == ctx->raw_stop) return lf_fail(ctx, LF_ERR_INVALID, who + ": the stop cannot carry an aspheric record");
+    if (ctx->bic.on[k]) return lf_fail(ctx, LF_ERR_INVALID, who + ": the interface carries a biconic record (lf_set_lens_biconics)");
     // the conic must cover the clear aperture: 1 - (1 + kappa) c^2 h^2 > 0 in the float arithmetic of the sag
     const LfSurfaceDev& s = ctx->lens.surf[k];
     const float kc2 = (1.0f + conic[k]) * (s.curv * s.curv);
@@ -2573,6 +2596,149 @@ lf_status lf_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, size_t n, co
   return LF_OK;
 }
 
+// ---------------------------------------------------------------- biconic interfaces ------------
+lf_status lf_set_lens_biconics(lf_ctx* ctx, int n_surfaces, const int* on, const float* radius_x, const float* conic_x,
+                               const float* conic_y) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lens_biconics before lf_set_lens");
+  if (!on) {   // every interface a surface of revolution
+    ctx->bic = LfBiconics{};
+    ctx->events_dirty = true;
+    ctx->lenscam_dirty = true;
+    return LF_OK;
+  }
+  if (n_surfaces != ctx->raw_n) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_biconics: n_surfaces differs from the installed lens");
+  if (!radius_x) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_biconics: radius_x is NULL");
+  LfBiconics B;
+  for (int k = 0; k < n_surfaces; k++) {
+    if (!on[k]) continue;
+    const std::string who = "lf_set_lens_biconics: interface " + std::to_string(k);
+    const float rx = radius_x[k], kx = conic_x ? conic_x[k] : 0.0f, ky = conic_y ? conic_y[k] : 0.0f;
+    if (!std::isfinite(rx) || !std::isfinite(kx) || !std::isfinite(ky)) return lf_fail(ctx, LF_ERR_INVALID, who + ": a value is not finite");
+    if (k == ctx->raw_stop) return lf_fail(ctx, LF_ERR_INVALID, who + ": the stop cannot carry a biconic record");
+    bool asph = ctx->asph.kappa[k] != 0.0f;
+    for (int m = 0; m < LF_MAX_ASPH_COEF; m++) asph = asph || ctx->asph.coef[(size_t)m * n_surfaces + k] != 0.0f;
+    if (asph) return lf_fail(ctx, LF_ERR_INVALID, who + ": the interface carries an aspheric record (lf_set_lens_aspheres)");
+    // either meridian's conic must cover the clear aperture: 1 - (1 + k) c^2 h^2 > 0 in the float arithmetic of the sag
+    // (on the disc x^2 + y^2 <= h^2 the root's argument is smallest on the axis of the larger (1 + k) c^2)
+    const LfSurfaceDev& s = ctx->lens.surf[k];
+    const float cx = rx == 0.0f ? 0.0f : 1.0f / rx;
+    if (!(fmaf(-((1.0f + kx) * cx * cx), s.h2, 1.0f) > 0.0f))
+      return lf_fail(ctx, LF_ERR_INVALID, who + ": 1 - (1 + kx) cx^2 h^2 is not positive at its semi-aperture (the x meridian's conic ends inside the clear aperture)");
+    if (!(fmaf(-((1.0f + ky) * s.curv * s.curv), s.h2, 1.0f) > 0.0f))
+      return lf_fail(ctx, LF_ERR_INVALID, who + ": 1 - (1 + ky) cy^2 h^2 is not positive at its semi-aperture (the y meridian's conic ends inside the clear aperture)");
+    B.on[k] = 1; B.rx[k] = rx; B.kx[k] = kx; B.ky[k] = ky;
+    B.n++;
+  }
+  ctx->bic = B;
+  ctx->events_dirty = true;
+  ctx->lenscam_dirty = true;
+  return LF_OK;
+}
+
+lf_status lf_get_lens_biconics(lf_ctx* ctx, int n_surfaces, int* on, float* radius_x, float* conic_x, float* conic_y,
+                               int* n_biconic) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_get_lens_biconics before lf_set_lens");
+  if (n_surfaces != ctx->raw_n) return lf_fail(ctx, LF_ERR_INVALID, "lf_get_lens_biconics: n_surfaces differs from the installed lens");
+  const LfBiconics& B = ctx->bic;
+  for (int k = 0; k < n_surfaces; k++) {
+    if (on) on[k] = B.on[k];
+    if (radius_x) radius_x[k] = B.rx[k];
+    if (conic_x) conic_x[k] = B.kx[k];
+    if (conic_y) conic_y[k] = B.ky[k];
+  }
+  if (n_biconic) *n_biconic = B.n;
+  return LF_OK;
+}
+
+lf_status lf_get_lens_meridian_scales(lf_ctx* ctx, double* scale_x, double* scale_y) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_get_lens_meridian_scales before lf_set_lens");
+  float rx[LF_MAX_SURFACES];
+  meridian_x_radii(ctx, rx);
+  const float* ior = ctx->raw_ior + (size_t)(ctx->lens.n_lambda / 2) * ctx->raw_n;
+  double sx = 0.0, sy = 0.0;
+  if (!paraxial_image_scale(ctx->raw_n, ctx->raw_stop, ctx->raw_radius, ctx->raw_thickness, ior, &sy) ||
+      !paraxial_image_scale(ctx->raw_n, ctx->raw_stop, rx, ctx->raw_thickness, ior, &sx))
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_get_lens_meridian_scales: a meridian of the prescription images no distant point on its sensor");
+  if (scale_x) *scale_x = sx;
+  if (scale_y) *scale_y = sy;
+  return LF_OK;
+}
+
+static bool bic_args_ok(float cx, float cy, float kx, float ky) {
+  return std::isfinite(cx) && std::isfinite(cy) && std::isfinite(kx) && std::isfinite(ky);
+}
+
+lf_status lf_biconic_sag(float curvature_x, float curvature_y, float conic_x, float conic_y, float x, float y, float* z,
+                         float* dz_dx, float* dz_dy) {
+  if (!bic_args_ok(curvature_x, curvature_y, conic_x, conic_y) || !std::isfinite(x) || !std::isfinite(y)) return LF_ERR_INVALID;
+  float zz, zx, zy;
+  if (!lfm::lf_bic_sag(curvature_x, curvature_y, conic_x, conic_y, x, y, zz, zx, zy)) return LF_ERR_INVALID;
+  if (z) *z = zz;
+  if (dz_dx) *dz_dx = zx;
+  if (dz_dy) *dz_dy = zy;
+  return LF_OK;
+}
+
+// the sixteen constants of one event as the host twin and the kernel take them: {cy, delta, h2, sgn, dzv, 0, 0, 0, cx, kx, ky, 0 ..}
+static bool bic_event_consts(float cx, float cy, float kx, float ky, float semi_aperture, float n_in, float n_out, int forward,
+                             float dzv, float out[16]) {
+  if (!bic_args_ok(cx, cy, kx, ky) || !(semi_aperture > 0.0f) || !std::isfinite(semi_aperture) || !(n_in >= 1.0f) ||
+      !(n_out >= 1.0f) || !std::isfinite(n_in) || !std::isfinite(n_out) || !std::isfinite(dzv))
+    return false;
+  const float n_in2 = n_in * n_in, n_out2 = n_out * n_out;   // (as pack_program forms a row's delta)
+  for (int i = 0; i < 16; i++) out[i] = 0.0f;
+  out[0] = cy; out[1] = n_out2 - n_in2; out[2] = semi_aperture * semi_aperture; out[3] = forward ? 1.0f : -1.0f;
+  out[4] = dzv; out[8] = cx; out[9] = kx; out[10] = ky;
+  return true;
+}
+
+lf_status lf_biconic_event(float curvature_x, float curvature_y, float conic_x, float conic_y, float semi_aperture, float n_in,
+                           float n_out, int reflect, int forward, float dzv, const float ray_in[6], float ray_out[6],
+                           float* sq, float* ct, int* fate) {
+  float k[16];
+  if (!ray_in || !ray_out || !fate || !bic_event_consts(curvature_x, curvature_y, conic_x, conic_y, semi_aperture, n_in, n_out, forward, dzv, k))
+    return LF_ERR_INVALID;
+  const lfm::LfBicRec rec{k[8], k[9], k[10], {}};
+  float px = ray_in[0], py = ray_in[1], hz = ray_in[2], dx = ray_in[3], dy = ray_in[4], dz = ray_in[5], r2;
+  const lfm::AsphHit h = lfm::lf_bic_event(px, py, hz, r2, dx, dy, dz, k[4], k[0], rec, k[1], k[2], reflect != 0, k[3]);
+  ray_out[0] = px; ray_out[1] = py; ray_out[2] = hz; ray_out[3] = dx; ray_out[4] = dy; ray_out[5] = dz;
+  if (sq) *sq = h.sq;
+  if (ct) *ct = h.ct;
+  *fate = h.fate;
+  return LF_OK;
+}
+
+lf_status lf_biconic_events(lf_ctx* ctx, float curvature_x, float curvature_y, float conic_x, float conic_y, float semi_aperture,
+                            float n_in, float n_out, int reflect, int forward, float dzv, size_t n, const float* rays,
+                            float* out, int* fates) {
+  if (!ctx || (n > 0 && (!rays || !out || !fates))) return LF_ERR_INVALID;
+  float k[16];
+  if (n > 0x7fffffffull / 8 || !bic_event_consts(curvature_x, curvature_y, conic_x, conic_y, semi_aperture, n_in, n_out, forward, dzv, k))
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_biconic_events: constants not finite / out of range, or too many rays for one call");
+  if (n == 0) return LF_OK;
+  LF_HIP(ctx, hipSetDevice(ctx->device));
+  float *d_rays = nullptr, *d_out = nullptr;
+  int* d_fates = nullptr;
+  hipError_t e = hipMalloc((void**)&d_rays, n * 6 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, n * 8 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_fates, n * sizeof(int));
+  if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * 6 * sizeof(float), hipMemcpyHostToDevice);
+  lf_status st = LF_OK;
+  if (e == hipSuccess) st = lfk_biconic_events(ctx, k, reflect, n, d_rays, d_out, d_fates);
+  if (e == hipSuccess && st == LF_OK) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && st == LF_OK) e = hipMemcpy(out, d_out, n * 8 * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && st == LF_OK) e = hipMemcpy(fates, d_fates, n * sizeof(int), hipMemcpyDeviceToHost);
+  if (d_rays) (void)hipFree(d_rays);
+  if (d_out) (void)hipFree(d_out);
+  if (d_fates) (void)hipFree(d_fates);
+  if (st != LF_OK) return st;
+  LF_HIP(ctx, e);
+  return LF_OK;
+}
+
 // ---------------------------------------------------------------- lens file ---------------------
 lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
   if (!ctx || !path) return LF_ERR_INVALID;
@@ -2584,7 +2750,8 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
   // `layer k thickness_nm m_1 .. m_L | m` (appends a layer to interface k's stack, scene side first:
   // lf_set_lens_coating_stacks; needs lambda_nm; not on an interface with a `coating` line)
   // `asphere k kappa [A4 [A6 ...]]` (interface k's conic constant and even coefficients: lf_set_lens_aspheres)
-  std::vector<std::vector<double>> rows, coats, layers, asphs;
+  // `biconic k Rx [kx [ky]]` (interface k's x-meridian radius, 0 = flat in x, and conic constants: lf_set_lens_biconics)
+  std::vector<std::vector<double>> rows, coats, layers, asphs, bics;
   std::vector<double> lambdas;
   bool lambda_line = false, lambda_bad = false;
   double sensor_w = 36.0;
@@ -2594,7 +2761,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (char* h = std::strchr(line, '#')) *h = 0;
     std::vector<double> v;
     char* p = line;
-    int keyword = 0;   // 1 sensor_width_mm, 2 lambda_nm, 3 coating, 4 layer, 5 asphere
+    int keyword = 0;   // 1 sensor_width_mm, 2 lambda_nm, 3 coating, 4 layer, 5 asphere, 6 biconic
     while (*p) {
       while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') p++;
       if (!*p) break;
@@ -2603,6 +2770,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
       if (v.empty() && !keyword && std::strncmp(p, "coating", 7) == 0) { keyword = 3; p += 7; continue; }
       if (v.empty() && !keyword && std::strncmp(p, "layer", 5) == 0) { keyword = 4; p += 5; continue; }
       if (v.empty() && !keyword && std::strncmp(p, "asphere", 7) == 0) { keyword = 5; p += 7; continue; }
+      if (v.empty() && !keyword && std::strncmp(p, "biconic", 7) == 0) { keyword = 6; p += 7; continue; }
       char* e = nullptr;
       const double d = std::strtod(p, &e);
       if (e == p) {
@@ -2618,6 +2786,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (keyword == 3) { coats.push_back(v); continue; }
     if (keyword == 4) { layers.push_back(v); continue; }
     if (keyword == 5) { asphs.push_back(v); continue; }
+    if (keyword == 6) { bics.push_back(v); continue; }
     if (keyword == 1) { if (v.size() != 1) { bad = true; break; } sensor_w = v[0]; continue; }
     if (!v.empty()) rows.push_back(v);
   }
@@ -2679,11 +2848,30 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     akappa[k] = (float)c[1];
     for (size_t m = 2; m < c.size(); m++) acoef[(m - 2) * (size_t)n + k] = (float)c[m];
   }
+  int bon[LF_MAX_SURFACES] = {};
+  float brx[LF_MAX_SURFACES] = {}, bkx[LF_MAX_SURFACES] = {}, bky[LF_MAX_SURFACES] = {};
+  for (const auto& c : bics) {
+    const int k = c.size() >= 2 ? (int)c[0] : -1;
+    if (k < 0 || k >= n || (double)k != c[0] || (int)c.size() > 4 || bon[k])
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_load_lens_file: a biconic line is `biconic k Rx [kx [ky]]` (once per interface)");
+    bon[k] = 1;
+    brx[k] = (float)c[1];
+    if (c.size() > 2) bkx[k] = (float)c[2];
+    if (c.size() > 3) bky[k] = (float)c[3];
+  }
   lf_status st = lf_set_lens(ctx, n, stop, nl, radius, thick, ior, semi, (float)sensor_w);
+  if (st == LF_OK && !bics.empty()) {   // (before the aspheres: an interface with both lines is refused by their setter)
+    st = lf_set_lens_biconics(ctx, n, bon, brx, bkx, bky);
+    if (st != LF_OK) {   // the lens stays, one of spheres
+      const std::string why = ctx->err;
+      return lf_fail(ctx, st, "lf_load_lens_file: " + why);
+    }
+  }
   if (st == LF_OK && !asphs.empty()) {
     st = lf_set_lens_aspheres(ctx, n, akappa, LF_MAX_ASPH_COEF, acoef);
     if (st != LF_OK) {   // the lens stays, one of spheres
       const std::string why = ctx->err;
+      (void)lf_set_lens_biconics(ctx, 0, nullptr, nullptr, nullptr, nullptr);
       return lf_fail(ctx, st, "lf_load_lens_file: " + why);
     }
   }

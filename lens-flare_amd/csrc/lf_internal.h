@@ -205,12 +205,25 @@ enum { LF_EV_REFLECT = 1, LF_EV_STOP = 2, LF_EV_FLAT = 4 };
 // interface has an aspheric record -- k_march_asph takes asphere_event there (lf_asphere.h).  Never set for any other lens: the
 // kernels that compare the kind against the three bits above never see it.
 enum { LF_EV_ASPH = 8 };
+// ... and, likewise only for a lens with a biconic record (lf_set_lens_biconics): the row's interface is a biconic -- the BIC
+// instantiations of k_march_asph take biconic_event there (lf_biconic.h); the row's slot of the aspheric table holds {1/Rx, kx, ky}.
+enum { LF_EV_BICONIC = 16 };
 // the conic constants and even coefficients of the prescription's interfaces (host; lf_set_lens_aspheres): coef[m * n_surfaces + k]
 // multiplies r^(4 + 2 m) on interface k.  n = interfaces whose record is not all zero (0: a lens of spheres).
 struct LfAspheres {
   int n = 0;
   float kappa[LF_MAX_SURFACES] = {};
   float coef[LF_MAX_ASPH_COEF * LF_MAX_SURFACES] = {};
+};
+// the biconic records of the prescription's interfaces (host; lf_set_lens_biconics): on[k] != 0: interface k is a biconic of
+// x-meridian radius rx[k] (0: flat in x) and conic constants kx[k], ky[k] on the row's own (y-meridian) curvature.  A record
+// of zeros is a record (a cylinder with power in y): `on` says whether there is one.  n = the records (0: none).
+struct LfBiconics {
+  int n = 0;
+  int on[LF_MAX_SURFACES] = {};
+  float rx[LF_MAX_SURFACES] = {};
+  float kx[LF_MAX_SURFACES] = {};
+  float ky[LF_MAX_SURFACES] = {};
 };
 // A program row as the device walks it: the interface once, the index ratios of the up to three
 // wavelengths that march it together (lf_march.hip, k_march<K>); one 64-byte scalar load.
@@ -557,6 +570,7 @@ struct lf_ctx {
   float pupil_target_h = 0.0f, pupil_target_z = 0.0f;   // lf_set_pupil_target; h <= 0: the rear element
   LfCoatings coat;                                        // lf_set_lens_coatings / lf_set_lens_coating_stacks (cleared by lf_set_lens)
   LfAspheres asph;                                        // lf_set_lens_aspheres (cleared by lf_set_lens, kept by lf_focus_lens)
+  LfBiconics bic;                                         // lf_set_lens_biconics (cleared by lf_set_lens, kept by lf_focus_lens)
   bool asph_force = false;                                // lf_test_knob("asph_force"): k_march_asph on a lens of spheres, zero records
   int mask_filter = LF_MASK_NEAREST;                      // lf_set_mask_filter (a setting of the context: nothing clears it)
   std::vector<float> mask_host;                           // the STARBURST slot's texels (occupancy / open radius follow the filter)
@@ -812,10 +826,14 @@ lf_status lfk_march_culled(lf_ctx* ctx, const lfm::MarchArgs& a, size_t blocks, 
 lf_status lfk_cull_prepare(lf_ctx* ctx, int spp);
 // lf_march_asph.hip: the march of a lens with aspheres (or of any lens under lf_test_knob("asph_force")), every path alone;
 // the batched single event; one explicit ray per lane along the sequence of pair (i, j)
-inline bool lf_march_aspheric(const lf_ctx* ctx) { return ctx->asph.n > 0 || ctx->asph_force; }
+// (a lens with a biconic record, lf_set_lens_biconics, takes the same route through the kernel's BIC instantiations)
+inline bool lf_march_biconic(const lf_ctx* ctx) { return ctx->bic.n > 0; }
+inline bool lf_march_aspheric(const lf_ctx* ctx) { return ctx->asph.n > 0 || ctx->asph_force || lf_march_biconic(ctx); }
 lf_status lfk_march_asph(lf_ctx* ctx, const lfm::MarchArgs& a, size_t blocks);
 lf_status lfk_asphere_events(lf_ctx* ctx, const float* consts16, int reflect, int forward, size_t n, const float* d_rays,
                              float* d_out, int* d_fates);
+lf_status lfk_biconic_events(lf_ctx* ctx, const float* consts16, int reflect, size_t n, const float* d_rays, float* d_out,
+                             int* d_fates);
 lf_status lfk_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, int n, const float* d_xy, const float* d_uv, float* d_out);
 // lf_group.hip: in-place all-gather of equal slabs of u64 on the communicator's stream, ordered after what the main
 // stream has queued and before what it queues next

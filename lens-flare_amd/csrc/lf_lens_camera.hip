@@ -156,6 +156,9 @@ lf_status lf_lenscam_prepare(lf_ctx* ctx) {
   if (ctx->asph.n > 0)
     return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lens camera: the lens has aspheric interfaces (lf_set_lens_aspheres) -- the scene term's primary "
                                             "path knows spherical interfaces only; lf_generate_lens_rays marches them");
+  if (ctx->bic.n > 0)
+    return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lens camera: the lens has biconic interfaces (lf_set_lens_biconics) -- the scene term's primary "
+                                            "path knows spherical interfaces only; lf_generate_lens_rays marches them");
   if (!ctx->lenscam_dirty) return LF_OK;
   if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lens camera: no prescription (lf_set_lens / lf_load_lens_file)");
   if (!ctx->ap[LF_APERTURE_STARBURST].valid)

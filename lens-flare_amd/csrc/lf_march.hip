@@ -1184,6 +1184,9 @@ static void pack_program(lf_ctx* ctx, const std::vector<LfEventRow>& rows, const
     for (int m = 0; m < LF_MAX_ASPH_COEF; m++) any = any || A.coef[(size_t)m * ctx->raw_n + surf] != 0.0f;
     return A.n > 0 ? any : (ctx->asph_force && r.curv != 0.0f);
   };
+  // (a biconic record, lf_set_lens_biconics, takes the interface's slot of the same table: {1/Rx, kx, ky}; bit LF_EV_BICONIC)
+  const LfBiconics& B = ctx->bic;
+  auto bic_row = [&](int k) { return B.n > 0 && B.on[surf_of(k)] != 0 && !(row_at(0, first_row[(size_t)k]).flags & LF_EV_STOP); };
   const size_t asph_off = (prog_bytes + 63) & ~(size_t)63;
   ctx->prog_asph_off = aspheric ? asph_off : 0;
   if (aspheric) prog_bytes = asph_off + (size_t)n_recs * sizeof(lfm::LfAsphRec);
@@ -1191,7 +1194,12 @@ static void pack_program(lf_ctx* ctx, const std::vector<LfEventRow>& rows, const
   if (aspheric)
     for (int k = 0; k < n_recs; k++) {
       lfm::LfAsphRec rec{};
-      if (A.n > 0 && asph_row(k)) {
+      if (bic_row(k)) {
+        const int surf = surf_of(k);
+        rec.kappa = B.rx[surf] == 0.0f ? 0.0f : 1.0f / B.rx[surf];
+        rec.a[0] = B.kx[surf];
+        rec.a[1] = B.ky[surf];
+      } else if (A.n > 0 && asph_row(k)) {
         const int surf = surf_of(k);
         rec.kappa = A.kappa[surf];
         for (int m = 0; m < LF_MAX_ASPH_COEF; m++) rec.a[m] = A.coef[(size_t)m * ctx->raw_n + surf];
@@ -1210,7 +1218,8 @@ static void pack_program(lf_ctx* ctx, const std::vector<LfEventRow>& rows, const
         if (same_record(row_at(0, first_row[k]), r)) id = k;
       if (id < 0) { *ok = false; return; }
       seq[e] = id * (int)sizeof(LfProgRow) | ((r.flags & (LF_EV_REFLECT | LF_EV_STOP | LF_EV_FLAT)) << 16);
-      if (aspheric && asph_row(id)) seq[e] |= LF_EV_ASPH << 16;
+      if (aspheric && bic_row(id)) seq[e] |= LF_EV_BICONIC << 16;
+      else if (aspheric && asph_row(id)) seq[e] |= LF_EV_ASPH << 16;
     }
   }
   LfProgHdr* hdrs = reinterpret_cast<LfProgHdr*>(out.data());

@@ -6,7 +6,10 @@
 //                          both reaches are the code that exists.  A row whose sequence dword carries LF_EV_ASPH takes
 //                          asphere_event (lf_asphere.h) behind a wave-uniform branch, every other row surface_event, bit for
 //                          bit as in the other kernels.  Launched iff the lens has a record (or under "asph_force").
+//   k_march_asph<VAR, true> the same kernel for a lens with a BICONIC record (lf_set_lens_biconics; lf_biconic.h): one more
+//                          wave-uniform branch, on LF_EV_BICONIC, to biconic_event.  BIC = false is the code it was.
 //   k_asphere_events       lf_asphere_events: one event for n rays, the device twin of lf_asphere_event
+//   k_biconic_events       lf_biconic_events: the device twin of lf_biconic_event
 //   k_march_path_rays      lf_march_path_rays: one explicit ray per lane along the sequence of pair (i, j), with its weight
 // The sample starts are sample_start's (lf_march_events.h): the path tree's rays for the same inputs, bit for bit.
 #include <hip/hip_runtime.h>
@@ -20,6 +23,7 @@
 #include "lf_march_events.h"
 #include "lf_march_common.h"
 #include "lf_asphere.h"
+#include "lf_biconic.h"
 
 using namespace lfm;
 
@@ -46,7 +50,7 @@ struct AsphTally {
 
 // One row of a path for wavelength slot j of its group, W as surface_event's: the stop, an aspheric row, or the spherical
 // event.  *stop: the row was the stop (its dead lanes count as clipped).
-template <bool W, int VAR>
+template <bool W, int VAR, bool BIC = false>
 __device__ __forceinline__ lanemask asph_row(Ray& r, unsigned cur, int j, const LfProgRow* __restrict__ recs,
                                              const LfWeightRow* __restrict__ wrecs, const LfWeightRow* __restrict__ wrec_table,
                                              const LfAsphRec* __restrict__ asph_table, const float* __restrict__ mask,
@@ -69,6 +73,11 @@ __device__ __forceinline__ lanemask asph_row(Ray& r, unsigned cur, int j, const 
     if (VAR & kVarCoat) coat = load_wrec_dword(wrecs, off + (unsigned)offsetof(LfWeightRow, coat));
   }
   const float delta = j == 0 ? wr.delta[0] : j == 1 ? wr.delta[1] : wr.delta[2];
+  if (BIC && (kind & LF_EV_BICONIC)) {   // wave-uniform: a biconic record in the aspheric record's slot
+    const LfAsphRec rec = load_asph(asph_table, off >> 1);
+    return biconic_event<W>(r, wr.dzv, wr.curv, LfBicRec{rec.kappa, rec.a[0], rec.a[1], {}}, delta, wr.h2,
+                            (kind & LF_EV_REFLECT) != 0, wr.sgn, geom_ok, fs, fo, fi, CoatSel<VAR>{wrec_table, coat, j});
+  }
   if (kind & LF_EV_ASPH) {   // wave-uniform: the interface has a record (one per program record: 32 of its 64 bytes' offset)
     const LfAsphRec rec = load_asph(asph_table, off >> 1);
     return asphere_event<W>(r, wr.dzv, wr.curv, rec, delta, wr.h2, (kind & LF_EV_REFLECT) != 0, wr.sgn, geom_ok, fs, fo, fi,
@@ -82,7 +91,7 @@ __device__ __forceinline__ lanemask asph_row(Ray& r, unsigned cur, int j, const 
 
 // path q of one sensor sample per lane, every wavelength on its own: geometry, tallies, the lights' pre-test, the weighted
 // march of the lit lanes, the lit epilogue into the tile's LDS sums
-template <int VAR>
+template <int VAR, bool BIC = false>
 __device__ __forceinline__ void march_asph_path(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                                                 const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
                                                 const LfWeightRow* __restrict__ wrec_table,
@@ -108,7 +117,7 @@ __device__ __forceinline__ void march_asph_path(const LfLensDev* __restrict__ le
     for (int e = 0; e < n_ev && nlive != 0u; e++) {
       lanemask gv;
       bool stop;
-      const lanemask ok = asph_row<false, VAR>(r[0], (unsigned)seq[e], j, recs, wrecs, wrec_table, asph_table, mask, a.inv_stop_h,
+      const lanemask ok = asph_row<false, VAR, BIC>(r[0], (unsigned)seq[e], j, recs, wrecs, wrec_table, asph_table, mask, a.inv_stop_h,
                                                a.mw, a.mh, gv, stop);
       const lanemask died = alive[0] & ~ok;
       if (died != 0ull) {
@@ -134,14 +143,14 @@ __device__ __forceinline__ void march_asph_path(const LfLensDev* __restrict__ le
     for (int e = 0; e < n_ev; e++) {
       lanemask gv;
       bool stop;
-      (void)asph_row<true, VAR>(rw, (unsigned)seq[e], j, recs, wrecs, wrec_table, asph_table, mask, a.inv_stop_h, a.mw, a.mh, gv,
+      (void)asph_row<true, VAR, BIC>(rw, (unsigned)seq[e], j, recs, wrecs, wrec_table, asph_table, mask, a.inv_stop_h, a.mw, a.mh, gv,
                                 stop);
     }
     lights_epilogue<VAR>(lens, s_chan, rw, ((lit[0] >> lane) & 1ull) != 0ull, l, &s_acc[lane * 3], T.n_light);
   }
 }
 
-template <int VAR>
+template <int VAR, bool BIC = false>
 __global__ __launch_bounds__(64 * kAsphWgWaves) void k_march_asph(
     const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs, const int* __restrict__ seq_table,
     const LfProgRow* __restrict__ rec_table, const LfWeightRow* __restrict__ wrec_table,
@@ -191,7 +200,7 @@ __global__ __launch_bounds__(64 * kAsphWgWaves) void k_march_asph(
       const int s = sg + k * sgroups;       // wave-uniform
       const StartRay s0 = sample_start(spec, x, y, s);
       for (int q = 0; q < n_paths; q++)
-        march_asph_path<VAR>(lens, pairs, seq_table, rec_table, wrec_table, asph_table, mask, a, K, q, active_mask, s0, lane, s_acc,
+        march_asph_path<VAR, BIC>(lens, pairs, seq_table, rec_table, wrec_table, asph_table, mask, a, K, q, active_mask, s0, lane, s_acc,
                              s_chan, T);
     }
 
@@ -242,10 +251,24 @@ __global__ __launch_bounds__(256) void k_asphere_events(AsphEventArgs c, int ref
   fates[i] = h.fate;
 }
 
+// ---- lf_biconic_events: the host's lf_biconic_event, n times; {cy, delta, h2, sgn, dzv, 0, 0, 0, cx, kx, ky, 0 ...} -----------
+__global__ __launch_bounds__(256) void k_biconic_events(AsphEventArgs c, int reflect, int n, const float* __restrict__ rays,
+                                                        float* __restrict__ out, int* __restrict__ fates) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const LfBicRec rec{c.k[8], c.k[9], c.k[10], {}};
+  const float* ri = rays + 6 * (size_t)i;
+  float px = ri[0], py = ri[1], hz = ri[2], dx = ri[3], dy = ri[4], dz = ri[5], r2;
+  const AsphHit h = lf_bic_event(px, py, hz, r2, dx, dy, dz, c.k[4], c.k[0], rec, c.k[1], c.k[2], reflect != 0, c.k[3]);
+  float* o = out + 8 * (size_t)i;
+  o[0] = px; o[1] = py; o[2] = hz; o[3] = dx; o[4] = dy; o[5] = dz; o[6] = h.sq; o[7] = h.ct;
+  fates[i] = h.fate;
+}
+
 // ---- lf_march_path_rays: the sequence of pair (i, j) for ONE wavelength, one row per event (host: build_path_table) -------
 struct alignas(32) LfPathRow {
   float dzv, curv, ch, c2, sc, h2, sgn;
-  int kind;        // LF_EV_REFLECT | LF_EV_STOP | LF_EV_FLAT | LF_EV_ASPH
+  int kind;        // LF_EV_REFLECT | LF_EV_STOP | LF_EV_FLAT | LF_EV_ASPH | LF_EV_BICONIC (then `asph` holds {1/Rx, kx, ky})
   float cn22, rn2, delta, fs, fo, fi;
   int coated;      // 0 bare; 1: a film, `coat` holds its constants; else 2 | the byte offset, from this row, of its stack record
   int pad;
@@ -268,7 +291,7 @@ struct PathCoat {
   __device__ __forceinline__ StackPlain stack() const { return StackPlain{(const int*)((const char*)row + (row->coated & ~3))}; }
 };
 
-template <bool FILT, bool COAT>
+template <bool FILT, bool COAT, bool BIC = false>
 __global__ __launch_bounds__(256) void k_march_path_rays(const LfLensDev* __restrict__ lens, const LfPathDev* __restrict__ P,
                                                          const float* __restrict__ mask, int mw, int mh, int n,
                                                          const float* __restrict__ sensor_xy, const float* __restrict__ pupil_uv,
@@ -289,6 +312,10 @@ __global__ __launch_bounds__(256) void k_march_path_rays(const LfLensDev* __rest
     const bool reflect = (w.kind & LF_EV_REFLECT) != 0;
     if (w.kind & LF_EV_STOP) {
       ok = stop_event<true, FILT>(r, w.dzv, w.h2, P->inv_stop_h, mask, mw, mh);
+    } else if (BIC && (w.kind & LF_EV_BICONIC)) {
+      const LfBicRec rec{w.asph.kappa, w.asph.a[0], w.asph.a[1], {}};
+      if (COAT) ok = biconic_event<true>(r, w.dzv, w.curv, rec, w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo, w.fi, PathCoat{&w});
+      else ok = biconic_event<true>(r, w.dzv, w.curv, rec, w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo, w.fi);
     } else if (w.kind & LF_EV_ASPH) {
       if (COAT) ok = asphere_event<true>(r, w.dzv, w.curv, w.asph, w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo, w.fi, PathCoat{&w});
       else ok = asphere_event<true>(r, w.dzv, w.curv, w.asph, w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo, w.fi);
@@ -353,7 +380,13 @@ lf_status build_path_table(lf_ctx* ctx, int l, int i, int j, std::vector<unsigne
     }
     bool any = A.kappa[k] != 0.0f;
     for (int m = 0; m < LF_MAX_ASPH_COEF; m++) any = any || A.coef[(size_t)m * L.n_surf + k] != 0.0f;
-    if (A.n > 0 ? any : (ctx->asph_force && s.curv != 0.0f)) {
+    const LfBiconics& B = ctx->bic;
+    if (B.n > 0 && B.on[k]) {
+      w.kind |= LF_EV_BICONIC;
+      w.asph.kappa = B.rx[k] == 0.0f ? 0.0f : 1.0f / B.rx[k];
+      w.asph.a[0] = B.kx[k];
+      w.asph.a[1] = B.ky[k];
+    } else if (A.n > 0 ? any : (ctx->asph_force && s.curv != 0.0f)) {
       w.kind |= LF_EV_ASPH;
       w.asph.kappa = A.kappa[k];
       for (int m = 0; m < LF_MAX_ASPH_COEF; m++) w.asph.a[m] = A.coef[(size_t)m * L.n_surf + k];
@@ -385,6 +418,16 @@ lf_status lfk_asphere_events(lf_ctx* ctx, const float* consts16, int reflect, in
   return LF_OK;
 }
 
+lf_status lfk_biconic_events(lf_ctx* ctx, const float* consts16, int reflect, size_t n, const float* d_rays, float* d_out,
+                             int* d_fates) {
+  AsphEventArgs c;
+  std::memcpy(c.k, consts16, sizeof(c.k));
+  hipLaunchKernelGGL(k_biconic_events, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, c, reflect, (int)n, d_rays,
+                     d_out, d_fates);
+  LF_HIP(ctx, hipGetLastError());
+  return LF_OK;
+}
+
 lf_status lfk_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, int n, const float* d_xy, const float* d_uv, float* d_out) {
   const LfApertureDev& m = ctx->ap[LF_APERTURE_STARBURST];
   ctx->lens.pitch = ctx->sensor_w_mm / (float)std::max(1, ctx->W);
@@ -397,13 +440,18 @@ lf_status lfk_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, int n, cons
   if (e == hipSuccess) e = hipMemcpyAsync(ctx->lens_dev, &ctx->lens, sizeof(LfLensDev), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
     const bool filt = ctx->mask_filter == LF_MASK_BILINEAR, coat = ctx->coat.n > 0;
-#define LF_LAUNCH_PATH(FF, CC)                                                                                          \
-  hipLaunchKernelGGL((k_march_path_rays<FF, CC>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,        \
+#define LF_LAUNCH_PATH(FF, CC, BB)                                                                                      \
+  hipLaunchKernelGGL((k_march_path_rays<FF, CC, BB>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,    \
                      ctx->lens_dev, (const LfPathDev*)d_tab, m.texels, m.w, m.h, n, d_xy, d_uv, d_out)
-    if (filt && coat) LF_LAUNCH_PATH(true, true);
-    else if (filt) LF_LAUNCH_PATH(true, false);
-    else if (coat) LF_LAUNCH_PATH(false, true);
-    else LF_LAUNCH_PATH(false, false);
+    if (lf_march_biconic(ctx)) {   // (a lens with a biconic record: the instantiations that know the branch)
+      if (filt && coat) LF_LAUNCH_PATH(true, true, true);
+      else if (filt) LF_LAUNCH_PATH(true, false, true);
+      else if (coat) LF_LAUNCH_PATH(false, true, true);
+      else LF_LAUNCH_PATH(false, false, true);
+    } else if (filt && coat) LF_LAUNCH_PATH(true, true, false);
+    else if (filt) LF_LAUNCH_PATH(true, false, false);
+    else if (coat) LF_LAUNCH_PATH(false, true, false);
+    else LF_LAUNCH_PATH(false, false, false);
 #undef LF_LAUNCH_PATH
     e = hipGetLastError();
   }
@@ -421,9 +469,12 @@ lf_status lfk_march_asph(lf_ctx* ctx, const MarchArgs& a, size_t blocks) {
   constexpr int kGen = kVarLights | kVarNear | kVarArea;
   const int var = kGen | (ctx->ghost_occlusion ? kVarOccl : 0) | (ctx->mask_filter == LF_MASK_BILINEAR ? kVarFilt : 0) |
                   (ctx->coat.n > 0 ? (kVarCoat | kVarStack) : 0);
+  const bool bic = lf_march_biconic(ctx);   // (a biconic record: the same kernel with the branch that knows it)
   hipEvent_t ev = lf_timing_begin(ctx, LFK_MARCH);
 #define LF_LAUNCH_ASPH(VV)                                                                                               \
-  hipLaunchKernelGGL((k_march_asph<VV>), dim3((unsigned)blocks), dim3(64 * kAsphWgWaves), 0, ctx->stream, ctx->lens_dev,  \
+  if (bic) LF_LAUNCH_ASPH2(VV, true); else LF_LAUNCH_ASPH2(VV, false)
+#define LF_LAUNCH_ASPH2(VV, BB)                                                                                          \
+  hipLaunchKernelGGL((k_march_asph<VV, BB>), dim3((unsigned)blocks), dim3(64 * kAsphWgWaves), 0, ctx->stream, ctx->lens_dev,  \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                                    \
                      (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),                                              \
                      (const LfWeightRow*)(ctx->prog_dev + ctx->prog_wrec_off),                                           \
@@ -440,6 +491,7 @@ lf_status lfk_march_asph(lf_ctx* ctx, const MarchArgs& a, size_t blocks) {
     default: LF_LAUNCH_ASPH(kGen | kVarOccl | kVarCoat | kVarStack | kVarFilt); break;
   }
 #undef LF_LAUNCH_ASPH
+#undef LF_LAUNCH_ASPH2
   lf_timing_end(ctx, LFK_MARCH, ev);
   LF_HIP(ctx, hipGetLastError());
   return LF_OK;
