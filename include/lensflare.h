@@ -515,8 +515,9 @@ lf_status lf_coating_reflectance(float n_in, float n_film, float n_out, float th
  * number of Newton steps from the base sphere's intersection on the aspheric rows, the unchanged spherical event on all
  * others); no cull table is built for it (lf_get_cull_reason: LF_CULL_ASPHERIC).  Films and stacks, every kind of light,
  * ghost occlusion, bands and deals work as on any lens.  The lens camera's scene image (lf_set_lens_camera,
- * lf_render_scene_term) refuses an aspheric lens with LF_ERR_UNSUPPORTED, and so does lf_get_lens_camera while a
- * lens-camera mode is on (it would calibrate that image); lf_generate_lens_rays works. */
+ * lf_render_scene_term) refuses an aspheric lens with LF_ERR_UNSUPPORTED under the default setting, and so does
+ * lf_get_lens_camera while a lens-camera mode is on (it would calibrate that image); lf_generate_lens_rays works.
+ * lf_set_lens_camera_surfaces(LF_LENSCAM_SURFACES_ALL) lifts the refusal: the scene kernel then marches the records. */
 lf_status lf_set_lens_aspheres(lf_ctx* ctx, int n_surfaces, const float* conic, int n_coef, const float* coef);
 /* what is installed (any pointer may be NULL): conic[n_surfaces], coef[LF_MAX_ASPH_COEF * n_surfaces] laid out as the
  * setter's with n_coef = LF_MAX_ASPH_COEF, n_aspheric = the interfaces whose record is not all zero */
@@ -572,7 +573,7 @@ lf_status lf_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, size_t n, co
  * Newton steps from the root of a start quadric, lf_biconic.h); no cull table is built (LF_CULL_ANAMORPHIC); lights, films,
  * stacks, occlusion, bands and deals work as on any lens; lf_march_path_rays and lf_generate_lens_rays follow the
  * records; the lens camera's scene image, and lf_get_lens_camera under a lens-camera mode, refuse the lens with
- * LF_ERR_UNSUPPORTED as they do an aspheric one. */
+ * LF_ERR_UNSUPPORTED under the default setting as they do an aspheric one (lf_set_lens_camera_surfaces lifts both). */
 lf_status lf_set_lens_biconics(lf_ctx* ctx, int n_surfaces, const int* on, const float* radius_x, const float* conic_x,
                                const float* conic_y);
 /* what is installed (any pointer may be NULL): arrays of n_surfaces, n_biconic = the interfaces with a record */
@@ -1161,9 +1162,10 @@ lf_status lf_set_flare_arithmetic(lf_ctx* ctx, int mode);
  * and the counter RNG (MT19937 parity mode is refused: its table has no pupil draws).
  * lf_get_lens_camera: the settings in force (after calibration) and the entrance pupil's z (mm).  With a mode other
  * than 0 it brings table and calibration up to date first, as lf_render_scene_term does, and so fails as that call
- * would: on an aspheric lens (lf_set_lens_aspheres) or one with biconic interfaces (lf_set_lens_biconics) both return LF_ERR_UNSUPPORTED -- the calibration belongs to a
- * scene image that is not built for such a lens, and the getter reports no figure that no frame would use.  With
- * mode 0 it succeeds on any lens. */
+ * would: on an aspheric lens (lf_set_lens_aspheres) or one with biconic interfaces (lf_set_lens_biconics) both return
+ * LF_ERR_UNSUPPORTED under the default setting (lf_set_lens_camera_surfaces below) -- the calibration belongs to a
+ * scene image that the default does not form for such a lens, and the getter reports no figure that no frame would use.
+ * With mode 0 it succeeds on any lens. */
 lf_status lf_set_lens_camera(lf_ctx* ctx, int mode, double world_per_mm, double exposure);
 lf_status lf_get_lens_camera(lf_ctx* ctx, int* mode, double* world_per_mm, double* exposure,
                              double* entrance_pupil_z_mm);
@@ -1176,6 +1178,32 @@ lf_status lf_get_lens_camera(lf_ctx* ctx, int* mode, double* world_per_mm, doubl
  * of its circumscribed circle); the march's own sampling is not touched.  Same expectation; the exposure
  * calibration follows. */
 lf_status lf_set_lens_camera_aim(lf_ctx* ctx, float margin);
+/* Which interfaces the lens camera's primary path may meet (a setting of the context: nothing clears it).
+ *   LF_LENSCAM_SURFACES_SPHERICAL (default)  spheres, flats and the stop: every refusal above, every message and every bit of
+ *                                            a frame as they always were
+ *   LF_LENSCAM_SURFACES_ALL                  lf_render_scene_term and lf_get_lens_camera also accept a lens with aspheric and / or
+ *                                            biconic records: the scene kernel marches a recorded row with the event of
+ *                                            lf_march_path_rays (a fixed number of Newton steps), every other row as before --
+ *                                            the scene image such a lens forms: an anamorphic lens's squeeze and oval bokeh, where
+ *                                            its ghosts belong.  A lens without records launches the kernels it always launched
+ *                                            and renders the same frame bit for bit.
+ * Focus (lf_focus_lens), the entrance pupil (where the camera position sits in the lens) and the exit-pupil aim
+ * (lf_set_lens_camera_aim) keep meaning the y meridian's paraxial quantities: for an anamorphic lens a convention about
+ * where the camera sits, not an approximation of the image, which real rays form.  The exposure calibration follows the
+ * records (it goes through lf_generate_lens_rays).  The per-lane test kernel (lf_test_knob("scene_compact", 0)) has no
+ * instantiation for records: LF_ERR_UNSUPPORTED.  Any other value: LF_ERR_INVALID.  A change re-derives table and calibration. */
+typedef enum { LF_LENSCAM_SURFACES_SPHERICAL = 0, LF_LENSCAM_SURFACES_ALL = 1 } lf_lenscam_surfaces;
+lf_status lf_set_lens_camera_surfaces(lf_ctx* ctx, int which);
+lf_status lf_get_lens_camera_surfaces(lf_ctx* ctx, int* which);
+/* The lens camera's samples, as the device draws them: out[(i * ns_aa + s) * 4 ..] = {X, Y, pa, pb} -- the sensor point in mm
+ * and the pupil-square coordinates in [-1, 1]^2 of the march's sample s = 0 .. ns_aa-1 of pixel pixels[i] = x + y W --
+ * computed on the device by the functions the scene kernels call, so bit for bit the values their start ray is aimed from.
+ * lf_generate_lens_rays(lambda, XY, uv) on them gives, bit for bit, the exit ray and weight the scene kernel carries into
+ * the scene for that sample under the march's disc (lf_set_lens_camera_aim(0)): a host or a float64 tracer can follow the
+ * lens camera sample by sample, for any kind of lens.  Needs lf_set_frame, lf_set_params (ns_aa >= 1) and lf_set_lens
+ * (LF_ERR_STATE) and the counter RNG, lf_set_jitter_counter; the samples follow lf_set_tile_stride and
+ * lf_set_pupil_subcells.  MT19937 parity mode or a pixel outside the frame: LF_ERR_INVALID. */
+lf_status lf_lens_camera_samples(lf_ctx* ctx, size_t n_pixels, const int* pixels, float* out);
 /* the paraxial image of the stop's centre through the interfaces IN FRONT of it (host arithmetic with
  * the reference's T / R operators, pathtracer.cpp:527-533): its z in lens space (the front vertex is
  * z = 0, the scene at z < 0; typically a few mm > 0, inside the lens) and its lateral magnification */

@@ -54,7 +54,8 @@ ABI_SYMBOLS = [
     "lf_set_lens_biconics", "lf_get_lens_biconics", "lf_get_lens_meridian_scales", "lf_biconic_sag", "lf_biconic_event", "lf_biconic_events",
     "lf_set_mask_filter", "lf_get_mask_filter", "lf_mask_lookup",
     "lf_set_pupil_target", "lf_get_pupil_target", "lf_aim_at_exit_pupil", "lf_paraxial_exit_pupil", "lf_set_ghost_accumulate",
-    "lf_set_lens_camera", "lf_get_lens_camera", "lf_set_lens_camera_aim", "lf_paraxial_entrance_pupil", "lf_focus_lens", "lf_focus_lens_from_pupil",
+    "lf_set_lens_camera", "lf_get_lens_camera", "lf_set_lens_camera_aim", "lf_set_lens_camera_surfaces", "lf_get_lens_camera_surfaces",
+    "lf_lens_camera_samples", "lf_paraxial_entrance_pupil", "lf_focus_lens", "lf_focus_lens_from_pupil",
     "lf_get_scene_counters", "lf_reset_scene_counters", "lf_set_flare_arithmetic",
     "lf_comm_get_unique_id", "lf_comm_init_rank", "lf_comm_gather", "lf_comm_gather_async", "lf_comm_wait",
     "lf_comm_destroy", "lf_comm_available", "lf_comm_info", "lf_comm_test", "lf_comm_abort",
@@ -421,6 +422,9 @@ def light_lobe_factors(kind, vec, angular_radius, rays):
 # where the shadow ray of a point light ends under ghost occlusion (lf_set_ghost_occlusion_reach): at the sky (the default: occlusion
 # with a point light installed is refused) or at the light
 OCCLUSION_REACH_SKY, OCCLUSION_REACH_LIGHT = 0, 1
+# which interfaces the lens camera's primary path may meet (lf_set_lens_camera_surfaces): spheres, flats and the stop (the default: a
+# lens with aspheric or biconic records is refused, as it always was), or every kind the geometric lens knows
+LENSCAM_SURFACES_SPHERICAL, LENSCAM_SURFACES_ALL = 0, 1
 
 
 def ghost_shadow_reach(kind, vec, rays, world_per_mm):
@@ -822,6 +826,7 @@ class LensFlare:
     def set_params(self, ns_aa=1, flare_radius=25.0, flare_intensity=1.0):
         self._ck(self.lib.lf_set_params(self.ctx, int(ns_aa), C.c_double(flare_radius),
                                         C.c_double(flare_intensity)))
+        self._ns_aa = int(ns_aa)
 
     # ---- inputs
     def set_aperture(self, slot, texels):
@@ -1588,6 +1593,30 @@ class LensFlare:
     def set_lens_camera_aim(self, margin=0.0):
         """> 0: the lens camera's samples aim at the exit pupil's image x margin (0: at the march's disc)."""
         self._ck(self.lib.lf_set_lens_camera_aim(self.ctx, C.c_float(margin)))
+
+    def set_lens_camera_surfaces(self, which=LENSCAM_SURFACES_SPHERICAL):
+        """LENSCAM_SURFACES_ALL: render_scene_term and lens_camera() accept a lens with aspheric and / or biconic records (the
+        scene kernel marches them); LENSCAM_SURFACES_SPHERICAL (the default) refuses such a lens as before."""
+        if isinstance(which, bool) or not isinstance(which, (int, np.integer)):
+            raise ValueError("set_lens_camera_surfaces: LENSCAM_SURFACES_SPHERICAL (0) or LENSCAM_SURFACES_ALL (1)")
+        self._ck(self.lib.lf_set_lens_camera_surfaces(self.ctx, int(which)))
+
+    def lens_camera_surfaces(self):
+        which = C.c_int(-1)
+        self._ck(self.lib.lf_get_lens_camera_surfaces(self.ctx, C.byref(which)))
+        return which.value
+
+    def lens_camera_samples(self, pixels):
+        """(n_pix, ns_aa, 4) float32 {X, Y, pa, pb}: the sensor point (mm) and the pupil-square coordinates of the lens camera's
+        samples 0 .. ns_aa-1 of the listed pixels (p = x + y W), as the device draws them; generate_lens_rays(lam, s[..., 0:2],
+        s[..., 2:4]) gives the exit ray and weight the scene kernel carries into the scene for each."""
+        pix = np.ascontiguousarray(pixels, np.int32).ravel()
+        ns_aa = getattr(self, "_ns_aa", None)     # (what set_params gave the context: the samples per pixel)
+        if ns_aa is None or ns_aa < 1:
+            raise LensFlareError(4, "lens_camera_samples before set_params (ns_aa samples per pixel)")
+        out = np.zeros((len(pix), ns_aa, 4), np.float32)
+        self._ck(self.lib.lf_lens_camera_samples(self.ctx, C.c_size_t(len(pix)), _fp(pix, C.c_int), _fp(out, C.c_float)))
+        return out
 
     def lens_camera(self):
         m, w, e, z = C.c_int(), C.c_double(), C.c_double(), C.c_double()

@@ -538,7 +538,7 @@ lf_status lf_destroy(lf_ctx* ctx) {
                   ctx->prog_dev, ctx->sun_lights_dev,
                   ctx->scene_dev.nodes, ctx->scene_dev.prims, ctx->scene_dev.normals, ctx->scene_dev.materials,
                   ctx->scene_dev.lights, ctx->env_block, ctx->probe_dev, ctx->scene_counters_dev,
-                  ctx->primary_dev, ctx->cull_dev, ctx->cull_lists.list[0], ctx->cull_lists.list[1], ctx->cull_counts, ctx->cull_popc_dev,
+                  ctx->primary_dev, ctx->primary_surf_dev, ctx->cull_dev, ctx->cull_lists.list[0], ctx->cull_lists.list[1], ctx->cull_counts, ctx->cull_popc_dev,
                   ctx->tail_acc, ctx->tail_done};
   for (void* p : ptrs) if (p) (void)hipFree(p);
   if (ctx->own_stream && ctx->stream) (void)hipStreamDestroy(ctx->stream);

@@ -435,6 +435,15 @@ struct LfPrimaryDev {
 };
 // the device allocation behind the table: every interface's stack records at their largest
 constexpr size_t kPrimaryStackBytes = (size_t)LF_MAX_SURFACES * LF_MAX_LAMBDA * 4 * (4 + 5 * LF_MAX_COAT_LAYERS);
+// The records of a lens with aspheric / biconic interfaces, beside the table in an allocation of their own (LfPrimaryRow keeps
+// its layout: the kernels read it with compile-time offsets): per primary row e a kind word -- 0, LF_EV_ASPH or LF_EV_BICONIC --
+// and a 32-byte slot in LfAsphRec's layout (lf_asphere.h; a biconic record {1/Rx, kx, ky} sits in the same slot, as it does in
+// the march's table).  Built and uploaded by lf_upload_primary_table only for a lens that has records; read by
+// primary_path_general (lf_primary_general.h) under LF_LENSCAM_SURFACES_ALL.
+struct alignas(32) LfPrimarySurfDev {
+  int kind[LF_MAX_SURFACES];
+  alignas(32) float rec[LF_MAX_SURFACES][8];
+};
 // what k_scene_term's lens mode needs beside the table (kernel argument, by value)
 struct LfLensCamArgs {
   int mode;              // 1 = one reference wavelength carries R, G and B; 2 = one ray per wavelength
@@ -551,6 +560,8 @@ struct lf_ctx {
   float lenscam_pupil_h = 0.0f, lenscam_pupil_z = 0.0f, lenscam_geom_norm = 0.0f;   // its own disc (margin > 0)
   bool lenscam_dirty = true;          // table / calibration older than the lens, the mask or the pupil target
   LfPrimaryDev* primary_dev = nullptr;
+  int lenscam_surfaces = LF_LENSCAM_SURFACES_SPHERICAL;   // lf_set_lens_camera_surfaces (a setting of the context: nothing clears it)
+  LfPrimarySurfDev* primary_surf_dev = nullptr;           // the records of the primary rows (allocated for the first lens that has any)
 
   // geometric
   LfLensDev lens{};
@@ -829,6 +840,18 @@ lf_status lfk_cull_prepare(lf_ctx* ctx, int spp);
 // (a lens with a biconic record, lf_set_lens_biconics, takes the same route through the kernel's BIC instantiations)
 inline bool lf_march_biconic(const lf_ctx* ctx) { return ctx->bic.n > 0; }
 inline bool lf_march_aspheric(const lf_ctx* ctx) { return ctx->asph.n > 0 || ctx->asph_force || lf_march_biconic(ctx); }
+// is there a record on glass interface k, and of which kind: 0, LF_EV_BICONIC or LF_EV_ASPH.  ONE predicate for the rows of
+// lf_march_path_rays (build_path_table) and of the lens camera's primary table (lf_upload_primary_table), so that
+// lf_generate_lens_rays and the scene kernel agree on which rows are recorded.
+inline int lf_surface_record_kind(const lf_ctx* ctx, int k) {
+  const LfAspheres& A = ctx->asph;
+  const int n_surf = ctx->lens.n_surf;
+  bool any = A.kappa[k] != 0.0f;
+  for (int m = 0; m < LF_MAX_ASPH_COEF; m++) any = any || A.coef[(size_t)m * n_surf + k] != 0.0f;
+  if (ctx->bic.n > 0 && ctx->bic.on[k]) return LF_EV_BICONIC;
+  if (A.n > 0 ? any : (ctx->asph_force && ctx->lens.surf[k].curv != 0.0f)) return LF_EV_ASPH;
+  return 0;
+}
 lf_status lfk_march_asph(lf_ctx* ctx, const lfm::MarchArgs& a, size_t blocks);
 lf_status lfk_asphere_events(lf_ctx* ctx, const float* consts16, int reflect, int forward, size_t n, const float* d_rays,
                              float* d_out, int* d_fates);

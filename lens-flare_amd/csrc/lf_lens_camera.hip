@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "lf_internal.h"
+#include "lf_march_events.h"
 
 // host: one row per interface in the order the primary path meets them, constants as pack_program
 // derives them for a ray travelling -z (n_in = the medium behind the interface, n_out = in front)
@@ -75,6 +76,30 @@ lf_status lf_upload_primary_table(lf_ctx* ctx) {
   // (the context's stream is non-blocking: a kernel that still reads the previous table must finish first)
   LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
   LF_HIP(ctx, hipMemcpy(ctx->primary_dev, buf.data(), buf.size(), hipMemcpyHostToDevice));
+  // the records of a lens that has any, row by row (LfPrimarySurfDev): which rows carry one is lf_march_path_rays's own
+  // predicate, so that lf_generate_lens_rays and the scene kernel march the same surfaces.  A lens of spheres uploads nothing.
+  if (ctx->asph.n > 0 || ctx->bic.n > 0) {
+    std::vector<unsigned char> sbuf(sizeof(LfPrimarySurfDev), 0);
+    LfPrimarySurfDev& S = *reinterpret_cast<LfPrimarySurfDev*>(sbuf.data());
+    const LfAspheres& A = ctx->asph;
+    const LfBiconics& B = ctx->bic;
+    for (int e = 0; e < L.n_surf; e++) {
+      const int k = L.n_surf - 1 - e;
+      if (L.surf[k].is_stop != 0.0f) continue;
+      const int kind = lf_surface_record_kind(ctx, k);
+      S.kind[e] = kind;
+      if (kind == LF_EV_BICONIC) {
+        S.rec[e][0] = B.rx[k] == 0.0f ? 0.0f : 1.0f / B.rx[k];
+        S.rec[e][1] = B.kx[k];
+        S.rec[e][2] = B.ky[k];
+      } else if (kind == LF_EV_ASPH) {
+        S.rec[e][0] = A.kappa[k];
+        for (int m = 0; m < LF_MAX_ASPH_COEF; m++) S.rec[e][1 + m] = A.coef[(size_t)m * L.n_surf + k];
+      }
+    }
+    if (!ctx->primary_surf_dev) LF_HIP(ctx, hipMalloc((void**)&ctx->primary_surf_dev, sbuf.size()));
+    LF_HIP(ctx, hipMemcpy(ctx->primary_surf_dev, sbuf.data(), sbuf.size(), hipMemcpyHostToDevice));
+  }
   return LF_OK;
 }
 
@@ -153,10 +178,13 @@ static lf_status calibrate_exposure(lf_ctx* ctx, double* exposure) {
 }
 
 lf_status lf_lenscam_prepare(lf_ctx* ctx) {
-  if (ctx->asph.n > 0)
+  // (the default setting, LF_LENSCAM_SURFACES_SPHERICAL, refuses a lens with records as it always has; under
+  // LF_LENSCAM_SURFACES_ALL the scene kernel marches them: lf_set_lens_camera_surfaces)
+  const bool spherical_only = ctx->lenscam_surfaces == LF_LENSCAM_SURFACES_SPHERICAL;
+  if (spherical_only && ctx->asph.n > 0)
     return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lens camera: the lens has aspheric interfaces (lf_set_lens_aspheres) -- the scene term's primary "
                                             "path knows spherical interfaces only; lf_generate_lens_rays marches them");
-  if (ctx->bic.n > 0)
+  if (spherical_only && ctx->bic.n > 0)
     return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lens camera: the lens has biconic interfaces (lf_set_lens_biconics) -- the scene term's primary "
                                             "path knows spherical interfaces only; lf_generate_lens_rays marches them");
   if (!ctx->lenscam_dirty) return LF_OK;
@@ -200,7 +228,79 @@ lf_status lf_lenscam_prepare(lf_ctx* ctx) {
   return LF_OK;
 }
 
+// lf_lens_camera_samples: the sensor point and the pupil-square coordinates of the lens camera's sample s of pixel p -- the
+// march's sample, from the device functions the scene kernels call (lf_march_events.h sample_point: what sample_start_in hands
+// to aim_at_pupil), so the values are the kernels' bit for bit.  One thread per (listed pixel, sample); the host has checked
+// the pixel indices against the frame.
+namespace {
+__global__ __launch_bounds__(256) void k_lenscam_samples(LfLensCamArgs lc, uint2 key, int ns_aa, size_t n, const int* __restrict__ pixels,
+                                                         float* __restrict__ out) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n * (size_t)ns_aa) return;
+  const int p = pixels[i / (size_t)ns_aa], s = (int)(i % (size_t)ns_aa);
+  lfm::SampleSpec spec;
+  spec.W = lc.W; spec.xs = lc.xs; spec.G = lc.G; spec.inv_G = lc.inv_G; spec.sub_bits = lc.sub_bits; spec.inv_sub = lc.inv_sub;
+  spec.key = key; spec.pitch = lc.pitch; spec.half_w = lc.half_w; spec.half_h = lc.half_h;
+  spec.pupil_h = lc.pupil_h; spec.vz = lc.vz; spec.geom_norm = lc.geom_norm;
+  const lfm::SamplePoint q = lfm::sample_point(spec, p % lc.W, p / lc.W, s);
+  float* o = out + 4 * i;
+  o[0] = q.X; o[1] = q.Y; o[2] = q.pa; o[3] = q.pb;
+}
+}  // namespace
+
 extern "C" {
+
+lf_status lf_set_lens_camera_surfaces(lf_ctx* ctx, int which) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (which != LF_LENSCAM_SURFACES_SPHERICAL && which != LF_LENSCAM_SURFACES_ALL)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_camera_surfaces: LF_LENSCAM_SURFACES_SPHERICAL (0) or LF_LENSCAM_SURFACES_ALL (1)");
+  if (which != ctx->lenscam_surfaces) ctx->lenscam_dirty = true;
+  ctx->lenscam_surfaces = which;
+  return LF_OK;
+}
+
+lf_status lf_get_lens_camera_surfaces(lf_ctx* ctx, int* which) {
+  if (!ctx || !which) return LF_ERR_INVALID;
+  *which = ctx->lenscam_surfaces;
+  return LF_OK;
+}
+
+lf_status lf_lens_camera_samples(lf_ctx* ctx, size_t n_pixels, const int* pixels, float* out) {
+  if (!ctx || (n_pixels > 0 && (!pixels || !out))) return LF_ERR_INVALID;
+  if (ctx->W == 0) return lf_fail(ctx, LF_ERR_STATE, "lf_lens_camera_samples before lf_set_frame");
+  if (ctx->ns_aa < 1) return lf_fail(ctx, LF_ERR_STATE, "lf_lens_camera_samples before lf_set_params (ns_aa samples per pixel)");
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_lens_camera_samples before lf_set_lens (the sensor's width is the lens file's)");
+  if (ctx->jitter_mode == 0)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_lens_camera_samples: the lens camera samples with the counter RNG of the march "
+                                        "(lf_set_jitter_counter)");
+  const size_t n_px = (size_t)ctx->W * (size_t)ctx->H;
+  if (n_pixels > 0x7fffffffull / (4 * (size_t)ctx->ns_aa))
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_lens_camera_samples: too many pixels for one call");
+  for (size_t i = 0; i < n_pixels; i++)
+    if (pixels[i] < 0 || (size_t)pixels[i] >= n_px)
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_lens_camera_samples: a pixel index outside the frame (p = x + y W)");
+  if (n_pixels == 0) return LF_OK;
+  LF_HIP(ctx, hipSetDevice(ctx->device));
+  LfLensCamArgs lc;
+  lf_fill_lenscam_args(ctx, &lc);
+  const size_t n_out = n_pixels * (size_t)ctx->ns_aa;
+  int* d_pix = nullptr;
+  float* d_out = nullptr;
+  hipError_t e = hipMalloc((void**)&d_pix, n_pixels * sizeof(int));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, n_out * 4 * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d_pix, pixels, n_pixels * sizeof(int), hipMemcpyHostToDevice);
+  if (e == hipSuccess) {
+    hipLaunchKernelGGL(k_lenscam_samples, dim3((unsigned)((n_out + 255) / 256)), dim3(256), 0, ctx->stream, lc,
+                       make_uint2((unsigned)ctx->jitter_key, (unsigned)(ctx->jitter_key >> 32)), ctx->ns_aa, n_pixels, d_pix, d_out);
+    e = hipGetLastError();
+  }
+  if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess) e = hipMemcpy(out, d_out, n_out * 4 * sizeof(float), hipMemcpyDeviceToHost);
+  if (d_pix) (void)hipFree(d_pix);
+  if (d_out) (void)hipFree(d_out);
+  LF_HIP(ctx, e);
+  return LF_OK;
+}
 
 lf_status lf_paraxial_entrance_pupil(int n, int stop, const float* radius, const float* thickness,
                                      const float* ior_row, double* z_mm, double* magnification) {

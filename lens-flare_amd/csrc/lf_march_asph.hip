@@ -378,15 +378,14 @@ lf_status build_path_table(lf_ctx* ctx, int l, int i, int j, std::vector<unsigne
       lf_stack_constants_of(C, L.n_surf, L.n_lambda, k, l, fwd, n_in, n_out, reinterpret_cast<float*>(buf.data() + next_stack));
       next_stack += sub;
     }
-    bool any = A.kappa[k] != 0.0f;
-    for (int m = 0; m < LF_MAX_ASPH_COEF; m++) any = any || A.coef[(size_t)m * L.n_surf + k] != 0.0f;
     const LfBiconics& B = ctx->bic;
-    if (B.n > 0 && B.on[k]) {
+    const int rec_kind = lf_surface_record_kind(ctx, k);
+    if (rec_kind == LF_EV_BICONIC) {
       w.kind |= LF_EV_BICONIC;
       w.asph.kappa = B.rx[k] == 0.0f ? 0.0f : 1.0f / B.rx[k];
       w.asph.a[0] = B.kx[k];
       w.asph.a[1] = B.ky[k];
-    } else if (A.n > 0 ? any : (ctx->asph_force && s.curv != 0.0f)) {
+    } else if (rec_kind == LF_EV_ASPH) {
       w.kind |= LF_EV_ASPH;
       w.asph.kappa = A.kappa[k];
       for (int m = 0; m < LF_MAX_ASPH_COEF; m++) w.asph.a[m] = A.coef[(size_t)m * L.n_surf + k];

@@ -554,8 +554,11 @@ __device__ __forceinline__ void sample_subcell(const SampleSpec& a, unsigned til
 }
 // ... and the sample itself, given its stratum (cx, cy) = (s mod G, s / G) and that sub-cell (all four unused for the
 // unstratified samples s >= G * G)
-__device__ __forceinline__ StartRay sample_start_in(const SampleSpec& a, int x, int y, int s, int cx, int cy, unsigned sxi,
-                                                    unsigned syi) {
+// (in two steps: the sensor point and the pupil-square coordinates, which lf_lens_camera_samples hands out as they are,
+// then the start ray aimed from them)
+struct SamplePoint { float X, Y, pa, pb; };
+__device__ __forceinline__ SamplePoint sample_point_in(const SampleSpec& a, int x, int y, int s, int cx, int cy, unsigned sxi,
+                                                       unsigned syi) {
   const unsigned p = (unsigned)y * (unsigned)a.W + (unsigned)x;
   const uint4 rnd = philox4x32_10(make_uint4(p, (unsigned)s, kDomainMarch, 0u), a.key);
   const float jx = u01(rnd.x), jy = u01(rnd.y);
@@ -567,13 +570,25 @@ __device__ __forceinline__ StartRay sample_start_in(const SampleSpec& a, int x, 
   const float pa = fmaf(2.0f, ua, -1.0f), pb = fmaf(2.0f, ub, -1.0f);
   const float X = -(((float)x + jx) - a.half_w) * a.pitch;
   const float Y = -(((float)y + jy) - a.half_h) * a.pitch;
-  return aim_at_pupil(X, Y, pa, pb, a.pupil_h, a.vz, a.geom_norm);
+  return SamplePoint{X, Y, pa, pb};
+}
+__device__ __forceinline__ StartRay sample_start_in(const SampleSpec& a, int x, int y, int s, int cx, int cy, unsigned sxi,
+                                                    unsigned syi) {
+  const SamplePoint q = sample_point_in(a, x, y, s, cx, cy, sxi, syi);
+  return aim_at_pupil(q.X, q.Y, q.pa, q.pb, a.pupil_h, a.vz, a.geom_norm);
 }
 __device__ __forceinline__ StartRay sample_start(const SampleSpec& a, int x, int y, int s) {
   unsigned sxi = 0u, syi = 0u;
   const int cy = s / a.G, cx = s - cy * a.G;
   if (s < a.G * a.G) sample_subcell(a, sample_tile_id(a, x, y), s, sxi, syi);
   return sample_start_in(a, x, y, s, cx, cy, sxi, syi);
+}
+// ... and its sensor point and pupil-square coordinates alone (k_lenscam_samples, lf_lens_camera.hip)
+__device__ __forceinline__ SamplePoint sample_point(const SampleSpec& a, int x, int y, int s) {
+  unsigned sxi = 0u, syi = 0u;
+  const int cy = s / a.G, cx = s - cy * a.G;
+  if (s < a.G * a.G) sample_subcell(a, sample_tile_id(a, x, y), s, sxi, syi);
+  return sample_point_in(a, x, y, s, cx, cy, sxi, syi);
 }
 
 // the film constants of a row of the weight re-march: wavelength j of record `off` (bytes from the weight

@@ -31,6 +31,7 @@
 
 #include "lf_internal.h"
 #include "lf_march_events.h"
+#include "lf_primary_general.h"
 #include "lf_scene_walk.h"
 
 namespace {
@@ -464,13 +465,27 @@ constexpr int kLensStridedMaxPrims = 1024;
 #ifndef LF_SCENE_LENS_WAVES
 #define LF_SCENE_LENS_WAVES 3     // (2 / 3 / 4 / 5 waves per SIMD: 10.0 / 8.2 / 10.3 / 14.2 ms on the c4 bench frame -- spills beyond 3)
 #endif
-template <bool SOFT, bool FILT = false, bool STACK = false>   // FILT, STACK: as scene_pixel's
-__global__ __launch_bounds__(256, LF_SCENE_LENS_WAVES) void k_scene_lens(LfSceneDev sc, LfEnvDev ev, LfCamera cam, ScenePixelArgs a,
+// The SURF != 0 instantiations (recorded interfaces) carry the Newton steps' live values on top and are bound so that none of
+// them uses scratch (profiles/lenscam_surfaces_resources.txt): 2 waves per SIMD with delta lights (197 - 200 VGPRs), 1 with
+// sampled lights (SOFT: 256 VGPRs + 30 AGPRs -- at 2 it spills 128 - 140 bytes a lane, at 3 as much as its SURF = 0 twin).
+#ifndef LF_SCENE_LENS_SURF_WAVES
+#define LF_SCENE_LENS_SURF_WAVES 2
+#endif
+#ifndef LF_SCENE_LENS_SURF_SOFT_WAVES
+#define LF_SCENE_LENS_SURF_SOFT_WAVES 1
+#endif
+// SURF (lf_set_lens_camera_surfaces, LF_LENSCAM_SURFACES_ALL): what the primary path's rows may be -- 0 spheres (the kernel it
+// was: primary_path itself, `surf` unread), 1 aspheric records too, 2 aspheric and biconic records (primary_path_general,
+// lf_primary_general.h; the records in `surf`).  Launched by what the lens holds: a lens of spheres never sees 1 or 2.
+template <bool SOFT, bool FILT = false, bool STACK = false, int SURF = 0>   // FILT, STACK: as scene_pixel's
+__global__ __launch_bounds__(256, SURF == 0 ? LF_SCENE_LENS_WAVES : SOFT ? LF_SCENE_LENS_SURF_SOFT_WAVES : LF_SCENE_LENS_SURF_WAVES) void k_scene_lens(
+                                                       LfSceneDev sc, LfEnvDev ev, LfCamera cam, ScenePixelArgs a,
                                                        int y0, int y1, LfDeal deal, int mxs, LfLensCamArgs lc,
                                                        const LfPrimaryDev* __restrict__ prim,
                                                        const float* __restrict__ mask,
                                                        unsigned long long* __restrict__ counters,
-                                                       double* __restrict__ scene) {
+                                                       double* __restrict__ scene,
+                                                       const LfPrimarySurfDev* __restrict__ surf) {
   extern __shared__ int s_stack[];
   __shared__ unsigned long long s_cnt[kSceneCounters];
   __shared__ float s_qf[4][7][kLensQueue];       // px py hz dx dy dz, transmitted weight
@@ -603,7 +618,7 @@ __global__ __launch_bounds__(256, LF_SCENE_LENS_WAVES) void k_scene_lens(LfScene
       bool left = false;
       lfm::Ray r{st.X, st.Y, 0.0f, fmaf(st.X, st.X, st.Y * st.Y), st.dx, st.dy, st.dz, st.w0, 1.0f};
       if (active) {
-        left = lfm::primary_path<(STACK ? lfm::kVarStack : 0) | (FILT ? lfm::kVarCoatFilt : lfm::kVarCoat)>(prim, l, r, mask, lc.mw, lc.mh, lane);
+        left = lfm::primary_path_general<(STACK ? lfm::kVarStack : 0) | (FILT ? lfm::kVarCoatFilt : lfm::kVarCoat), SURF>(prim, surf, l, r, mask, lc.mw, lc.mh, lane);
         lens_started++;
         if (left) lens_left++;
       }
@@ -1165,15 +1180,26 @@ lf_status lf_render_scene_term(lf_ctx* ctx) {
   pa.hemisphere = ctx->hemisphere_sample ? 1 : 0; pa.max_tolerance = ctx->max_tolerance; pa.key = ctx->jitter_key;
   LfLensCamArgs lc;
   lf_fill_lenscam_args(ctx, &lc);
+  // (lf_set_lens_camera_surfaces(LF_LENSCAM_SURFACES_ALL) let a lens with records through lf_lenscam_prepare: the compacted
+  // kernel's SURF instantiations march them -- 2 knows both kinds, a lens may carry both; the per-lane A/B kernel has none)
+  const int lens_surf = !lens ? 0 : ctx->bic.n > 0 ? 2 : ctx->asph.n > 0 ? 1 : 0;
+  if (lens_surf != 0 && ctx->scene_compact == 0)
+    return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lens camera: a lens with aspheric / biconic records is marched by the compacted scene "
+                                            "kernel alone (lf_test_knob(\"scene_compact\", 0) selects the per-lane kernel)");
+  if (lens_surf != 0 && !ctx->primary_surf_dev)
+    return lf_fail(ctx, LF_ERR_STATE, "lens camera: the primary rows' records were not uploaded");
   hipEvent_t ev = lf_timing_begin(ctx, LFK_SCENE);
-#define LF_LAUNCH_SCENE_LENS(SOFT)  do { if (filt && stacks) LF_LAUNCH_SCENE_LENS2(SOFT, true, true); else if (stacks) LF_LAUNCH_SCENE_LENS2(SOFT, false, true); \
-                                         else if (filt) LF_LAUNCH_SCENE_LENS2(SOFT, true, false); else LF_LAUNCH_SCENE_LENS2(SOFT, false, false); } while (0)
-#define LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK)                                                           \
-  hipLaunchKernelGGL((k_scene_lens<SOFT, FILT, STACK>), dim3((unsigned)((lens_tiles_x + 3) / 4), (unsigned)(((ctx->y1 + 7) >> 3) - (ctx->y0 >> 3))), \
+#define LF_LAUNCH_SCENE_LENS(SOFT)  do { if (filt && stacks) LF_LAUNCH_SCENE_LENS1(SOFT, true, true); else if (stacks) LF_LAUNCH_SCENE_LENS1(SOFT, false, true); \
+                                         else if (filt) LF_LAUNCH_SCENE_LENS1(SOFT, true, false); else LF_LAUNCH_SCENE_LENS1(SOFT, false, false); } while (0)
+#define LF_LAUNCH_SCENE_LENS1(SOFT, FILT, STACK)  do { if (lens_surf == 2) LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK, 2); else if (lens_surf == 1) LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK, 1); \
+                                                       else LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK, 0); } while (0)
+#define LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK, SURF)                                                     \
+  hipLaunchKernelGGL((k_scene_lens<SOFT, FILT, STACK, SURF>), dim3((unsigned)((lens_tiles_x + 3) / 4), (unsigned)(((ctx->y1 + 7) >> 3) - (ctx->y0 >> 3))), \
                      dim3(256), (size_t)std::min(kStackDepth, std::max(1, ctx->scene_tree_depth + 1)) * 256 * sizeof(int), \
                      ctx->stream, ctx->scene_dev, ctx->env_dev, ctx->cam, pa, ctx->y0, ctx->y1,           \
                      lf_deal_of(ctx), lens_mxs, lc, ctx->primary_dev,                                      \
-                     ctx->ap[LF_APERTURE_STARBURST].texels, ctx->scene_counters_dev, ctx->scene)
+                     ctx->ap[LF_APERTURE_STARBURST].texels, ctx->scene_counters_dev, ctx->scene,           \
+                     (const LfPrimarySurfDev*)ctx->primary_surf_dev)
   // a small tree is resident in the caches whichever lanes walk it: the wave takes the march's strided tile (see the
   // kernel)
   int lens_mxs = ctx->scene_dev.n_prims <= kLensStridedMaxPrims ? lc.xs : 0;
@@ -1190,6 +1216,7 @@ lf_status lf_render_scene_term(lf_ctx* ctx) {
 #undef LF_LAUNCH_SCENE
 #undef LF_LAUNCH_SCENE2
 #undef LF_LAUNCH_SCENE_LENS
+#undef LF_LAUNCH_SCENE_LENS1
 #undef LF_LAUNCH_SCENE_LENS2
   LF_HIP(ctx, hipGetLastError());
   return LF_OK;
