@@ -548,6 +548,56 @@ lf_status lf_asphere_events(lf_ctx* ctx, float curvature, float conic, int n_coe
  * lf_generate_lens_rays defines them.  Works for any lens; on an aspheric one lf_generate_lens_rays routes through it. */
 lf_status lf_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, size_t n, const float* sensor_xy_mm,
                              const float* pupil_uv, float* out);
+/* SENSOR GHOSTS: the sensor as a mirror behind the lens (no reference counterpart).  A sensor's cover glass and silicon
+ * reflect a few per cent of the focused image back into the lens, and the rear elements return it as a second, defocused
+ * image of the light.  The sensor path of interface i (any interface but the stop) of a sensor sample is marched from the
+ * sensor like every other path: interfaces n-1 .. i+1 refracted towards the scene, mirrored at i, i+1 .. n-1 refracted
+ * towards the sensor, mirrored at the sensor plane, n-1 .. 0 refracted and out -- 3 n - 2 i events, every stop crossing the
+ * stop's own event with its mask.  The sensor's event carries the ray to z = z_sensor and flips d_z; the weight is
+ * multiplied by reflectance[lambda], one number per wavelength whatever the angle; a ray that lands outside the WHOLE
+ * frame's rectangle |X| <= W pitch / 2, |Y| <= H pitch / 2 is lost; a wavelength whose reflectance is 0 is not marched.
+ * The lit ray is what any ghost ray is: every kind of light, several lights, films, stacks, the bilinear stop, aspheric and
+ * biconic records, ghost occlusion with both reaches, bands and deals are the code that exists.  The sensor paths ALWAYS aim
+ * at the default disc -- the rear element's clear aperture at its vertex plane -- whatever lf_set_pupil_target or
+ * lf_aim_at_exit_pupil holds for the ordinary paths: their first mirror lies behind the stop, or sends the light through it a
+ * second and third time (the comment on lf_set_pupil_target).  They enter neither the pair selection nor the path tree nor the
+ * cull table: every selected sensor path of every sample is marched on its own, unculled -- about 3 n - 2 i events per path,
+ * sample and wavelength, a multiple of the default frame's cost.  Out of scope: angle- or polarisation-dependent reflectance,
+ * diffuse or microlens-diffraction reflection, paths that meet the sensor twice.
+ *
+ * lf_set_sensor_reflectance: one value in [0, 1] per index column of the installed lens; NULL clears.  A wrong n_lambda, a
+ * value that is not finite or out of range: LF_ERR_INVALID, the previous state stays.  lf_set_lens clears the values (they
+ * belong to the prescription's columns), lf_focus_lens keeps them -- as the coatings.  The getter: *installed 0 / 1;
+ * reflectance (n_lambda floats, may be NULL) zeros while none is installed. */
+lf_status lf_set_sensor_reflectance(lf_ctx* ctx, int n_lambda, const float* reflectance);
+lf_status lf_get_sensor_reflectance(lf_ctx* ctx, int n_lambda, float* reflectance, int* installed);
+/* The mode, a setting of the context (it survives lf_set_lens): OFF, the default -- lf_trace_ghosts launches exactly the kernels
+ * it always launched; ADD -- it marches the ordinary selection as ever and then adds the sensor paths to the ghost buffer;
+ * ONLY -- the ordinary march is skipped, the sensor paths replace the buffer (or add to it under lf_set_ghost_accumulate).
+ * interfaces: n distinct interfaces, none the stop or out of range (else LF_ERR_INVALID, the previous state stays); NULL: every
+ * interface but the stop, of whatever lens is installed at the launch.  ADD or ONLY without a reflectance makes lf_trace_ghosts
+ * return LF_ERR_STATE.  The getter: the interfaces a launch would march, in its order (cap: the list's room; any pointer may be
+ * NULL). */
+enum { LF_SENSOR_GHOSTS_OFF = 0, LF_SENSOR_GHOSTS_ADD = 1, LF_SENSOR_GHOSTS_ONLY = 2 };
+lf_status lf_set_sensor_ghosts(lf_ctx* ctx, int mode, const int* interfaces, int n);
+lf_status lf_get_sensor_ghosts(lf_ctx* ctx, int* mode, int* interfaces, int cap, int* n);
+/* lf_march_path_rays' twin for the sensor path of interface i: the same eight floats per ray, the weight with
+ * reflectance[lambda]; follows films, stacks, aspheric and biconic records and the mask filter; aims at the default disc. */
+lf_status lf_march_sensor_path_rays(lf_ctx* ctx, int lambda, int i, size_t n, const float* sensor_xy_mm, const float* pupil_uv,
+                                    float* out);
+/* host only: the events of the sensor path of interface i in marching order, out[e] = interface | reflect << 8 | forward << 9
+ * with n_surfaces standing for the sensor's mirror; *n_events = 3 n_surfaces - 2 i.  LF_ERR_INVALID: i the stop or out of range,
+ * cap too small. */
+lf_status lf_sensor_path_sequence(int n_surfaces, int stop_index, int i, int* out, int cap, int* n_events);
+/* host only: the sensor's event on ONE ray, the kernels' own definition (bit for bit).  ray_in {x, y, z, Kx, Ky, Kz}: z relative to
+ * the vertex the ray sits on, dzv = that vertex's z minus the sensor plane's, K any multiple of the direction, K_z > 0.
+ * ray_out: the point on the plane (z = 0) and the mirrored direction; *inside: |x| <= half_width_mm and |y| <= half_height_mm. */
+lf_status lf_sensor_mirror_event(const float ray_in[6], float dzv, float half_width_mm, float half_height_mm, float ray_out[6],
+                                 int* inside);
+/* Since the last lf_reset_counters: {sensor-path rays started, rays that reached the sensor's mirror, of those lost off the
+ * rectangle there, lit (ray, light) contributions}.  lf_get_counters, lf_get_executed_events and lf_get_march_stats keep
+ * describing the ordinary paths alone, under ADD too.  lf_timing_get's slot of the launch: "march_sensor". */
+lf_status lf_get_sensor_ghost_stats(lf_ctx* ctx, uint64_t out[4]);
 /* BICONIC INTERFACES: cylinders, toroids, the anamorphic flare (no reference counterpart).  Interface k of the installed
  * lens becomes
  *   z(x, y) = (cx x^2 + cy y^2) / (1 + sqrt(1 - (1 + kx) cx^2 x^2 - (1 + ky) cy^2 y^2))

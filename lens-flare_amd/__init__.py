@@ -52,6 +52,8 @@ ABI_SYMBOLS = [
     "lf_set_lens_coating_stacks", "lf_get_lens_coating_stacks", "lf_coating_stack_reflectance",
     "lf_set_lens_aspheres", "lf_get_lens_aspheres", "lf_asphere_sag", "lf_asphere_event", "lf_asphere_events", "lf_march_path_rays",
     "lf_set_lens_biconics", "lf_get_lens_biconics", "lf_get_lens_meridian_scales", "lf_biconic_sag", "lf_biconic_event", "lf_biconic_events",
+    "lf_set_sensor_reflectance", "lf_get_sensor_reflectance", "lf_set_sensor_ghosts", "lf_get_sensor_ghosts",
+    "lf_march_sensor_path_rays", "lf_sensor_path_sequence", "lf_sensor_mirror_event", "lf_get_sensor_ghost_stats",
     "lf_set_mask_filter", "lf_get_mask_filter", "lf_mask_lookup",
     "lf_set_pupil_target", "lf_get_pupil_target", "lf_aim_at_exit_pupil", "lf_paraxial_exit_pupil", "lf_set_ghost_accumulate",
     "lf_set_lens_camera", "lf_get_lens_camera", "lf_set_lens_camera_aim", "lf_set_lens_camera_surfaces", "lf_get_lens_camera_surfaces",
@@ -170,7 +172,7 @@ def load_lens_file(path):
     """Parse a .lens prescription (see data/dgauss11.lens) -> dict of float32 arrays."""
     if not os.path.isabs(path) and not os.path.exists(path):
         path = os.path.join(DATA, path)
-    rows, sensor_w, lambda_nm, coats, layers, asphs, bics = [], 36.0, None, [], [], [], []
+    rows, sensor_w, lambda_nm, coats, layers, asphs, bics, sens = [], 36.0, None, [], [], [], [], None
     for line in open(path):
         line = line.split("#")[0].strip()
         if not line:
@@ -178,6 +180,11 @@ def load_lens_file(path):
         t = line.split()
         if t[0] == "sensor_width_mm":
             sensor_w = float(t[1])
+            continue
+        if t[0] == "sensor_reflectance":   # sensor_reflectance r_1 .. r_L | r  (lf_set_sensor_reflectance)
+            if sens is not None or len(t) < 2:
+                raise ValueError(f"{path}: a sensor_reflectance line is `sensor_reflectance r_1 .. r_L` or `sensor_reflectance r` (once)")
+            sens = [float(v) for v in t[1:]]
             continue
         if t[0] == "lambda_nm":      # the wavelengths of the index columns (spectral prescriptions)
             lambda_nm = [float(v) for v in t[1:]]
@@ -208,6 +215,10 @@ def load_lens_file(path):
     lens = dict(n=n, stop=stop[0] if stop else -1, radius=rows[:, 0].astype(np.float32),
                 thickness=rows[:, 1].astype(np.float32), ior=ior.astype(np.float32),
                 semi_aperture=rows[:, -1].astype(np.float32), sensor_width_mm=float(sensor_w))
+    if sens is not None:
+        if len(sens) not in (1, ior.shape[0]) or not all(0.0 <= v <= 1.0 for v in sens):
+            raise ValueError(f"{path}: sensor_reflectance takes one value in [0, 1], or one per index column")
+        lens["sensor_reflectance"] = np.array(sens if len(sens) > 1 else sens * ior.shape[0], np.float32)
     if asphs:
         conic = np.zeros(n, np.float32)
         coef = np.zeros((MAX_ASPH_COEF, n), np.float32)
@@ -280,6 +291,34 @@ MAX_ASPH_COEF = 6        # LF_MAX_ASPH_COEF
 CULL_ASPHERIC = 9        # LF_CULL_ASPHERIC
 ASPH_ALIVE, ASPH_MISSED, ASPH_APERTURE, ASPH_TIR = 0, 1, 2, 3   # the fates of lf_asphere_event
 CULL_ANAMORPHIC = 10     # LF_CULL_ANAMORPHIC
+SENSOR_GHOSTS_OFF, SENSOR_GHOSTS_ADD, SENSOR_GHOSTS_ONLY = 0, 1, 2   # the modes of lf_set_sensor_ghosts
+
+
+def sensor_path_sequence(n_surfaces, stop_index, i):
+    """The events of the sensor path of interface i in marching order: interface | reflect << 8 | forward << 9, n_surfaces
+    standing for the sensor's mirror (host arithmetic)."""
+    out = np.zeros(3 * max(int(n_surfaces), 1), np.int32)
+    n_ev = C.c_int()
+    st = load_library().lf_sensor_path_sequence(int(n_surfaces), int(stop_index), int(i), _fp(out, C.c_int), len(out), C.byref(n_ev))
+    if st != 0:
+        raise LensFlareError(st, "lf_sensor_path_sequence")
+    return out[:n_ev.value].copy()
+
+
+def sensor_mirror_event(rays, dzv, half_width_mm, half_height_mm):
+    """The sensor's event on n rays {x, y, z, Kx, Ky, Kz} (host arithmetic, the kernels' own definition): (out n x 6, inside n)."""
+    lib = load_library()
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    out = np.zeros_like(rays)
+    inside = np.zeros(len(rays), np.int32)
+    one = C.c_int()
+    for k in range(len(rays)):
+        st = lib.lf_sensor_mirror_event(_fp(rays[k], C.c_float), C.c_float(dzv), C.c_float(half_width_mm), C.c_float(half_height_mm),
+                                        _fp(out[k], C.c_float), C.byref(one))
+        if st != 0:
+            raise LensFlareError(st, "lf_sensor_mirror_event")
+        inside[k] = one.value
+    return out, inside
 
 
 def biconic_sag(curvature_x, curvature_y, conic_x, conic_y, x, y):
@@ -1035,6 +1074,60 @@ class LensFlare:
         if "biconics" in lens:
             b = lens["biconics"]
             self.set_lens_biconics(b["on"], b["radius_x"], b["conic_x"], b["conic_y"])
+        if "sensor_reflectance" in lens:
+            self.set_sensor_reflectance(lens["sensor_reflectance"])
+
+    def set_sensor_reflectance(self, reflectance=None):
+        """The sensor's reflectance, one value in [0, 1] per index column of the installed lens (None clears it)."""
+        if reflectance is None:
+            self._ck(self.lib.lf_set_sensor_reflectance(self.ctx, 0, None))
+            return
+        r = np.ascontiguousarray(reflectance, np.float32).ravel()
+        self._ck(self.lib.lf_set_sensor_reflectance(self.ctx, len(r), _fp(r, C.c_float)))
+
+    def sensor_reflectance(self):
+        """The installed reflectance per index column, or None."""
+        nl = self.lens_info()["n_lambda"]
+        r = np.zeros(nl, np.float32)
+        on = C.c_int()
+        self._ck(self.lib.lf_get_sensor_reflectance(self.ctx, nl, _fp(r, C.c_float), C.byref(on)))
+        return r if on.value else None
+
+    def set_sensor_ghosts(self, mode=SENSOR_GHOSTS_ADD, interfaces=None):
+        """Sensor-reflection ghosts: SENSOR_GHOSTS_OFF / _ADD (behind the ordinary march) / _ONLY; interfaces None: every
+        interface but the stop."""
+        if interfaces is None:
+            self._ck(self.lib.lf_set_sensor_ghosts(self.ctx, int(mode), None, 0))
+            return
+        sel = np.ascontiguousarray(interfaces, np.int32).ravel()
+        self._ck(self.lib.lf_set_sensor_ghosts(self.ctx, int(mode), _fp(sel, C.c_int), len(sel)))
+
+    def sensor_ghosts(self):
+        """(mode, the interfaces a launch marches)"""
+        mode, n = C.c_int(), C.c_int()
+        sel = np.zeros(16, np.int32)
+        self._ck(self.lib.lf_get_sensor_ghosts(self.ctx, C.byref(mode), _fp(sel, C.c_int), len(sel), C.byref(n)))
+        return mode.value, [int(v) for v in sel[:n.value]]
+
+    def march_sensor_path_rays(self, lam, i, sensor_xy_mm, pupil_uv):
+        """march_path_rays along the sensor path of interface i: n x 8, the weight with the sensor's reflectance."""
+        xy = np.ascontiguousarray(sensor_xy_mm, np.float32).reshape(-1, 2)
+        uv = np.ascontiguousarray(pupil_uv, np.float32).reshape(-1, 2)
+        out = np.zeros((len(xy), 8), np.float32)
+        self._ck(self.lib.lf_march_sensor_path_rays(self.ctx, int(lam), int(i), C.c_size_t(len(xy)), _fp(xy, C.c_float),
+                                                    _fp(uv, C.c_float), _fp(out, C.c_float)))
+        return out
+
+    def sensor_path_sequence(self, i):
+        """sensor_path_sequence of the installed lens"""
+        info = self.lens_info()
+        return sensor_path_sequence(info["n"], info["stop"], i)
+
+    def sensor_ghost_stats(self):
+        """{started, reached_sensor, lost_at_sensor, lit} of the sensor paths since reset_counters"""
+        out = (C.c_uint64 * 4)()
+        self._ck(self.lib.lf_get_sensor_ghost_stats(self.ctx, out))
+        return dict(zip(("started", "reached_sensor", "lost_at_sensor", "lit"), (int(v) for v in out)))
 
     def set_lens_biconics(self, on=None, radius_x=None, conic_x=None, conic_y=None):
         """Biconic records on the installed lens: on[k] != 0 marks interface k, radius_x[k] its x-meridian radius (0: flat in

@@ -12,6 +12,7 @@
 #include "lf_march_events.h"
 #include "lf_asphere.h"
 #include "lf_biconic.h"
+#include "lf_sensor_event.h"
 #include "../host/lf_collada.h"
 
 lf_status lf_fail(const lf_ctx* ctx, lf_status st, const std::string& msg) {
@@ -76,7 +77,7 @@ namespace {
 
 const char* kKernelNames[LFK_COUNT] = {"march", "flare_layer", "ghost_raster", "dft",
                                        "frame_setup", "tonemap", "exchange", "scene_term", "cull_prepass", "cull_audit",
-                                       "cull_cache_build", "flare_visibility"};
+                                       "cull_cache_build", "flare_visibility", "march_sensor"};
 
 // the reference's hard-coded prescription (pathtracer.cpp:541-556); literals narrowed to float
 // where the reference narrows them
@@ -527,6 +528,7 @@ lf_status lf_destroy(lf_ctx* ctx) {
   free_frame_buffers(ctx);
   lf_cull_cache_free(ctx);
   lf_flare_occlusion_free(ctx);
+  lf_sensor_free(ctx);
   for (auto& t : ctx->timed) { (void)hipEventDestroy(t.start); (void)hipEventDestroy(t.stop); }
   for (hipEvent_t e : ctx->event_pool) (void)hipEventDestroy(e);
   for (int s = 0; s < 2; s++) {
@@ -1016,6 +1018,7 @@ lf_status lf_set_lens(lf_ctx* ctx, int n_surfaces, int stop_index, int n_lambda,
   ctx->coat = LfCoatings{};
   ctx->asph = LfAspheres{};      // (and its aspheres: a new lens is one of spheres)
   ctx->bic = LfBiconics{};       // (and its biconic records)
+  ctx->sensor.n_refl = 0;        // (and its sensor's reflectance; the sensor ghosts' mode is a setting of the context and stays)
   ctx->lenscam_dirty = true;
   lf_derive_lens(ctx, n_surfaces, stop_index, n_lambda, radius, thickness, ior, semi_aperture,
                  sensor_width_mm);
@@ -1624,7 +1627,7 @@ lf_status lf_trace_ghosts(lf_ctx* ctx, int spp, uint64_t key) {
     return lf_fail(ctx, LF_ERR_STATE, "lf_trace_ghosts needs lf_set_lens and lf_set_sun");
   if (!ctx->ap[LF_APERTURE_STARBURST].valid)
     return lf_fail(ctx, LF_ERR_STATE, "aperture mask (LF_APERTURE_STARBURST slot) not set");
-  if (ctx->pupil_target_h > 0.0f && ctx->lens.stop >= 0) {
+  if (ctx->pupil_target_h > 0.0f && ctx->lens.stop >= 0 && ctx->sensor.mode != LF_SENSOR_GHOSTS_ONLY) {
     // a reduced disc (the stop's image) is an unbiased estimator only for paths that cross the stop before
     // their first reflection; a pair with both mirrors behind the stop reaches the sensor through parts of
     // the rear element the disc does not cover
@@ -1638,8 +1641,14 @@ lf_status lf_trace_ghosts(lf_ctx* ctx, int spp, uint64_t key) {
     const lf_status ready = lf_occlusion_ready(ctx, "lf_trace_ghosts");
     if (ready != LF_OK) return ready;
   }
+  const int sensor_mode = ctx->sensor.mode;
+  if (sensor_mode != LF_SENSOR_GHOSTS_OFF && ctx->sensor.n_refl == 0)
+    return lf_fail(ctx, LF_ERR_STATE, "lf_trace_ghosts: sensor ghosts are on and the sensor has no reflectance (lf_set_sensor_reflectance)");
   LF_HIP(ctx, hipSetDevice(ctx->device));
-  lf_status st = lfk_march(ctx, spp, key);
+  lf_status st = LF_OK;
+  if (sensor_mode != LF_SENSOR_GHOSTS_ONLY) st = lfk_march(ctx, spp, key);
+  // the sensor's mirror: its paths behind the ordinary selection's (ADD) or alone (ONLY), a launch of their own
+  if (st == LF_OK && sensor_mode != LF_SENSOR_GHOSTS_OFF) st = lfk_march_sensor(ctx, spp, key, sensor_mode == LF_SENSOR_GHOSTS_ADD);
   if (st != LF_OK) return st;
   ctx->ghost_valid = true;
   return LF_OK;
@@ -2596,6 +2605,140 @@ lf_status lf_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, size_t n, co
   return LF_OK;
 }
 
+// ---------------------------------------------------------------- sensor ghosts -----------------
+lf_status lf_set_sensor_reflectance(lf_ctx* ctx, int n_lambda, const float* reflectance) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_set_sensor_reflectance before lf_set_lens");
+  if (!reflectance) { ctx->sensor.n_refl = 0; return LF_OK; }
+  if (n_lambda != ctx->lens.n_lambda)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_sensor_reflectance: one value per index column of the installed lens");
+  for (int l = 0; l < n_lambda; l++)
+    if (!std::isfinite(reflectance[l]) || reflectance[l] < 0.0f || reflectance[l] > 1.0f)
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_set_sensor_reflectance: a reflectance is a finite number in [0, 1]");
+  for (int l = 0; l < n_lambda; l++) ctx->sensor.refl[l] = reflectance[l];
+  ctx->sensor.n_refl = n_lambda;
+  return LF_OK;
+}
+
+lf_status lf_get_sensor_reflectance(lf_ctx* ctx, int n_lambda, float* reflectance, int* installed) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_get_sensor_reflectance before lf_set_lens");
+  if (installed) *installed = ctx->sensor.n_refl > 0 ? 1 : 0;
+  if (reflectance) {
+    if (n_lambda != ctx->lens.n_lambda)
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_get_sensor_reflectance: one value per index column of the installed lens");
+    for (int l = 0; l < n_lambda; l++) reflectance[l] = ctx->sensor.n_refl > 0 ? ctx->sensor.refl[l] : 0.0f;
+  }
+  return LF_OK;
+}
+
+lf_status lf_set_sensor_ghosts(lf_ctx* ctx, int mode, const int* interfaces, int n) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (mode != LF_SENSOR_GHOSTS_OFF && mode != LF_SENSOR_GHOSTS_ADD && mode != LF_SENSOR_GHOSTS_ONLY)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_sensor_ghosts: the mode is LF_SENSOR_GHOSTS_OFF, _ADD or _ONLY");
+  if (!interfaces) {
+    ctx->sensor.mode = mode;
+    ctx->sensor.n_sel = -1;
+    return LF_OK;
+  }
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_set_sensor_ghosts with a list of interfaces before lf_set_lens");
+  if (n < 1 || n > LF_MAX_SURFACES) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_sensor_ghosts: the list holds 1 .. LF_MAX_SURFACES interfaces");
+  for (int q = 0; q < n; q++) {
+    if (interfaces[q] < 0 || interfaces[q] >= ctx->lens.n_surf || interfaces[q] == ctx->lens.stop)
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_set_sensor_ghosts: an interface is a glass interface 0 <= i < n_surfaces, never the stop");
+    for (int r = 0; r < q; r++)
+      if (interfaces[r] == interfaces[q]) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_sensor_ghosts: an interface is listed twice");
+  }
+  ctx->sensor.mode = mode;
+  ctx->sensor.n_sel = n;
+  for (int q = 0; q < n; q++) ctx->sensor.sel[q] = interfaces[q];
+  return LF_OK;
+}
+
+lf_status lf_get_sensor_ghosts(lf_ctx* ctx, int* mode, int* interfaces, int cap, int* n) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (mode) *mode = ctx->sensor.mode;
+  if (!interfaces && !n) return LF_OK;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_get_sensor_ghosts: the selection is resolved against a lens (lf_set_lens)");
+  int sel[LF_MAX_SURFACES];
+  const int m = lf_sensor_selection(ctx, sel);
+  if (m < 0) return lf_fail(ctx, LF_ERR_STATE, "lf_get_sensor_ghosts: the selection does not fit the installed lens");
+  if (n) *n = m;
+  if (interfaces) {
+    if (cap < m) return lf_fail(ctx, LF_ERR_INVALID, "lf_get_sensor_ghosts: the list does not fit");
+    for (int q = 0; q < m; q++) interfaces[q] = sel[q];
+  }
+  return LF_OK;
+}
+
+lf_status lf_sensor_path_sequence(int n_surfaces, int stop_index, int i, int* out, int cap, int* n_events) {
+  if (n_surfaces < 1 || n_surfaces > LF_MAX_SURFACES || stop_index < -1 || stop_index >= n_surfaces || !out || !n_events)
+    return LF_ERR_INVALID;
+  if (i < 0 || i >= n_surfaces || i == stop_index) return LF_ERR_INVALID;
+  const int n = n_surfaces, total = 3 * n - 2 * i;
+  if (cap < total) return LF_ERR_INVALID;
+  int m = 0;
+  for (int k = n - 1; k > i; k--) out[m++] = k;
+  out[m++] = i | 1 << 8;
+  for (int k = i + 1; k < n; k++) out[m++] = k | 1 << 9;
+  out[m++] = n | 1 << 8 | 1 << 9;          // the sensor's mirror, met travelling +z
+  for (int k = n - 1; k >= 0; k--) out[m++] = k;
+  *n_events = m;
+  return LF_OK;
+}
+
+lf_status lf_sensor_mirror_event(const float ray_in[6], float dzv, float half_width_mm, float half_height_mm, float ray_out[6],
+                                 int* inside) {
+  if (!ray_in || !ray_out || !inside) return LF_ERR_INVALID;
+  float px = ray_in[0], py = ray_in[1], hz = ray_in[2], dx = ray_in[3], dy = ray_in[4], dz = ray_in[5], r2;
+  *inside = lfm::lf_sensor_mirror(px, py, hz, r2, dx, dy, dz, dzv, half_width_mm, half_height_mm) ? 1 : 0;
+  ray_out[0] = px; ray_out[1] = py; ray_out[2] = hz; ray_out[3] = dx; ray_out[4] = dy; ray_out[5] = dz;
+  return LF_OK;
+}
+
+lf_status lf_march_sensor_path_rays(lf_ctx* ctx, int lambda, int i, size_t n, const float* sensor_xy_mm, const float* pupil_uv,
+                                    float* out) {
+  if (!ctx || !sensor_xy_mm || !pupil_uv || !out) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_march_sensor_path_rays before lf_set_lens");
+  if (!ctx->ap[LF_APERTURE_STARBURST].valid)
+    return lf_fail(ctx, LF_ERR_STATE, "aperture mask (LF_APERTURE_STARBURST slot) not set");
+  if (ctx->sensor.n_refl == 0)
+    return lf_fail(ctx, LF_ERR_STATE, "lf_march_sensor_path_rays: the sensor has no reflectance (lf_set_sensor_reflectance)");
+  if (lambda < 0 || lambda >= ctx->lens.n_lambda || n > 0x7fffffffull / 8)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_march_sensor_path_rays: wavelength index / count out of range");
+  if (i < 0 || i >= ctx->lens.n_surf || i == ctx->lens.stop)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_march_sensor_path_rays: the mirror is a glass interface 0 <= i < n_surfaces, never the stop");
+  if (n == 0) return LF_OK;
+  LF_HIP(ctx, hipSetDevice(ctx->device));
+  float *d_xy = nullptr, *d_uv = nullptr, *d_out = nullptr;
+  hipError_t e = hipMalloc((void**)&d_xy, n * 2 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_uv, n * 2 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, n * 8 * sizeof(float));
+  if (e == hipSuccess) e = hipMemcpy(d_xy, sensor_xy_mm, n * 2 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_uv, pupil_uv, n * 2 * sizeof(float), hipMemcpyHostToDevice);
+  lf_status st = LF_OK;
+  if (e == hipSuccess) st = lfk_march_sensor_path_rays(ctx, lambda, i, (int)n, d_xy, d_uv, d_out);
+  if (e == hipSuccess && st == LF_OK) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && st == LF_OK) e = hipMemcpy(out, d_out, n * 8 * sizeof(float), hipMemcpyDeviceToHost);
+  if (d_xy) (void)hipFree(d_xy);
+  if (d_uv) (void)hipFree(d_uv);
+  if (d_out) (void)hipFree(d_out);
+  if (st != LF_OK) return st;
+  LF_HIP(ctx, e);
+  return LF_OK;
+}
+
+lf_status lf_get_sensor_ghost_stats(lf_ctx* ctx, uint64_t out[4]) {
+  if (!ctx || !out) return LF_ERR_INVALID;
+  for (int k = 0; k < kSensorStats; k++) out[k] = 0;
+  if (!ctx->sensor.stats_dev) return LF_OK;      // (no sensor launch yet)
+  unsigned long long c[kSensorStats];
+  LF_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  LF_HIP(ctx, hipMemcpy(c, ctx->sensor.stats_dev, sizeof(c), hipMemcpyDeviceToHost));
+  for (int k = 0; k < kSensorStats; k++) out[k] = c[k];
+  return LF_OK;
+}
+
 // ---------------------------------------------------------------- biconic interfaces ------------
 lf_status lf_set_lens_biconics(lf_ctx* ctx, int n_surfaces, const int* on, const float* radius_x, const float* conic_x,
                                const float* conic_y) {
@@ -2751,7 +2894,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
   // lf_set_lens_coating_stacks; needs lambda_nm; not on an interface with a `coating` line)
   // `asphere k kappa [A4 [A6 ...]]` (interface k's conic constant and even coefficients: lf_set_lens_aspheres)
   // `biconic k Rx [kx [ky]]` (interface k's x-meridian radius, 0 = flat in x, and conic constants: lf_set_lens_biconics)
-  std::vector<std::vector<double>> rows, coats, layers, asphs, bics;
+  std::vector<std::vector<double>> rows, coats, layers, asphs, bics, sens;
   std::vector<double> lambdas;
   bool lambda_line = false, lambda_bad = false;
   double sensor_w = 36.0;
@@ -2761,10 +2904,11 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (char* h = std::strchr(line, '#')) *h = 0;
     std::vector<double> v;
     char* p = line;
-    int keyword = 0;   // 1 sensor_width_mm, 2 lambda_nm, 3 coating, 4 layer, 5 asphere, 6 biconic
+    int keyword = 0;   // 1 sensor_width_mm, 2 lambda_nm, 3 coating, 4 layer, 5 asphere, 6 biconic, 7 sensor_reflectance
     while (*p) {
       while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') p++;
       if (!*p) break;
+      if (v.empty() && !keyword && std::strncmp(p, "sensor_reflectance", 18) == 0) { keyword = 7; p += 18; continue; }
       if (v.empty() && !keyword && std::strncmp(p, "sensor_width_mm", 15) == 0) { keyword = 1; p += 15; continue; }
       if (v.empty() && !keyword && std::strncmp(p, "lambda_nm", 9) == 0) { keyword = 2; p += 9; continue; }
       if (v.empty() && !keyword && std::strncmp(p, "coating", 7) == 0) { keyword = 3; p += 7; continue; }
@@ -2787,6 +2931,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (keyword == 4) { layers.push_back(v); continue; }
     if (keyword == 5) { asphs.push_back(v); continue; }
     if (keyword == 6) { bics.push_back(v); continue; }
+    if (keyword == 7) { sens.push_back(v); continue; }
     if (keyword == 1) { if (v.size() != 1) { bad = true; break; } sensor_w = v[0]; continue; }
     if (!v.empty()) rows.push_back(v);
   }
@@ -2803,6 +2948,16 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     const bool is_stop = rows[k][0] == 0 && rows[k][2] == 0;
     if (is_stop && stop < 0) stop = k;
     for (int l = 0; l < nl; l++) ior[l * n + k] = (is_stop && stop == k) ? 1.0f : (float)rows[k][2 + l];
+  }
+  // `sensor_reflectance r_1 .. r_L | r` (the sensor's reflectance per index column: lf_set_sensor_reflectance; once)
+  float srefl[LF_MAX_LAMBDA] = {};
+  if (!sens.empty()) {
+    const std::vector<double>& c = sens[0];
+    bool ok = sens.size() == 1 && ((int)c.size() == 1 || (int)c.size() == nl);
+    for (size_t m = 0; ok && m < c.size(); m++) ok = c[m] >= 0.0 && c[m] <= 1.0;   // (false for a NaN)
+    if (!ok)
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_load_lens_file: a sensor_reflectance line is `sensor_reflectance r_1 .. r_L` or `sensor_reflectance r`, each in [0, 1] (once)");
+    for (int l = 0; l < nl; l++) srefl[l] = (float)c[c.size() == 1 ? 0 : (size_t)l];
   }
   float lam[LF_MAX_LAMBDA] = {}, cth[LF_MAX_SURFACES] = {}, cidx[LF_MAX_LAMBDA * LF_MAX_SURFACES] = {};
   bool has_coating[LF_MAX_SURFACES] = {};   // interface k has a `coating` line (whatever its thickness)
@@ -2860,6 +3015,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (c.size() > 3) bky[k] = (float)c[3];
   }
   lf_status st = lf_set_lens(ctx, n, stop, nl, radius, thick, ior, semi, (float)sensor_w);
+  if (st == LF_OK && !sens.empty()) st = lf_set_sensor_reflectance(ctx, nl, srefl);   // (the mode stays what it is)
   if (st == LF_OK && !bics.empty()) {   // (before the aspheres: an interface with both lines is refused by their setter)
     st = lf_set_lens_biconics(ctx, n, bon, brx, bkx, bky);
     if (st != LF_OK) {   // the lens stays, one of spheres
@@ -3061,6 +3217,8 @@ lf_status lf_get_march_stats(lf_ctx* ctx, uint64_t out[4]) {
 lf_status lf_reset_counters(lf_ctx* ctx) {
   if (!ctx) return LF_ERR_INVALID;
   LF_HIP(ctx, hipMemsetAsync(ctx->counters_dev, 0, kMarchCounterSlots * sizeof(unsigned long long), ctx->stream));
+  if (ctx->sensor.stats_dev)
+    LF_HIP(ctx, hipMemsetAsync(ctx->sensor.stats_dev, 0, kSensorStats * sizeof(unsigned long long), ctx->stream));
   ctx->cull_audit_rays = 0; ctx->cull_audit_lit = 0; ctx->cull_audit_tripped = 0;
   return LF_OK;
 }

@@ -466,9 +466,29 @@ struct LfLensCamArgs {
 // (BVHAccel::total_isects, bvh.cpp:211), lens samples started / that left the front element
 constexpr int kSceneCounters = 4;
 
+// ---- sensor ghosts (lf_set_sensor_reflectance, lf_set_sensor_ghosts; lf_march_sensor.hip) ------------------------------
+// The sensor's reflectance per index column (n_refl = 0: none installed; cleared by lf_set_lens, kept by lf_focus_lens), the
+// mode and the selected interfaces (n_sel < 0: every interface but the stop, resolved against the lens of the launch), and
+// the paths' own table: one row list per (sensor path, wavelength), resident on the device.  Its dirty test is by content:
+// a launch forms the rows on the host (a few hundred, microseconds) and uploads them only where they differ from
+// table_host, what the device holds -- so a change of the lens, its focus, films, stacks, aspheric or biconic records, the
+// reflectance or the selection is caught without every setter having to know the table.
+constexpr int kSensorStats = 4;   // rays started, that reached the mirror, lost off the rectangle there, lit (ray, light) pairs
+struct LfSensorGhosts {
+  int n_refl = 0;
+  float refl[LF_MAX_LAMBDA] = {};
+  int mode = LF_SENSOR_GHOSTS_OFF;
+  int n_sel = -1;
+  int sel[LF_MAX_SURFACES] = {};
+  unsigned char* table_dev = nullptr;
+  size_t table_cap = 0;
+  std::vector<unsigned char> table_host;
+  unsigned long long* stats_dev = nullptr;   // kSensorStats x u64, allocated by the first launch
+};
+
 // ---- timing ---------------------------------------------------------------------------------
 enum LfKernelId { LFK_MARCH = 0, LFK_FLARE_LAYER, LFK_GHOST_RASTER, LFK_DFT, LFK_FRAME_SETUP,
-                  LFK_TONEMAP, LFK_EXCHANGE, LFK_SCENE, LFK_CULL, LFK_CULL_AUDIT, LFK_CULL_CACHE_BUILD, LFK_FLARE_VIS, LFK_COUNT };
+                  LFK_TONEMAP, LFK_EXCHANGE, LFK_SCENE, LFK_CULL, LFK_CULL_AUDIT, LFK_CULL_CACHE_BUILD, LFK_FLARE_VIS, LFK_MARCH_SENSOR, LFK_COUNT };
 
 struct LfTimedLaunch { int kernel; hipEvent_t start, stop; };
 
@@ -659,6 +679,7 @@ struct lf_ctx {
   int march_k = 1;                             // wavelengths (rays per lane) that walk together
   int march_fix_bits = 36;                     // the last launch's fixed-point exponent (lf_get_march_fix_bits)
   bool events_dirty = true;
+  LfSensorGhosts sensor;                       // the sensor's mirror: reflectance, mode, selection and the paths' table
 
   // multi-GPU (lf_group.hip): the communicator this context belongs to, staging for the exchange
   void* comm = nullptr;          // ncclComm_t, or null (single GPU / rehearsal group)
@@ -858,6 +879,12 @@ lf_status lfk_asphere_events(lf_ctx* ctx, const float* consts16, int reflect, in
 lf_status lfk_biconic_events(lf_ctx* ctx, const float* consts16, int reflect, size_t n, const float* d_rays, float* d_out,
                              int* d_fates);
 lf_status lfk_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, int n, const float* d_xy, const float* d_uv, float* d_out);
+// lf_march_sensor.hip: the sensor ghosts -- the frame's launch behind (add) or instead of the ordinary march, one explicit ray
+// per lane along the sensor path of interface i, and what lf_destroy frees
+lf_status lfk_march_sensor(lf_ctx* ctx, int spp, uint64_t key, bool add);
+lf_status lfk_march_sensor_path_rays(lf_ctx* ctx, int lambda, int i, int n, const float* d_xy, const float* d_uv, float* d_out);
+int lf_sensor_selection(const lf_ctx* ctx, int out[LF_MAX_SURFACES]);   // the interfaces a launch marches, in order; -1: one no longer fits the lens
+void lf_sensor_free(lf_ctx* ctx);
 // lf_group.hip: in-place all-gather of equal slabs of u64 on the communicator's stream, ordered after what the main
 // stream has queued and before what it queues next
 lf_status lf_comm_allgather_u64_inplace(lf_ctx* ctx, unsigned long long* base, size_t count_per_rank);

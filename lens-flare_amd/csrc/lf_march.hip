@@ -1328,19 +1328,42 @@ static int march_strata(int spp) {
   return G;
 }
 
+// what a launch of the march refuses before anything is uploaded: the installed point lights against the front element as it
+// is NOW (lf_set_lens keeps the lights; lf_set_lights_ex's limits, lensflare.h), and, under occlusion, shadow rays that do not
+// end at them (lf_set_ghost_occlusion_reach: LF_OCCLUSION_REACH_SKY with a point light is refused)
+lf_status lf_march_lights_ready(const lf_ctx* ctx) {
+  if (!lf_has_point_light(ctx->lens)) return LF_OK;
+  const lf_status st = lf_point_lights_fit(ctx, "lf_trace_ghosts");
+  if (st != LF_OK) return st;
+  return ctx->ghost_occlusion ? lf_occlusion_reach_ready(ctx, "lf_trace_ghosts") : LF_OK;
+}
+
+// the lens of a launch (L: ctx->lens, or a copy with another pupil disc) on the launch's fixed-point grid, and behind it the
+// occlusion record: the kernels scale by the literal 2^36 and back, the device's radiances carry 2^(bits - 36) (exact)
+lf_status lf_march_upload_lens(lf_ctx* ctx, const LfLensDev& L, int bits) {
+  LfLensDev up = L;
+  for (int c = 0; c < 3; c++) up.sun_radiance[c] = std::ldexp(L.sun_radiance[c], bits - 36);
+  for (int k = 0; k < up.n_lights; k++)
+    for (int c = 0; c < 3; c++) up.light_radiance[k][c] = std::ldexp(L.light_radiance[k][c], bits - 36);
+  // (pageable source of an asynchronous copy: the runtime stages it before the call returns)
+  LF_HIP(ctx, hipMemcpyAsync(ctx->lens_dev, &up, sizeof(LfLensDev), hipMemcpyHostToDevice, ctx->stream));
+  // ghost occlusion: the scene, the camera and the mapping as they stand at THIS launch (a later lf_set_scene / lf_set_camera
+  // is picked up by the next one), behind the lens; off: no kernel launched reads the record
+  if (ctx->ghost_occlusion) {
+    LfOcclDev occl;
+    const lf_status st = lf_fill_occlusion(ctx, ctx->ghost_occl_wpm, &occl);
+    if (st != LF_OK) return st;
+    LF_HIP(ctx, hipMemcpyAsync((char*)ctx->lens_dev + kLensOcclOffset, &occl, sizeof(occl), hipMemcpyHostToDevice, ctx->stream));
+  }
+  return LF_OK;
+}
+
 // what a launch uploads before anything runs: the event program, the lens (with the launch's fixed-point grid), the paths
 static lf_status march_upload(lf_ctx* ctx, int spp, int total_paths = 0) {
   ctx->lens.pitch = ctx->sensor_w_mm / (float)ctx->W;
-  if (lf_has_point_light(ctx->lens)) {
-    // the installed point lights against the front element as it is NOW: lf_set_lens keeps the lights, a launch through a
-    // lens whose front element has come too close to one is refused (lf_set_lights_ex's limits, lensflare.h)
-    const lf_status st = lf_point_lights_fit(ctx, "lf_trace_ghosts");
+  {
+    const lf_status st = lf_march_lights_ready(ctx);
     if (st != LF_OK) return st;
-    // ... and their shadow rays have to end at them (lf_set_ghost_occlusion_reach): under LF_OCCLUSION_REACH_SKY the launch is refused
-    if (ctx->ghost_occlusion) {
-      const lf_status reach = lf_occlusion_reach_ready(ctx, "lf_trace_ghosts");
-      if (reach != LF_OK) return reach;
-    }
   }
   if (ctx->events_dirty) {
     lf_status st = build_event_table(ctx);
@@ -1352,20 +1375,8 @@ static lf_status march_upload(lf_ctx* ctx, int spp, int total_paths = 0) {
     // together (u64)(v 2^bits) and back, as the contract says
     const int bits = lf_march_fix_bits(ctx->lens, total_paths > 0 ? total_paths : ctx->pairs.n, spp);
     ctx->march_fix_bits = bits;
-    LfLensDev up = ctx->lens;
-    for (int c = 0; c < 3; c++) up.sun_radiance[c] = std::ldexp(ctx->lens.sun_radiance[c], bits - 36);
-    for (int k = 0; k < up.n_lights; k++)
-      for (int c = 0; c < 3; c++) up.light_radiance[k][c] = std::ldexp(ctx->lens.light_radiance[k][c], bits - 36);
-    // (pageable source of an asynchronous copy: the runtime stages it before the call returns)
-    LF_HIP(ctx, hipMemcpyAsync(ctx->lens_dev, &up, sizeof(LfLensDev), hipMemcpyHostToDevice, ctx->stream));
-    // ghost occlusion: the scene, the camera and the mapping as they stand at THIS launch (a later lf_set_scene / lf_set_camera
-    // is picked up by the next one), behind the lens; off: no kernel launched reads the record
-    if (ctx->ghost_occlusion) {
-      LfOcclDev occl;
-      const lf_status st = lf_fill_occlusion(ctx, ctx->ghost_occl_wpm, &occl);
-      if (st != LF_OK) return st;
-      LF_HIP(ctx, hipMemcpyAsync((char*)ctx->lens_dev + kLensOcclOffset, &occl, sizeof(occl), hipMemcpyHostToDevice, ctx->stream));
-    }
+    const lf_status st = lf_march_upload_lens(ctx, ctx->lens, bits);
+    if (st != LF_OK) return st;
   }
   LF_HIP(ctx, hipMemcpyAsync(ctx->pairs_dev, &ctx->pairs, sizeof(LfPairsDev), hipMemcpyHostToDevice,
                              ctx->stream));
@@ -1386,6 +1397,65 @@ lf_status lfk_cull_prepare(lf_ctx* ctx, int spp) {
   return st;
 }
 
+// The launch arguments of a march over this context's share of the frame -- the sampling specification, the band, the deal,
+// the wave tiles and the split of a tile's samples over workgroups -- for the ordinary launch (march_launch) and for the
+// sensor paths' (lf_march_sensor.hip): ONE definition, so that bands, deals and sample groups are the same by construction.
+// culled: the launch marches what a cull table starts (it prefers its tiles whole).  false: the context owns no tile.
+bool lf_march_launch_args(const lf_ctx* ctx, int spp, uint64_t key, bool culled, MarchArgs* out, size_t* out_tiles) {
+  MarchArgs& a = *out;
+  const LfApertureDev& m = ctx->ap[LF_APERTURE_STARBURST];
+  size_t& tiles = *out_tiles;
+  a.mw = m.w; a.mh = m.h; a.W = ctx->W; a.H = ctx->H; a.y0 = ctx->y0; a.y1 = ctx->y1;
+  a.spp = spp;
+  a.G = march_strata(spp);
+  a.inv_G = 1.0f / (float)a.G;
+  a.sub_bits = ctx->march_sub_bits;
+  a.inv_sub = 1.0f / (float)(1 << a.sub_bits);
+  a.key = make_uint2((unsigned)key, (unsigned)(key >> 32));
+  a.inv_stop_h = 1.0f / ctx->lens.stop_h;
+  a.half_w = 0.5f * (float)ctx->W; a.half_h = 0.5f * (float)ctx->H;
+  a.vz = ctx->lens.pupil_z - ctx->lens.z_sensor;
+  a.accumulate = ctx->ghost_accumulate ? 1 : 0;
+  a.xs = ctx->march_xstride_log2;
+  a.lobe_thr = lf_march_lobe_thr(ctx->lens);      // candidate selection (the contract: lf_internal.h)
+  // tile rows (8 sensor rows each) of the band that belong to this context's interleave phase -- or, the frame dealt by
+  // blocks, the 64 wave tiles of every block of this context's
+  a.deal = lf_deal_of(ctx);
+  if (a.deal.bx > 0 && a.deal.n > 1) {
+    const int nblk = a.deal.bx * ((ctx->H + (1 << kDealBlockLog2) - 1) >> kDealBlockLog2);
+    const int n_own = (nblk - a.deal.rank + a.deal.n - 1) / a.deal.n;
+    if (n_own <= 0) return false;
+    a.trow0 = 0; a.tperiod = 1;
+    tiles = (size_t)n_own * 64;
+  } else {
+    a.deal.bx = 0;
+    const int t_lo = ctx->y0 / 8, t_hi = (ctx->y1 + 7) / 8;  // [t_lo, t_hi)
+    const int period = a.deal.n, phase = a.deal.rank;
+    int first = t_lo + ((phase - t_lo) % period + period) % period;
+    if (first >= t_hi) return false;
+    const int n_trows = (t_hi - 1 - first) / period + 1;
+    a.trow0 = first; a.tperiod = period;
+    tiles = (size_t)n_trows * ((((size_t)ctx->W + (8u << a.xs) - 1) >> (3 + a.xs)) << a.xs);
+  }
+  // A launch that covers only part of the frame (one GPU's share) splits each tile's samples over
+  // `sgroups` workgroups (power of two): more, shorter workgroups keep its tail short -- but a workgroup
+  // needs >= 64 samples to amortise its set-up and its 192 global atomics.  The whole frame on one GPU
+  // stays unsplit: the split is worth another 0.5 % there and costs 5x the HBM write traffic (atomics).
+  // Measured per share of the 1080p bench frame (profiles/r03_share_timing.json): 1 / 2 / 2 / 2 groups
+  // for 1, 1/2, 1/4, 1/8 of the frame.
+  // The culled march (round 6: the started paths' common leg once) prefers its tiles whole: per rank of the block deal,
+  // 1 / 2 / 4 / 8 groups: 4.86 / 4.91 / 5.35 / 6.52 ms for 1/8 of the bench frame, 9.09 / 9.38 / 10.4 / 12.7 for 1/4
+  // (profiles/r06_cull_bounds.txt) -- split only launches of a few hundred tiles.
+  a.sgroups = 1; a.tail_from = 0; a.tail_groups = 1;
+  if (culled) {
+    while (tiles * a.sgroups < 2000 && a.sgroups * 2 * 64 <= spp) a.sgroups *= 2;
+  } else {
+    while (tiles * a.sgroups < 8000 && a.sgroups * 2 * 64 <= spp) a.sgroups *= 2;
+    if (a.sgroups == 1 && tiles < 20000 && 2 * 64 <= spp) a.sgroups = 2;
+  }
+  return true;
+}
+
 // one launch of the march over the selection ctx->pairs holds.  A selection of more than 64 paths (a mask's bits) is
 // marched culled in TWO such launches over its halves (lfk_march below): chunk c of n_chunks, the fixed-point grid sized
 // for all total_paths, the integer sums of both halves in `accum` (exact, so the frame is the one launch's), converted
@@ -1404,55 +1474,8 @@ static lf_status march_launch(lf_ctx* ctx, int spp, uint64_t key, int chunk, int
     return LF_OK;
   }
   MarchArgs a;
-  a.mw = m.w; a.mh = m.h; a.W = ctx->W; a.H = ctx->H; a.y0 = ctx->y0; a.y1 = ctx->y1;
-  a.spp = spp;
-  a.G = march_strata(spp);
-  a.inv_G = 1.0f / (float)a.G;
-  a.sub_bits = ctx->march_sub_bits;
-  a.inv_sub = 1.0f / (float)(1 << a.sub_bits);
-  a.key = make_uint2((unsigned)key, (unsigned)(key >> 32));
-  a.inv_stop_h = 1.0f / ctx->lens.stop_h;
-  a.half_w = 0.5f * (float)ctx->W; a.half_h = 0.5f * (float)ctx->H;
-  a.vz = ctx->lens.pupil_z - ctx->lens.z_sensor;
-  a.accumulate = ctx->ghost_accumulate ? 1 : 0;
-  a.xs = ctx->march_xstride_log2;
-  a.lobe_thr = lf_march_lobe_thr(ctx->lens);      // candidate selection (the contract: lf_internal.h)
-  // tile rows (8 sensor rows each) of the band that belong to this context's interleave phase -- or, the frame dealt by
-  // blocks, the 64 wave tiles of every block of this context's
-  a.deal = lf_deal_of(ctx);
   size_t tiles;
-  if (a.deal.bx > 0 && a.deal.n > 1) {
-    const int nblk = a.deal.bx * ((ctx->H + (1 << kDealBlockLog2) - 1) >> kDealBlockLog2);
-    const int n_own = (nblk - a.deal.rank + a.deal.n - 1) / a.deal.n;
-    if (n_own <= 0) return LF_OK;
-    a.trow0 = 0; a.tperiod = 1;
-    tiles = (size_t)n_own * 64;
-  } else {
-    a.deal.bx = 0;
-    const int t_lo = ctx->y0 / 8, t_hi = (ctx->y1 + 7) / 8;  // [t_lo, t_hi)
-    const int period = a.deal.n, phase = a.deal.rank;
-    int first = t_lo + ((phase - t_lo) % period + period) % period;
-    if (first >= t_hi) return LF_OK;
-    const int n_trows = (t_hi - 1 - first) / period + 1;
-    a.trow0 = first; a.tperiod = period;
-    tiles = (size_t)n_trows * ((((size_t)ctx->W + (8u << a.xs) - 1) >> (3 + a.xs)) << a.xs);
-  }
-  // A launch that covers only part of the frame (one GPU's share) splits each tile's samples over
-  // `sgroups` workgroups (power of two): more, shorter workgroups keep its tail short -- but a workgroup
-  // needs >= 64 samples to amortise its set-up and its 192 global atomics.  The whole frame on one GPU
-  // stays unsplit: the split is worth another 0.5 % there and costs 5x the HBM write traffic (atomics).
-  // Measured per share of the 1080p bench frame (profiles/r03_share_timing.json): 1 / 2 / 2 / 2 groups
-  // for 1, 1/2, 1/4, 1/8 of the frame.
-  // The culled march (round 6: the started paths' common leg once) prefers its tiles whole: per rank of the block deal,
-  // 1 / 2 / 4 / 8 groups: 4.86 / 4.91 / 5.35 / 6.52 ms for 1/8 of the bench frame, 9.09 / 9.38 / 10.4 / 12.7 for 1/4
-  // (profiles/r06_cull_bounds.txt) -- split only launches of a few hundred tiles.
-  a.sgroups = 1; a.tail_from = 0; a.tail_groups = 1;
-  if (lf_cull_reason_of(ctx, a.G) == LF_CULL_APPLIED) {
-    while (tiles * a.sgroups < 2000 && a.sgroups * 2 * 64 <= spp) a.sgroups *= 2;
-  } else {
-    while (tiles * a.sgroups < 8000 && a.sgroups * 2 * 64 <= spp) a.sgroups *= 2;
-    if (a.sgroups == 1 && tiles < 20000 && 2 * 64 <= spp) a.sgroups = 2;
-  }
+  if (!lf_march_launch_args(ctx, spp, key, lf_cull_reason_of(ctx, march_strata(spp)) == LF_CULL_APPLIED, &a, &tiles)) return LF_OK;
 #ifdef LF_EXPERIMENTS
   if (const char* sgv = std::getenv("LF_MARCH_SGROUPS")) {
     int v = std::atoi(sgv);

@@ -24,6 +24,7 @@
 #include "lf_march_common.h"
 #include "lf_asphere.h"
 #include "lf_biconic.h"
+#include "lf_path_table.h"
 
 using namespace lfm;
 
@@ -265,32 +266,7 @@ __global__ __launch_bounds__(256) void k_biconic_events(AsphEventArgs c, int ref
   fates[i] = h.fate;
 }
 
-// ---- lf_march_path_rays: the sequence of pair (i, j) for ONE wavelength, one row per event (host: build_path_table) -------
-struct alignas(32) LfPathRow {
-  float dzv, curv, ch, c2, sc, h2, sgn;
-  int kind;        // LF_EV_REFLECT | LF_EV_STOP | LF_EV_FLAT | LF_EV_ASPH | LF_EV_BICONIC (then `asph` holds {1/Rx, kx, ky})
-  float cn22, rn2, delta, fs, fo, fi;
-  int coated;      // 0 bare; 1: a film, `coat` holds its constants; else 2 | the byte offset, from this row, of its stack record
-  int pad;
-  LfCoatK coat;
-  LfAsphRec asph;
-};
-constexpr int kPathRowsMax = 3 * LF_MAX_SURFACES;
-struct LfPathDev {
-  int n;
-  float inv_stop_h, front_zv, n_start;
-  int pad[4];
-  LfPathRow row[kPathRowsMax];
-};
-constexpr size_t kPathStackBytes = (size_t)kPathRowsMax * 4 * (4 + 5 * LF_MAX_COAT_LAYERS);
-struct PathCoat {
-  const LfPathRow* row;
-  __device__ __forceinline__ bool on() const { return row->coated != 0; }
-  __device__ __forceinline__ bool stacked() const { return (row->coated & 2) != 0; }
-  __device__ __forceinline__ LfCoatK get() const { return row->coat; }
-  __device__ __forceinline__ StackPlain stack() const { return StackPlain{(const int*)((const char*)row + (row->coated & ~3))}; }
-};
-
+// ---- lf_march_path_rays: the sequence of pair (i, j) for ONE wavelength, one row per event (lf_path_table.h; host: build_path_table) ----
 template <bool FILT, bool COAT, bool BIC = false>
 __global__ __launch_bounds__(256) void k_march_path_rays(const LfLensDev* __restrict__ lens, const LfPathDev* __restrict__ P,
                                                          const float* __restrict__ mask, int mw, int mh, int n,
@@ -348,48 +324,11 @@ lf_status build_path_table(lf_ctx* ctx, int l, int i, int j, std::vector<unsigne
   P.inv_stop_h = 1.0f / L.stop_h;
   P.front_zv = L.surf[0].zv;
   P.n_start = L.n_start[l];
-  const LfCoatings& C = ctx->coat;
-  const LfAspheres& A = ctx->asph;
   lf_status st = LF_OK;
   auto put = [&](int k, int from, bool reflect, bool fwd) {
     if (P.n >= kPathRowsMax) { st = LF_ERR_STATE; return; }
-    const LfSurfaceDev& s = L.surf[k];
-    LfPathRow& w = P.row[P.n++];
-    w.dzv = (from >= L.n_surf ? L.z_sensor : L.surf[from].zv) - s.zv;
-    w.sgn = fwd ? 1.0f : -1.0f;
-    w.curv = s.curv; w.ch = 0.5f * s.curv; w.c2 = 2.0f * s.curv; w.sc = w.sgn * s.curv; w.h2 = s.h2;
-    w.kind = (reflect ? LF_EV_REFLECT : 0) | (s.is_stop != 0.0f ? LF_EV_STOP : 0) | (s.curv == 0.0f ? LF_EV_FLAT : 0);
-    const float n_in = fwd ? s.n_before[l] : s.n_after[l], n_out = fwd ? s.n_after[l] : s.n_before[l];
-    const float n_in2 = n_in * n_in, n_out2 = n_out * n_out;
-    w.cn22 = w.c2 * n_in2;
-    w.rn2 = s.curv == 0.0f ? 0.0f : s.radius / n_in2;
-    w.delta = n_out2 - n_in2;
-    const float q = std::fmaf(n_out2, n_in, n_in2 * n_out);
-    w.fs = 1.0f / (n_in + n_out);
-    w.fo = n_out2 / q;
-    w.fi = n_in2 / q;
-    if (s.is_stop != 0.0f) return;
-    w.coated = C.n > 0 && C.thickness_nm[k] > 0.0f ? 1 : 0;
-    if (w.coated) lf_coat_constants(n_in, C.index[(size_t)l * L.n_surf + k], n_out, C.thickness_nm[k], C.lambda_nm[l], &w.coat);
-    if (C.n_stacked > 0 && C.n_layers[k] >= 2) {
-      const size_t sub = sizeof(float) * kStackDwords(C.n_layers[k]);
-      if (next_stack + sub > buf.size()) { st = LF_ERR_STATE; return; }
-      w.coated = 2 | (int)(next_stack - (size_t)((const unsigned char*)&w - buf.data()));
-      lf_stack_constants_of(C, L.n_surf, L.n_lambda, k, l, fwd, n_in, n_out, reinterpret_cast<float*>(buf.data() + next_stack));
-      next_stack += sub;
-    }
-    const LfBiconics& B = ctx->bic;
-    const int rec_kind = lf_surface_record_kind(ctx, k);
-    if (rec_kind == LF_EV_BICONIC) {
-      w.kind |= LF_EV_BICONIC;
-      w.asph.kappa = B.rx[k] == 0.0f ? 0.0f : 1.0f / B.rx[k];
-      w.asph.a[0] = B.kx[k];
-      w.asph.a[1] = B.ky[k];
-    } else if (rec_kind == LF_EV_ASPH) {
-      w.kind |= LF_EV_ASPH;
-      w.asph.kappa = A.kappa[k];
-      for (int m = 0; m < LF_MAX_ASPH_COEF; m++) w.asph.a[m] = A.coef[(size_t)m * L.n_surf + k];
-    }
+    const size_t row_off = (size_t)((const unsigned char*)&P.row[P.n++] - buf.data());
+    if (lf_path_row_fill(ctx, l, k, from, reflect, fwd, buf.data(), row_off, &next_stack, buf.size()) != LF_OK) st = LF_ERR_STATE;
   };
   if (i < 0) {
     for (int k = L.n_surf - 1; k >= 0; k--) put(k, k + 1, false, false);

@@ -400,3 +400,11 @@ __device__ __forceinline__ void weighted_remarch(Ray& rw, const int* __restrict_
 }
 
 }  // namespace lfm
+
+// host, lf_march.hip: what every launch of a march over this context's share of the frame has in common -- the refusals of
+// the installed lights, the launch arguments (false: the context owns no tile) and the upload of the lens on the launch's
+// fixed-point grid with the occlusion record behind it.  The ordinary launch and the sensor paths' (lf_march_sensor.hip)
+// both go through them.
+lf_status lf_march_lights_ready(const lf_ctx* ctx);
+bool lf_march_launch_args(const lf_ctx* ctx, int spp, uint64_t key, bool culled, lfm::MarchArgs* out, size_t* out_tiles);
+lf_status lf_march_upload_lens(lf_ctx* ctx, const LfLensDev& L, int bits);
