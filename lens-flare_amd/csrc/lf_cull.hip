@@ -240,6 +240,52 @@ __device__ __forceinline__ lanemask surface_rows(Ray (&r)[K], const lanemask (&a
   return died;
 }
 
+// One row (sequence dword `cur`) of the geometry-first march on a state of K rays (s, alive, nlive): the common leg's, whose
+// rows count for the `mult` started paths that still share it, or a path's own copy of it (mult = 1).  A ray the row ends
+// counts `mult` times in its fate; a state that lost its last ray leaves its loop through the row counter (e = end).
+// (the scalar unit is what the row loops wait for: the row's kind is decided ONCE for its K wavelengths -- curved glass
+// crossed, by far the most frequent, first -- and the event inlined with its flags constant, so that the row's end tests
+// one thing)
+template <int K, int VAR>
+__device__ __forceinline__ void started_row(Ray (&s)[K], lanemask (&alive)[K], unsigned& nlive, unsigned cur, unsigned mult,
+                                            const LfProgRow* __restrict__ recs, const float* __restrict__ mask, const MarchArgs& a,
+                                            float inv_stop_h, PathTally& T, int& e, int end) {
+  const LfProgRow wr = load_prec(recs, cur & 0xffffu);
+  const unsigned kind = cur >> 16;
+  lanemask okv[K], gv[K], died = 0ull;
+  if (__builtin_expect(kind == 0u, 1)) {
+    died = surface_rows<K, false, false>(s, alive, wr, okv, gv);
+  } else if (kind & LF_EV_STOP) {
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      if (K > 1 && __builtin_expect(alive[j] == 0ull, 0)) { okv[j] = 0ull; gv[j] = 0ull; continue; }
+      okv[j] = stop_event_var<false, VAR>(s[j], wr.dzv, wr.h2, inv_stop_h, mask, a.mw, a.mh);
+      gv[j] = okv[j];
+      died |= alive[j] & ~okv[j];
+    }
+  } else if (kind & LF_EV_REFLECT) {
+    if (kind & LF_EV_FLAT) died = surface_rows<K, true, true>(s, alive, wr, okv, gv);
+    else died = surface_rows<K, true, false>(s, alive, wr, okv, gv);
+  } else {
+    died = surface_rows<K, false, true>(s, alive, wr, okv, gv);
+  }
+  if (__builtin_expect(died != 0ull, 0)) {
+    // (a stop row: gv = okv, every ray it ends is clipped; a surface row: missed / outside the aperture, or totally reflected)
+    const bool stop_row = (kind & LF_EV_STOP) != 0;
+#pragma unroll
+    for (int j = 0; j < K; j++) {
+      const unsigned nd = (unsigned)__popcll(alive[j] & ~okv[j]);
+      const unsigned nv = (unsigned)__popcll(alive[j] & ~gv[j]);
+      T.n_clip += stop_row ? (unsigned long long)nd * mult : 0ull;
+      T.n_vign += stop_row ? 0ull : (unsigned long long)nv * mult;
+      T.n_tir += stop_row ? 0ull : (unsigned long long)(nd - nv) * mult;
+      nlive -= nd;
+      alive[j] &= okv[j];
+    }
+    if (nlive == 0u) e = end;
+  }
+}
+
 template <int K, int VAR>
 __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                                                   const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
@@ -254,14 +300,18 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
   const float sx = lens->sun_dir[0], sy = lens->sun_dir[1], sz = lens->sun_dir[2];
   const float inv_1mc = lens->sun_inv_one_minus_cos, sun_ss = lens->sun_ss;
   const unsigned n_started = (unsigned)__popcll(todo);
+  // the sample's re-march tallies, added to the 64-bit ones once: at most kCullMaxPaths paths x LF_MAX_LAMBDA wavelengths of
+  // at most 0xffff events (the s_meta packing), 64 lanes each
+  static_assert((unsigned long long)kCullMaxPaths * LF_MAX_LAMBDA * 0xffffull * 64ull < (1ull << 32), "a sample's re-march rows overflow 32 bits");
+  unsigned rm_lane = 0u, rm_rows = 0u;
   for (int g = 0; g < n_groups; g++) {
     const LfProgRow* const recs = rec_table + (size_t)g * (size_t)prog_recs;
     const LfWeightRow* const wrecs = wrec_table + (size_t)g * (size_t)prog_recs;
-    // ONE running state: the common leg while it is common, then the path that left it -- whose start (the leg's state at
-    // the fork) is parked in p and taken back when the path is done
-    Ray r[K], p[K];
-    lanemask alive[K], palive[K];
-    unsigned nlive = 0u, pn = 0u;
+    // TWO states: r, the common leg, which only ever runs the leg's rows and stays where it is; c, the copy of it a started
+    // path takes at its fork (or at the leg's end: the primary path) and runs its own rows on -- nothing is taken back
+    Ray r[K], c[K];
+    lanemask alive[K], calive[K];
+    unsigned nlive = 0u;
 #pragma unroll
     for (int j = 0; j < K; j++) {
       r[j] = Ray{X, Y, 0.0f, fmaf(X, X, Y * Y), s0.dx, s0.dy, s0.dz, s0.w0, 1.0f};
@@ -269,7 +319,6 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
       r[j].dx *= ns; r[j].dy *= ns; r[j].dz *= ns;
       alive[j] = (g * K + j < n_lambda) ? active_mask : 0ull;
       nlive += (unsigned)__popcll(alive[j]);
-      p[j] = r[j]; palive[j] = alive[j];
     }
     T.n_rays += (unsigned long long)nlive * n_started;
     int depth = 0;            // events of the common leg done
@@ -282,81 +331,56 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
       const int mx = __builtin_amdgcn_readfirstlane(meta.x);       // (q is wave-uniform: so are the path's lengths and rows)
       const int n_ev = mx >> 16, L = mx & 0xffff;
       const int* const seq = seq_table + __builtin_amdgcn_readfirstlane(meta.y);
-      unsigned mult = (unsigned)__popcll(left) + 1u;               // this path and those still to come share the leg so far
-      bool forked = false;
-      unsigned seg = 0u;                 // sum of the rays alive after each row of the current segment (leg / path)
-      unsigned long long ev_logical = 0ull;
-      unsigned ev_exec = 0u;
-      // (the sequence dword one row ahead, unconditionally: the table ends on a spare dword -- pack_program)
+      const unsigned mult = (unsigned)__popcll(left) + 1u;         // this path and those still to come share the leg so far
+      // (the sequence dword one row ahead, unconditionally: the leg's loop stops at L < n_ev or on the table's spare dword, the
+      // path's own on the spare dword -- pack_program)
       unsigned se = (unsigned)*(const int __attribute__((address_space(4)))*)(seq + depth);
+      // ---- the common leg, extended to where path q leaves it: rows depth .. L on r ----------------------
+      unsigned seg = 0u;                 // sum of the rays alive after each row of the segment
       int e = depth;
-      if (e < n_ev && nlive != 0u) for (;;) {
-        if (e == L) {      // the path leaves the common leg: park the leg
-#pragma unroll
-          for (int j = 0; j < K; j++) { p[j] = r[j]; palive[j] = alive[j]; }
-          pn = nlive; forked = true;
-          ev_logical = (unsigned long long)seg * mult; ev_exec = seg; seg = 0u; mult = 1u;
-        }
+      if (e < L) for (;;) {
         const unsigned cur = se;
         se = (unsigned)*(const int __attribute__((address_space(4)))*)(seq + e + 1);
-        const LfProgRow wr = load_prec(recs, cur & 0xffffu);
-        const unsigned kind = cur >> 16;
-        lanemask okv[K], gv[K], died = 0ull;
-        // (the scalar unit is what this loop waits for: the row's kind is decided ONCE for its K wavelengths -- curved glass
-        // crossed, by far the most frequent, first -- and the event inlined with its flags constant; a wave that lost its
-        // last ray leaves through the row counter, so that the row's end tests one thing)
-        if (__builtin_expect(kind == 0u, 1)) {
-          died = surface_rows<K, false, false>(r, alive, wr, okv, gv);
-        } else if (kind & LF_EV_STOP) {
-#pragma unroll
-          for (int j = 0; j < K; j++) {
-            if (K > 1 && __builtin_expect(alive[j] == 0ull, 0)) { okv[j] = 0ull; gv[j] = 0ull; continue; }
-            okv[j] = stop_event_var<false, VAR>(r[j], wr.dzv, wr.h2, inv_stop_h, mask, a.mw, a.mh);
-            gv[j] = okv[j];
-            died |= alive[j] & ~okv[j];
-          }
-        } else if (kind & LF_EV_REFLECT) {
-          if (kind & LF_EV_FLAT) died = surface_rows<K, true, true>(r, alive, wr, okv, gv);
-          else died = surface_rows<K, true, false>(r, alive, wr, okv, gv);
-        } else {
-          died = surface_rows<K, false, true>(r, alive, wr, okv, gv);
-        }
-        if (__builtin_expect(died != 0ull, 0)) {
-          // (a stop row: gv = okv, every ray it ends is clipped; a surface row: missed / outside the aperture, or totally reflected)
-          const bool stop_row = (kind & LF_EV_STOP) != 0;
-#pragma unroll
-          for (int j = 0; j < K; j++) {
-            const unsigned nd = (unsigned)__popcll(alive[j] & ~okv[j]);
-            const unsigned nv = (unsigned)__popcll(alive[j] & ~gv[j]);
-            T.n_clip += stop_row ? (unsigned long long)nd * mult : 0ull;
-            T.n_vign += stop_row ? 0ull : (unsigned long long)nv * mult;
-            T.n_tir += stop_row ? 0ull : (unsigned long long)(nd - nv) * mult;
-            nlive -= nd;
-            alive[j] &= okv[j];
-          }
-          if (nlive == 0u) e = n_ev;
-        }
+        started_row<K, VAR>(r, alive, nlive, cur, mult, recs, mask, a, inv_stop_h, T, e, L);
         seg += nlive;       // events completed: one per ray still alive after the row
-        if (++e >= n_ev) break;
+        if (++e >= L) break;
       }
-      // ... counted once for every logical path that shares the row (the leg's rows: `mult` paths), and once as executed
-      T.events += ev_logical + (unsigned long long)seg * mult;
-      T.executed += ev_exec + seg;
-      if (!forked && L < n_ev) break;       // the common leg ended for every lane before path q left it: so did every path still to come
-      if (nlive != 0u) {
-        // ---- the path is complete for nlive rays (as march_started_path) ---------------------------------
-        T.n_scene += nlive;
+      // ... counted once for every logical path that shares the row (`mult` paths), and once as executed
+      T.events += (unsigned long long)seg * mult;
+      T.executed += seg;
+      depth = L;
+      if (nlive == 0u) break;       // the common leg ended for every lane before path q left it: so did every path still to come
+      // ---- the fork: the path's own rows L .. n_ev on a copy ---------------------------------------------
+      unsigned cn = nlive;
+#pragma unroll
+      for (int j = 0; j < K; j++) { c[j] = r[j]; calive[j] = alive[j]; }
+      if (L < n_ev) {
+        unsigned own = 0u;
+        for (;;) {
+          const unsigned cur = se;
+          se = (unsigned)*(const int __attribute__((address_space(4)))*)(seq + e + 1);
+          started_row<K, VAR>(c, calive, cn, cur, 1u, recs, mask, a, inv_stop_h, T, e, n_ev);
+          own += cn;
+          if (++e >= n_ev) break;
+        }
+        T.events += own;
+        T.executed += own;
+      }
+      if (cn != 0u) {
+        // ---- the path is complete for cn rays (as march_started_path) ------------------------------------
+        T.n_scene += cn;
         lanemask lit[K], lit_any = 0ull;
+        float gq[K];       // the gate's lobe_q per wavelength: what the lit epilogue needs of the copy, which is dead from here on
         if (VAR & kVarLights) {
-          lit_any = lights_pretest<K, true, VAR>(lens, r, alive, lit);
+          lit_any = lights_pretest<K, true, VAR>(lens, c, calive, lit);
         } else {
 #pragma unroll
         for (int j = 0; j < K; j++) {
-          const float cg = fmaf(r[j].dx, sx, fmaf(r[j].dy, sy, r[j].dz * sz));
-          lit[j] = alive[j] & __ballot(cg > lobe_thr);
+          const float cg = fmaf(c[j].dx, sx, fmaf(c[j].dy, sy, c[j].dz * sz));
+          lit[j] = calive[j] & __ballot(cg > lobe_thr);
           lit_any |= lit[j];
         }
-        if (lit_any != 0ull) lit_any = lobe_gate<K>(r, lit, sx, sy, sz, sun_ss, inv_1mc);
+        if (lit_any != 0ull) lit_any = lobe_gate<K>(c, lit, sx, sy, sz, sun_ss, inv_1mc, gq);
         }
         if (lit_any != 0ull) {
           for (int j = 0; j < K; j++) {        // not unrolled: one copy of the weighted march
@@ -368,36 +392,39 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
             // the path again, alone and with its weight: the same arithmetic on the ray, so the same ray bit for bit
             Ray rw = Ray{X, Y, 0.0f, fmaf(X, X, Y * Y), s0.dx, s0.dy, s0.dz, s0.w0, 1.0f};
             { const float ns = lens->n_start[l]; rw.dx *= ns; rw.dy *= ns; rw.dz *= ns; }
-            T.n_rm_lane += (unsigned long long)((unsigned)n_ev * (unsigned)__popcll(lj));
-            T.n_rm_rows += (unsigned)n_ev;
+            rm_lane += (unsigned)n_ev * (unsigned)__popcll(lj);
+            rm_rows += (unsigned)n_ev;
             weighted_remarch<VAR>(rw, seq, n_ev, j, recs, wrecs, wrec_table, mask, inv_stop_h, a.mw, a.mh);
             if (VAR & kVarLights) {
               lights_epilogue<VAR>(lens, s_chan, rw, ((lj >> lane) & 1ull) != 0ull, l, &s_acc[lane * 3], T.n_light);
               continue;
             }
-            const float qq = lobe_q(rw.dx, rw.dy, rw.dz, sx, sy, sz, sun_ss, inv_1mc);
+            // the three channel factors off ONE address, on their way while the weight is divided
+            const float* const ch = s_chan + l * 3;
+            const float ch0 = ch[0], ch1 = ch[1], ch2 = ch[2];
+            // lobe_q of the re-marched ray's direction IS the gate's, bit for bit (lobe_gate): not computed again
+            float qq = gq[0];
+#pragma unroll
+            for (int jj = 1; jj < K; jj++) qq = (j == jj) ? gq[jj] : qq;
             const float om = 1.0f - qq;
             float contrib = __fdiv_rn(rw.wn, rw.wd) * (om * om);
             contrib = (((lj >> lane) & 1ull) != 0ull && qq < 1.0f && contrib > 0.0f) ? contrib : 0.0f;
             T.n_light += contrib > 0.0f ? 1u : 0u;
+            const float chv[3] = {ch0, ch1, ch2};
 #pragma unroll
-            for (int c = 0; c < 3; c++) {
-              const float v = contrib * s_chan[l * 3 + c];
+            for (int c3 = 0; c3 < 3; c3++) {
+              const float v = contrib * chv[c3];
               const unsigned long long fx = (unsigned long long)(v * 68719476736.0f);
-              if (fx) atomicAdd(&s_acc[lane * 3 + c], fx);
+              if (fx) atomicAdd(&s_acc[lane * 3 + c3], fx);
             }
           }
         }
       }
-      if (!forked || left == 0ull) break;     // (the primary path: the common leg to its end, nothing after it; the group's last started path: the loop ends here
-                                              // anyway, and nobody reads the leg again -- no take-back)
-      // back to the common leg where path q left it
-#pragma unroll
-      for (int j = 0; j < K; j++) { r[j] = p[j]; alive[j] = palive[j]; }
-      nlive = pn;
-      depth = L;
+      if (L >= n_ev) break;     // (the primary path: the common leg to its end, nothing after it)
     }
   }
+  T.n_rm_lane += rm_lane;
+  T.n_rm_rows += rm_rows;
 }
 
 // W1: the first (and then only) march of a started path carries its Fresnel / aperture weight.  false = geometry first,
@@ -408,7 +435,7 @@ __device__ __forceinline__ void march_started_set(const LfLensDev* __restrict__ 
 // tile) and the started paths' common leg is marched once (march_started_set); otherwise (independent pixels, blocks smaller
 // than a wave tile, the weight on every event, a selection out of order) every started path is marched alone.
 #ifndef LF_SHARED_WAVES
-#define LF_SHARED_WAVES 6     // waves per SIMD of the shared-leg kernel with K > 1 (two ray states per lane: 80 VGPR, a few spilled;
+#define LF_SHARED_WAVES 6     // waves per SIMD of the shared-leg kernel with K > 1 (two ray states per lane: 76 .. 80 VGPR;
                               // a workgroup holds 2 waves per SIMD, so 5 runs as 4: 47 ms against 38 on the bench frame)
 #endif
 // MODE 0: every started path alone; 1 = SHARED (one table entry per wave and sample, the leg once: march_started_set)

@@ -35,16 +35,29 @@ __device__ __forceinline__ float lobe_q(float dx, float dy, float dz, float sx, 
 // the first march's rays: lit[j] keeps the lanes that will contribute, and a wavelength none of whose lanes will is not
 // marched again.  Behind the pre-test (a root and a division per wavelength), never on every completed path.  Returns the
 // union of the narrowed masks.
+// q[j]: the lobe_q the gate computed for wavelength j -- the value the epilogue would compute again on the re-marched ray's
+// direction, so an epilogue that takes it from here needs neither the root nor the division a second time; defined where
+// lit[j] came in non-empty (elsewhere 2: outside every lobe), and lit[j] goes out empty everywhere else.
 template <int K>
 __device__ __forceinline__ lanemask lobe_gate(const Ray (&r)[K], lanemask (&lit)[K], float sx, float sy, float sz, float ss,
-                                              float inv_1mc) {
+                                              float inv_1mc, float (&q)[K]) {
   lanemask lit_any = 0ull;
 #pragma unroll
   for (int j = 0; j < K; j++) {
-    if (lit[j] != 0ull) lit[j] &= __ballot(lobe_q(r[j].dx, r[j].dy, r[j].dz, sx, sy, sz, ss, inv_1mc) < 1.0f);
+    q[j] = 2.0f;
+    if (lit[j] != 0ull) {
+      q[j] = lobe_q(r[j].dx, r[j].dy, r[j].dz, sx, sy, sz, ss, inv_1mc);
+      lit[j] &= __ballot(q[j] < 1.0f);
+    }
     lit_any |= lit[j];
   }
   return lit_any;
+}
+template <int K>
+__device__ __forceinline__ lanemask lobe_gate(const Ray (&r)[K], lanemask (&lit)[K], float sx, float sy, float sz, float ss,
+                                              float inv_1mc) {
+  float q[K];
+  return lobe_gate<K>(r, lit, sx, sy, sz, ss, inv_1mc, q);
 }
 
 // ---- ghost occlusion (lf_set_ghost_occlusion; the kernels instantiated with kVarOccl, k_ghost_ray_visibility) ------------
