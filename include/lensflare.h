@@ -647,6 +647,48 @@ lf_status lf_biconic_event(float curvature_x, float curvature_y, float conic_x, 
 lf_status lf_biconic_events(lf_ctx* ctx, float curvature_x, float curvature_y, float conic_x, float conic_y, float semi_aperture,
                             float n_in, float n_out, int reflect, int forward, float dzv, size_t n, const float* rays,
                             float* out, int* fates);
+/* POSED INTERFACES: decentred, tilted and rotated surfaces (no reference counterpart).  Interface k of the installed lens
+ * becomes the surface
+ *   P = V_k + t + R q,   R = Rx(ax) Ry(ay) Rz(az)
+ * q on the interface as lf_set_lens, lf_set_lens_aspheres and lf_set_lens_biconics define it (vertex at the origin), V_k its
+ * nominal vertex on the axis, and
+ *   on[k]                  != 0: interface k carries a record (a record of zeros is one, as for biconics)
+ *   decentre[3 k .. 3 k+2] t = (dx, dy, dz) in mm                                         (NULL: zeros)
+ *   tilt_deg[3 k .. 3 k+2] (ax, ay, az), right-handed, in degrees; |ax|, |ay| <= 30, az in [-180, 180]   (NULL: zeros)
+ * The turn about the surface's own z comes first: az is what rotates a cylinder's axis (az = 90 turns power in x into
+ * power in y).  Each interface is posed on its own -- a record is no cumulative coordinate break; an ELEMENT tilted about a
+ * pivot needs different records on its faces (the Python helper pose_group writes them).
+ * on == NULL clears the records; lf_set_lens clears them, lf_focus_lens keeps them.  Refused with LF_ERR_INVALID and a
+ * message that names the interface, the previous state kept: a wrong n_surfaces, a value that is not finite, a record on
+ * the stop (a turned iris is a turned mask texture; a decentred one would move the stop event and the pupil aim), an angle
+ * out of range.
+ * A lens file carries them as `pose k dx dy dz ax ay az` lines (lf_load_lens_file; data/dgauss11_decentred.lens).
+ * Such a lens is marched by the aspheric lens's kernel with one more branch (k_march_asph<VAR, true, true>, lf_pose.h): the
+ * ray is carried into the surface's frame, meets the interface through the aspheric or the biconic event (a sphere or a
+ * plane as a biconic), and is carried back -- the clear aperture is the glass's own, a ray that meets the surface from
+ * behind is vignetted.  No cull table is built (LF_CULL_POSED); lights, films, stacks, occlusion, bands and deals work as on
+ * any lens; lf_march_path_rays and lf_generate_lens_rays follow the records.  Refused with LF_ERR_UNSUPPORTED: sensor ghosts
+ * under LF_SENSOR_GHOSTS_ADD / _ONLY (at lf_trace_ghosts) with lf_march_sensor_path_rays, and the lens camera's scene image under either setting of
+ * lf_set_lens_camera_surfaces.  Everything paraxial -- pupils, focus, efl, the hand-over of a flare to a light -- stays the
+ * centred lens's. */
+lf_status lf_set_lens_poses(lf_ctx* ctx, int n_surfaces, const int* on, const float* decentre, const float* tilt_deg);
+/* what is installed (any pointer may be NULL): on n_surfaces, decentre and tilt_deg 3 n_surfaces, n_posed = the records */
+lf_status lf_get_lens_poses(lf_ctx* ctx, int n_surfaces, int* on, float* decentre, float* tilt_deg, int* n_posed);
+/* host arithmetic, no device: ONE event of ONE ray on a posed interface, the definition the kernels run (bit for bit:
+ * lf_pose_events is its device twin).  The arguments of lf_biconic_event, plus an aspheric record -- aspheric != 0: the
+ * interface is the surface of revolution of curvature_y with conic constant kappa and coef[0 .. n_coef) = A4, A6 .. (the
+ * biconic arguments are then not read); aspheric == 0: the biconic (curvature_x = curvature_y, conics 0: a sphere) -- and
+ * the pose as lf_set_lens_poses takes it.  Output and fates as lf_biconic_event's; the ray in lens coordinates, z from the
+ * interface's NOMINAL vertex. */
+lf_status lf_pose_event(float curvature_x, float curvature_y, float conic_x, float conic_y, int aspheric, float kappa,
+                        const float* coef, int n_coef, const float decentre[3], const float tilt_deg[3], float semi_aperture,
+                        float n_in, float n_out, int reflect, int forward, float dzv, const float ray_in[6], float ray_out[6],
+                        float* sq, float* ct, int* fate);
+/* the same event for n rays on the device: rays n x 6 as ray_in, out n x 8 = {ray_out, sq, ct}, fates n ints */
+lf_status lf_pose_events(lf_ctx* ctx, float curvature_x, float curvature_y, float conic_x, float conic_y, int aspheric, float kappa,
+                         const float* coef, int n_coef, const float decentre[3], const float tilt_deg[3], float semi_aperture,
+                         float n_in, float n_out, int reflect, int forward, float dzv, size_t n, const float* rays, float* out,
+                         int* fates);
 /* what lf_set_lens / lf_load_lens_file installed (any pointer may be NULL); efl_mm = lf_paraxial_efl at
  * the middle wavelength (0 for an afocal prescription) */
 lf_status lf_get_lens_info(lf_ctx* ctx, int* n_surfaces, int* stop_index, int* n_lambda, float* sensor_width_mm,
@@ -1099,8 +1141,10 @@ typedef enum {
                                        do not bracket what lies between, the pre-pass's dispersion bound does not hold */
   LF_CULL_ASPHERIC = 9,             /* the lens has an aspheric interface (lf_set_lens_aspheres): the pre-pass's bounds were found
                                        on spherical designs, no table is built and neither pre-pass nor audit launches */
-  LF_CULL_ANAMORPHIC = 10           /* the lens has a biconic interface (lf_set_lens_biconics): likewise, and the pre-pass's boxes
+  LF_CULL_ANAMORPHIC = 10,          /* the lens has a biconic interface (lf_set_lens_biconics): likewise, and the pre-pass's boxes
                                        assume surfaces of revolution */
+  LF_CULL_POSED = 11                /* the lens has a posed interface (lf_set_lens_poses): likewise, and the boxes assume a
+                                       centred lens */
 } lf_cull_reason;
 lf_status lf_get_cull_reason(lf_ctx* ctx, int* reason);
 /* THE AUDIT.  The pre-pass's bounds are second-order estimates from 15 rays per box: conservative on every

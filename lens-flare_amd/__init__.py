@@ -52,6 +52,7 @@ ABI_SYMBOLS = [
     "lf_set_lens_coating_stacks", "lf_get_lens_coating_stacks", "lf_coating_stack_reflectance",
     "lf_set_lens_aspheres", "lf_get_lens_aspheres", "lf_asphere_sag", "lf_asphere_event", "lf_asphere_events", "lf_march_path_rays",
     "lf_set_lens_biconics", "lf_get_lens_biconics", "lf_get_lens_meridian_scales", "lf_biconic_sag", "lf_biconic_event", "lf_biconic_events",
+    "lf_set_lens_poses", "lf_get_lens_poses", "lf_pose_event", "lf_pose_events",
     "lf_set_sensor_reflectance", "lf_get_sensor_reflectance", "lf_set_sensor_ghosts", "lf_get_sensor_ghosts",
     "lf_march_sensor_path_rays", "lf_sensor_path_sequence", "lf_sensor_mirror_event", "lf_get_sensor_ghost_stats",
     "lf_set_mask_filter", "lf_get_mask_filter", "lf_mask_lookup",
@@ -172,7 +173,7 @@ def load_lens_file(path):
     """Parse a .lens prescription (see data/dgauss11.lens) -> dict of float32 arrays."""
     if not os.path.isabs(path) and not os.path.exists(path):
         path = os.path.join(DATA, path)
-    rows, sensor_w, lambda_nm, coats, layers, asphs, bics, sens = [], 36.0, None, [], [], [], [], None
+    rows, sensor_w, lambda_nm, coats, layers, asphs, bics, sens, poses = [], 36.0, None, [], [], [], [], None, []
     for line in open(path):
         line = line.split("#")[0].strip()
         if not line:
@@ -204,6 +205,11 @@ def load_lens_file(path):
             if len(t) < 3 or len(t) > 5:
                 raise ValueError(f"{path}: a biconic line is `biconic k Rx [kx [ky]]`")
             bics.append((int(t[1]), [float(v) for v in t[2:]]))
+            continue
+        if t[0] == "pose":           # pose k dx dy dz ax ay az  (lf_set_lens_poses; mm and degrees)
+            if len(t) != 8:
+                raise ValueError(f"{path}: a pose line is `pose k dx dy dz ax ay az`")
+            poses.append((int(t[1]), [float(v) for v in t[2:]]))
             continue
         rows.append([float(v) for v in t])
     rows = np.array(rows, np.float64)
@@ -243,6 +249,19 @@ def load_lens_file(path):
             on[k] = 1
             rec[:len(v), k] = v
         lens["biconics"] = dict(on=on, radius_x=rec[0].copy(), conic_x=rec[1].copy(), conic_y=rec[2].copy())
+    if poses:
+        on = np.zeros(n, np.int32)
+        rec = np.zeros((n, 6), np.float32)       # dx, dy, dz, ax, ay, az
+        for k, v in poses:
+            if not 0 <= k < n or on[k]:
+                raise ValueError(f"{path}: bad pose line for interface {k}")
+            if k == lens["stop"]:
+                raise ValueError(f"{path}: a pose line on the stop (interface {k})")
+            if not np.all(np.isfinite(v)) or abs(v[3]) > 30 or abs(v[4]) > 30 or abs(v[5]) > 180:
+                raise ValueError(f"{path}: interface {k}: |ax|, |ay| <= 30 and |az| <= 180 degrees, every value finite")
+            on[k] = 1
+            rec[k] = v
+        lens["poses"] = dict(on=on, decentre=rec[:, :3].copy(), tilt_deg=rec[:, 3:].copy())
     if lambda_nm is not None:
         if len(lambda_nm) != ior.shape[0]:
             raise ValueError(f"{path}: lambda_nm lists {len(lambda_nm)} wavelengths for {ior.shape[0]} index columns")
@@ -291,6 +310,7 @@ MAX_ASPH_COEF = 6        # LF_MAX_ASPH_COEF
 CULL_ASPHERIC = 9        # LF_CULL_ASPHERIC
 ASPH_ALIVE, ASPH_MISSED, ASPH_APERTURE, ASPH_TIR = 0, 1, 2, 3   # the fates of lf_asphere_event
 CULL_ANAMORPHIC = 10     # LF_CULL_ANAMORPHIC
+CULL_POSED = 11          # LF_CULL_POSED
 SENSOR_GHOSTS_OFF, SENSOR_GHOSTS_ADD, SENSOR_GHOSTS_ONLY = 0, 1, 2   # the modes of lf_set_sensor_ghosts
 
 
@@ -346,6 +366,75 @@ def biconic_event(curvature_x, curvature_y, conic_x, conic_y, semi_aperture, n_i
         st = fn(*consts, _fp(rays[i], C.c_float), ro, C.byref(sq), C.byref(ct), C.byref(fate))
         if st != 0:
             raise LensFlareError(st, "lf_biconic_event")
+        out[i, :6] = ro[:]
+        out[i, 6], out[i, 7], fates[i] = sq.value, ct.value, fate.value
+    return out, fates
+
+
+def pose_rotation(tilt_deg):
+    """R = Rx(ax) Ry(ay) Rz(az) of lf_set_lens_poses (float64; angles right-handed, in degrees)."""
+    ax, ay, az = np.deg2rad(np.asarray(tilt_deg, np.float64))
+    ca, sa, cb, sb, cg, sg = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+    rx = np.array([[1, 0, 0], [0, ca, -sa], [0, sa, ca]])
+    ry = np.array([[cb, 0, sb], [0, 1, 0], [-sb, 0, cb]])
+    rz = np.array([[cg, -sg, 0], [sg, cg, 0], [0, 0, 1]])
+    return rx @ ry @ rz
+
+
+def pose_group(lens, first, last, pivot_z, decentre, tilt_deg):
+    """The pose records of the rigid group of interfaces first .. last of `lens`, turned by tilt_deg about the point
+    (0, 0, pivot_z) of the axis and then moved by decentre: the same R on every interface and
+    t_k = d + (R - I) (0, 0, z_k - pivot_z), z_k the vertex of interface k measured from interface 0's (the sum of the
+    thicknesses before it).  Returns dict(on, decentre n x 3, tilt_deg n x 3) for set_lens_poses; an interface outside the
+    group keeps on = 0.  (This is how an ELEMENT is tilted: its faces need different records.)"""
+    n = int(lens["n"])
+    if not 0 <= first <= last < n:
+        raise ValueError("pose_group: 0 <= first <= last < n")
+    z = np.concatenate([[0.0], np.cumsum(np.asarray(lens["thickness"], np.float64)[:-1])])
+    R = pose_rotation(tilt_deg)
+    d = np.asarray(decentre, np.float64)
+    on = np.zeros(n, np.int32)
+    t = np.zeros((n, 3), np.float32)
+    a = np.zeros((n, 3), np.float32)
+    for k in range(first, last + 1):
+        on[k] = 1
+        t[k] = d + (R - np.eye(3)) @ np.array([0.0, 0.0, z[k] - pivot_z])
+        a[k] = tilt_deg
+    return dict(on=on, decentre=t, tilt_deg=a)
+
+
+def _pose_event_consts(curvature_x, curvature_y, conic_x, conic_y, asphere, decentre, tilt_deg, semi_aperture, n_in, n_out,
+                       reflect, forward, dzv):
+    kappa, coef = (0.0, ()) if asphere is None else asphere
+    a = np.ascontiguousarray(coef, np.float32).ravel()
+    d = np.ascontiguousarray(decentre, np.float32).ravel()
+    t = np.ascontiguousarray(tilt_deg, np.float32).ravel()
+    if len(d) != 3 or len(t) != 3:
+        raise ValueError("decentre and tilt_deg hold three values")
+    keep = (a, d, t)
+    return keep, (C.c_float(curvature_x), C.c_float(curvature_y), C.c_float(conic_x), C.c_float(conic_y), int(asphere is not None),
+                  C.c_float(kappa), _fp(a, C.c_float) if len(a) else None, len(a), _fp(d, C.c_float), _fp(t, C.c_float),
+                  C.c_float(semi_aperture), C.c_float(n_in), C.c_float(n_out), int(bool(reflect)), int(bool(forward)),
+                  C.c_float(dzv))
+
+
+def pose_event(curvature_x, curvature_y, conic_x, conic_y, asphere, decentre, tilt_deg, semi_aperture, n_in, n_out, reflect,
+               forward, dzv, rays):
+    """One event on a posed interface for each of the n x 6 rays {x, y, z, Kx, Ky, Kz}, host arithmetic (lf_pose_event):
+    biconic_event's arguments, `asphere` = None or (kappa, coef) -- then the surface of revolution of curvature_y -- and the
+    pose (decentre mm, tilt_deg).  (out n x 8 = {ray, sq, ct}, fates n)."""
+    rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+    out = np.zeros((len(rays), 8), np.float32)
+    fates = np.zeros(len(rays), np.int32)
+    fn = load_library().lf_pose_event
+    ro = (C.c_float * 6)()
+    sq, ct, fate = C.c_float(), C.c_float(), C.c_int()
+    keep, consts = _pose_event_consts(curvature_x, curvature_y, conic_x, conic_y, asphere, decentre, tilt_deg, semi_aperture,
+                                      n_in, n_out, reflect, forward, dzv)
+    for i in range(len(rays)):
+        st = fn(*consts, _fp(rays[i], C.c_float), ro, C.byref(sq), C.byref(ct), C.byref(fate))
+        if st != 0:
+            raise LensFlareError(st, "lf_pose_event")
         out[i, :6] = ro[:]
         out[i, 6], out[i, 7], fates[i] = sq.value, ct.value, fate.value
     return out, fates
@@ -1074,6 +1163,9 @@ class LensFlare:
         if "biconics" in lens:
             b = lens["biconics"]
             self.set_lens_biconics(b["on"], b["radius_x"], b["conic_x"], b["conic_y"])
+        if "poses" in lens:
+            p = lens["poses"]
+            self.set_lens_poses(p["on"], p["decentre"], p["tilt_deg"])
         if "sensor_reflectance" in lens:
             self.set_sensor_reflectance(lens["sensor_reflectance"])
 
@@ -1152,6 +1244,40 @@ class LensFlare:
         self._ck(self.lib.lf_get_lens_biconics(self.ctx, n, _fp(on, C.c_int), _fp(rx, C.c_float), _fp(kx, C.c_float),
                                                _fp(ky, C.c_float), C.byref(cnt)))
         return dict(on=on, radius_x=rx, conic_x=kx, conic_y=ky, n_biconic=cnt.value)
+
+    def set_lens_poses(self, on=None, decentre=None, tilt_deg=None):
+        """Pose records on the installed lens: on[k] != 0 marks interface k, decentre[k] = (dx, dy, dz) in mm, tilt_deg[k] =
+        (ax, ay, az) in degrees (None: zeros).  on None clears the records.  (pose_group writes a rigid group's.)"""
+        if on is None:
+            self._ck(self.lib.lf_set_lens_poses(self.ctx, 0, None, None, None))
+            return
+        on = np.ascontiguousarray(on, np.int32).ravel()
+        arr = lambda v: np.zeros((len(on), 3), np.float32) if v is None else np.ascontiguousarray(v, np.float32).reshape(-1, 3)
+        d, t = arr(decentre), arr(tilt_deg)
+        if not (len(d) == len(t) == len(on)):
+            raise ValueError("on holds one value per interface, decentre and tilt_deg three")
+        self._ck(self.lib.lf_set_lens_poses(self.ctx, len(on), _fp(on, C.c_int), _fp(d, C.c_float), _fp(t, C.c_float)))
+
+    def lens_poses(self):
+        """dict(on (n), decentre, tilt_deg (n x 3 each), n_posed) of the installed lens."""
+        n = self.lens_info()["n"]
+        on = np.zeros(n, np.int32)
+        d, t = np.zeros((n, 3), np.float32), np.zeros((n, 3), np.float32)
+        cnt = C.c_int()
+        self._ck(self.lib.lf_get_lens_poses(self.ctx, n, _fp(on, C.c_int), _fp(d, C.c_float), _fp(t, C.c_float), C.byref(cnt)))
+        return dict(on=on, decentre=d, tilt_deg=t, n_posed=cnt.value)
+
+    def pose_events(self, curvature_x, curvature_y, conic_x, conic_y, asphere, decentre, tilt_deg, semi_aperture, n_in, n_out,
+                    reflect, forward, dzv, rays):
+        """pose_event on the device (lf_pose_events): the same (out, fates), bit for bit."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 6)
+        out = np.zeros((len(rays), 8), np.float32)
+        fates = np.zeros(len(rays), np.int32)
+        keep, consts = _pose_event_consts(curvature_x, curvature_y, conic_x, conic_y, asphere, decentre, tilt_deg, semi_aperture,
+                                          n_in, n_out, reflect, forward, dzv)
+        self._ck(self.lib.lf_pose_events(self.ctx, *consts, C.c_size_t(len(rays)), _fp(rays, C.c_float), _fp(out, C.c_float),
+                                         _fp(fates, C.c_int)))
+        return out, fates
 
     def lens_meridian_scales(self):
         """(scale_x, scale_y): the paraxial image scales of the x and the y meridian (lf_get_lens_meridian_scales)."""
@@ -1520,7 +1646,7 @@ class LensFlare:
                     reason=self.cull_reason())
 
     CULL_REASONS = ("applied", "off", "no_stop", "too_many_paths", "too_many_samples", "block_too_large", "table_too_full",
-                    "audit_refuted", "dispersion_not_monotonic", "aspheric", "anamorphic")
+                    "audit_refuted", "dispersion_not_monotonic", "aspheric", "anamorphic", "posed")
 
     def cull_reason(self):
         """why the last trace_ghosts did (not) cull: one of CULL_REASONS (lf_cull_reason)"""

@@ -12,6 +12,7 @@
 #include "lf_march_events.h"
 #include "lf_asphere.h"
 #include "lf_biconic.h"
+#include "lf_pose.h"
 #include "lf_sensor_event.h"
 #include "../host/lf_collada.h"
 
@@ -1018,6 +1019,7 @@ lf_status lf_set_lens(lf_ctx* ctx, int n_surfaces, int stop_index, int n_lambda,
   ctx->coat = LfCoatings{};
   ctx->asph = LfAspheres{};      // (and its aspheres: a new lens is one of spheres)
   ctx->bic = LfBiconics{};       // (and its biconic records)
+  ctx->pose = LfPoses{};         // (and its pose records)
   ctx->sensor.n_refl = 0;        // (and its sensor's reflectance; the sensor ghosts' mode is a setting of the context and stays)
   ctx->lenscam_dirty = true;
   lf_derive_lens(ctx, n_surfaces, stop_index, n_lambda, radius, thickness, ior, semi_aperture,
@@ -1644,6 +1646,9 @@ lf_status lf_trace_ghosts(lf_ctx* ctx, int spp, uint64_t key) {
   const int sensor_mode = ctx->sensor.mode;
   if (sensor_mode != LF_SENSOR_GHOSTS_OFF && ctx->sensor.n_refl == 0)
     return lf_fail(ctx, LF_ERR_STATE, "lf_trace_ghosts: sensor ghosts are on and the sensor has no reflectance (lf_set_sensor_reflectance)");
+  if (sensor_mode != LF_SENSOR_GHOSTS_OFF && ctx->pose.n > 0)
+    return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lf_trace_ghosts: sensor ghosts (lf_set_sensor_ghosts: LF_SENSOR_GHOSTS_ADD / LF_SENSOR_GHOSTS_ONLY) "
+                                            "are not marched through a lens with posed interfaces (lf_set_lens_poses)");
   LF_HIP(ctx, hipSetDevice(ctx->device));
   lf_status st = LF_OK;
   if (sensor_mode != LF_SENSOR_GHOSTS_ONLY) st = lfk_march(ctx, spp, key);
@@ -2704,6 +2709,9 @@ lf_status lf_march_sensor_path_rays(lf_ctx* ctx, int lambda, int i, size_t n, co
     return lf_fail(ctx, LF_ERR_STATE, "aperture mask (LF_APERTURE_STARBURST slot) not set");
   if (ctx->sensor.n_refl == 0)
     return lf_fail(ctx, LF_ERR_STATE, "lf_march_sensor_path_rays: the sensor has no reflectance (lf_set_sensor_reflectance)");
+  if (ctx->pose.n > 0)   // (as lf_trace_ghosts refuses the frame: the sensor paths know no pose record)
+    return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lf_march_sensor_path_rays: sensor paths are not marched through a lens with posed "
+                                            "interfaces (lf_set_lens_poses)");
   if (lambda < 0 || lambda >= ctx->lens.n_lambda || n > 0x7fffffffull / 8)
     return lf_fail(ctx, LF_ERR_INVALID, "lf_march_sensor_path_rays: wavelength index / count out of range");
   if (i < 0 || i >= ctx->lens.n_surf || i == ctx->lens.stop)
@@ -2882,6 +2890,138 @@ lf_status lf_biconic_events(lf_ctx* ctx, float curvature_x, float curvature_y, f
   return LF_OK;
 }
 
+// ---------------------------------------------------------------- posed interfaces --------------
+lf_status lf_set_lens_poses(lf_ctx* ctx, int n_surfaces, const int* on, const float* decentre, const float* tilt_deg) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_set_lens_poses before lf_set_lens");
+  if (!on) {   // every interface centred
+    ctx->pose = LfPoses{};
+    ctx->events_dirty = true;
+    ctx->lenscam_dirty = true;
+    return LF_OK;
+  }
+  if (n_surfaces != ctx->raw_n) return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_poses: n_surfaces differs from the installed lens");
+  LfPoses P;
+  for (int k = 0; k < n_surfaces; k++) {
+    if (!on[k]) continue;
+    const std::string who = "lf_set_lens_poses: interface " + std::to_string(k);
+    float t[3], a[3];
+    for (int m = 0; m < 3; m++) {
+      t[m] = decentre ? decentre[3 * k + m] : 0.0f;
+      a[m] = tilt_deg ? tilt_deg[3 * k + m] : 0.0f;
+      if (!std::isfinite(t[m]) || !std::isfinite(a[m])) return lf_fail(ctx, LF_ERR_INVALID, who + ": a value is not finite");
+    }
+    if (k == ctx->raw_stop) return lf_fail(ctx, LF_ERR_INVALID, who + ": the stop cannot carry a pose record");
+    if (!(std::fabs(a[0]) <= 30.0f) || !(std::fabs(a[1]) <= 30.0f))
+      return lf_fail(ctx, LF_ERR_INVALID, who + ": |ax| and |ay| are at most 30 degrees");
+    if (!(std::fabs(a[2]) <= 180.0f)) return lf_fail(ctx, LF_ERR_INVALID, who + ": az lies in [-180, 180] degrees");
+    P.on[k] = 1;
+    for (int m = 0; m < 3; m++) { P.t[3 * k + m] = t[m]; P.a[3 * k + m] = a[m]; }
+    P.n++;
+  }
+  ctx->pose = P;
+  ctx->events_dirty = true;
+  ctx->lenscam_dirty = true;
+  return LF_OK;
+}
+
+lf_status lf_get_lens_poses(lf_ctx* ctx, int n_surfaces, int* on, float* decentre, float* tilt_deg, int* n_posed) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (!ctx->lens_valid) return lf_fail(ctx, LF_ERR_STATE, "lf_get_lens_poses before lf_set_lens");
+  if (n_surfaces != ctx->raw_n) return lf_fail(ctx, LF_ERR_INVALID, "lf_get_lens_poses: n_surfaces differs from the installed lens");
+  const LfPoses& P = ctx->pose;
+  for (int k = 0; k < n_surfaces; k++) {
+    if (on) on[k] = P.on[k];
+    for (int m = 0; m < 3; m++) {
+      if (decentre) decentre[3 * k + m] = P.t[3 * k + m];
+      if (tilt_deg) tilt_deg[3 * k + m] = P.a[3 * k + m];
+    }
+  }
+  if (n_posed) *n_posed = P.n;
+  return LF_OK;
+}
+
+// the constants of one posed event as the host twin and the kernel take them: lf_biconic_event's sixteen (with the whole
+// aspheric record in 8 .. 14 where aspheric), and the pose {R row-major, t, 0 ..}
+static bool pose_event_consts(float cx, float cy, float kx, float ky, int aspheric, float kappa, const float* coef, int n_coef,
+                              const float decentre[3], const float tilt_deg[3], float semi_aperture, float n_in, float n_out,
+                              int forward, float dzv, float k[16], float pose[16]) {
+  if (!decentre || !tilt_deg || n_coef < 0 || n_coef > LF_MAX_ASPH_COEF || (n_coef > 0 && !coef)) return false;
+  if (!bic_event_consts(cx, cy, kx, ky, semi_aperture, n_in, n_out, forward, dzv, k)) return false;
+  for (int m = 0; m < 3; m++)
+    if (!std::isfinite(decentre[m]) || !std::isfinite(tilt_deg[m])) return false;
+  if (aspheric) {
+    if (!std::isfinite(kappa)) return false;
+    k[8] = kappa; k[9] = k[10] = 0.0f;
+    for (int m = 0; m < n_coef; m++) {
+      if (!std::isfinite(coef[m])) return false;
+      k[9 + m] = coef[m];
+    }
+  }
+  const lfm::LfPoseRec p = lfm::lf_pose_make(decentre[0], decentre[1], decentre[2], tilt_deg[0], tilt_deg[1], tilt_deg[2]);
+  for (int m = 0; m < 16; m++) pose[m] = 0.0f;
+  for (int m = 0; m < 9; m++) pose[m] = p.r[m];
+  for (int m = 0; m < 3; m++) pose[9 + m] = p.t[m];
+  return true;
+}
+
+lf_status lf_pose_event(float curvature_x, float curvature_y, float conic_x, float conic_y, int aspheric, float kappa,
+                        const float* coef, int n_coef, const float decentre[3], const float tilt_deg[3], float semi_aperture,
+                        float n_in, float n_out, int reflect, int forward, float dzv, const float ray_in[6], float ray_out[6],
+                        float* sq, float* ct, int* fate) {
+  float k[16], pose[16];
+  if (!ray_in || !ray_out || !fate ||
+      !pose_event_consts(curvature_x, curvature_y, conic_x, conic_y, aspheric, kappa, coef, n_coef, decentre, tilt_deg, semi_aperture,
+                         n_in, n_out, forward, dzv, k, pose))
+    return LF_ERR_INVALID;
+  lfm::LfAsphRec ka;
+  ka.kappa = k[8];
+  for (int m = 0; m < 6; m++) ka.a[m] = k[9 + m];
+  ka.spare = 0.0f;
+  const lfm::LfBicRec kb{k[8], k[9], k[10], {}};
+  lfm::LfPoseRec p{};
+  for (int m = 0; m < 9; m++) p.r[m] = pose[m];
+  for (int m = 0; m < 3; m++) p.t[m] = pose[9 + m];
+  float px = ray_in[0], py = ray_in[1], hz = ray_in[2], dx = ray_in[3], dy = ray_in[4], dz = ray_in[5], r2;
+  const lfm::AsphHit h = lfm::lf_pose_event(px, py, hz, r2, dx, dy, dz, k[4], k[0], aspheric != 0, ka, kb, p, k[1], k[2], reflect != 0, k[3]);
+  ray_out[0] = px; ray_out[1] = py; ray_out[2] = hz; ray_out[3] = dx; ray_out[4] = dy; ray_out[5] = dz;
+  if (sq) *sq = h.sq;
+  if (ct) *ct = h.ct;
+  *fate = h.fate;
+  return LF_OK;
+}
+
+lf_status lf_pose_events(lf_ctx* ctx, float curvature_x, float curvature_y, float conic_x, float conic_y, int aspheric, float kappa,
+                         const float* coef, int n_coef, const float decentre[3], const float tilt_deg[3], float semi_aperture,
+                         float n_in, float n_out, int reflect, int forward, float dzv, size_t n, const float* rays, float* out,
+                         int* fates) {
+  if (!ctx || (n > 0 && (!rays || !out || !fates))) return LF_ERR_INVALID;
+  float k[16], pose[16];
+  if (n > 0x7fffffffull / 8 ||
+      !pose_event_consts(curvature_x, curvature_y, conic_x, conic_y, aspheric, kappa, coef, n_coef, decentre, tilt_deg, semi_aperture,
+                         n_in, n_out, forward, dzv, k, pose))
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_pose_events: constants not finite / out of range, or too many rays for one call");
+  if (n == 0) return LF_OK;
+  LF_HIP(ctx, hipSetDevice(ctx->device));
+  float *d_rays = nullptr, *d_out = nullptr;
+  int* d_fates = nullptr;
+  hipError_t e = hipMalloc((void**)&d_rays, n * 6 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_out, n * 8 * sizeof(float));
+  if (e == hipSuccess) e = hipMalloc((void**)&d_fates, n * sizeof(int));
+  if (e == hipSuccess) e = hipMemcpy(d_rays, rays, n * 6 * sizeof(float), hipMemcpyHostToDevice);
+  lf_status st = LF_OK;
+  if (e == hipSuccess) st = lfk_pose_events(ctx, k, pose, reflect, aspheric, n, d_rays, d_out, d_fates);
+  if (e == hipSuccess && st == LF_OK) e = hipStreamSynchronize(ctx->stream);
+  if (e == hipSuccess && st == LF_OK) e = hipMemcpy(out, d_out, n * 8 * sizeof(float), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && st == LF_OK) e = hipMemcpy(fates, d_fates, n * sizeof(int), hipMemcpyDeviceToHost);
+  if (d_rays) (void)hipFree(d_rays);
+  if (d_out) (void)hipFree(d_out);
+  if (d_fates) (void)hipFree(d_fates);
+  if (st != LF_OK) return st;
+  LF_HIP(ctx, e);
+  return LF_OK;
+}
+
 // ---------------------------------------------------------------- lens file ---------------------
 lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
   if (!ctx || !path) return LF_ERR_INVALID;
@@ -2894,7 +3034,8 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
   // lf_set_lens_coating_stacks; needs lambda_nm; not on an interface with a `coating` line)
   // `asphere k kappa [A4 [A6 ...]]` (interface k's conic constant and even coefficients: lf_set_lens_aspheres)
   // `biconic k Rx [kx [ky]]` (interface k's x-meridian radius, 0 = flat in x, and conic constants: lf_set_lens_biconics)
-  std::vector<std::vector<double>> rows, coats, layers, asphs, bics, sens;
+  // `pose k dx dy dz ax ay az` (interface k's decentre in mm and tilt in degrees: lf_set_lens_poses)
+  std::vector<std::vector<double>> rows, coats, layers, asphs, bics, sens, poses;
   std::vector<double> lambdas;
   bool lambda_line = false, lambda_bad = false;
   double sensor_w = 36.0;
@@ -2904,7 +3045,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (char* h = std::strchr(line, '#')) *h = 0;
     std::vector<double> v;
     char* p = line;
-    int keyword = 0;   // 1 sensor_width_mm, 2 lambda_nm, 3 coating, 4 layer, 5 asphere, 6 biconic, 7 sensor_reflectance
+    int keyword = 0;   // 1 sensor_width_mm, 2 lambda_nm, 3 coating, 4 layer, 5 asphere, 6 biconic, 7 sensor_reflectance, 8 pose
     while (*p) {
       while (*p == ' ' || *p == '\t' || *p == '\r' || *p == '\n') p++;
       if (!*p) break;
@@ -2915,6 +3056,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
       if (v.empty() && !keyword && std::strncmp(p, "layer", 5) == 0) { keyword = 4; p += 5; continue; }
       if (v.empty() && !keyword && std::strncmp(p, "asphere", 7) == 0) { keyword = 5; p += 7; continue; }
       if (v.empty() && !keyword && std::strncmp(p, "biconic", 7) == 0) { keyword = 6; p += 7; continue; }
+      if (v.empty() && !keyword && std::strncmp(p, "pose", 4) == 0) { keyword = 8; p += 4; continue; }
       char* e = nullptr;
       const double d = std::strtod(p, &e);
       if (e == p) {
@@ -2932,6 +3074,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (keyword == 5) { asphs.push_back(v); continue; }
     if (keyword == 6) { bics.push_back(v); continue; }
     if (keyword == 7) { sens.push_back(v); continue; }
+    if (keyword == 8) { poses.push_back(v); continue; }
     if (keyword == 1) { if (v.size() != 1) { bad = true; break; } sensor_w = v[0]; continue; }
     if (!v.empty()) rows.push_back(v);
   }
@@ -3014,12 +3157,29 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (c.size() > 2) bkx[k] = (float)c[2];
     if (c.size() > 3) bky[k] = (float)c[3];
   }
+  int pon[LF_MAX_SURFACES] = {};
+  float pt[3 * LF_MAX_SURFACES] = {}, pa[3 * LF_MAX_SURFACES] = {};
+  for (const auto& c : poses) {
+    const int k = c.size() >= 1 ? (int)c[0] : -1;
+    if (k < 0 || k >= n || (double)k != c[0] || (int)c.size() != 7 || pon[k])
+      return lf_fail(ctx, LF_ERR_INVALID, "lf_load_lens_file: a pose line is `pose k dx dy dz ax ay az` (once per interface)");
+    pon[k] = 1;
+    for (int m = 0; m < 3; m++) { pt[3 * k + m] = (float)c[1 + m]; pa[3 * k + m] = (float)c[4 + m]; }
+  }
   lf_status st = lf_set_lens(ctx, n, stop, nl, radius, thick, ior, semi, (float)sensor_w);
+  if (st == LF_OK && !poses.empty()) {
+    st = lf_set_lens_poses(ctx, n, pon, pt, pa);
+    if (st != LF_OK) {   // the lens stays, centred
+      const std::string why = ctx->err;
+      return lf_fail(ctx, st, "lf_load_lens_file: " + why);
+    }
+  }
   if (st == LF_OK && !sens.empty()) st = lf_set_sensor_reflectance(ctx, nl, srefl);   // (the mode stays what it is)
   if (st == LF_OK && !bics.empty()) {   // (before the aspheres: an interface with both lines is refused by their setter)
     st = lf_set_lens_biconics(ctx, n, bon, brx, bkx, bky);
     if (st != LF_OK) {   // the lens stays, one of spheres
       const std::string why = ctx->err;
+      (void)lf_set_lens_poses(ctx, 0, nullptr, nullptr, nullptr);
       return lf_fail(ctx, st, "lf_load_lens_file: " + why);
     }
   }
@@ -3028,6 +3188,7 @@ lf_status lf_load_lens_file(lf_ctx* ctx, const char* path) {
     if (st != LF_OK) {   // the lens stays, one of spheres
       const std::string why = ctx->err;
       (void)lf_set_lens_biconics(ctx, 0, nullptr, nullptr, nullptr, nullptr);
+      (void)lf_set_lens_poses(ctx, 0, nullptr, nullptr, nullptr);
       return lf_fail(ctx, st, "lf_load_lens_file: " + why);
     }
   }

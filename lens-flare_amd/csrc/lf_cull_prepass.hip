@@ -954,6 +954,7 @@ static int cull_m(const lf_ctx* ctx, int G) {
 // Does the cull apply to this launch, and if not, why (lf_get_cull_reason)
 int lf_cull_reason_of(const lf_ctx* ctx, int G) {
   // (the pre-pass's bounds are empirical rules found on spherical designs: DESIGN.md section 5)
+  if (lf_march_posed(ctx)) return LF_CULL_POSED;   // (nor on a centred lens alone)
   if (lf_march_biconic(ctx)) return LF_CULL_ANAMORPHIC;   // (nor on surfaces of revolution alone)
   if (lf_march_aspheric(ctx)) return LF_CULL_ASPHERIC;
   if (ctx->march_cull == 0) return LF_CULL_OFF;

@@ -208,6 +208,11 @@ enum { LF_EV_ASPH = 8 };
 // ... and, likewise only for a lens with a biconic record (lf_set_lens_biconics): the row's interface is a biconic -- the BIC
 // instantiations of k_march_asph take biconic_event there (lf_biconic.h); the row's slot of the aspheric table holds {1/Rx, kx, ky}.
 enum { LF_EV_BICONIC = 16 };
+// ... and, only for a lens with a pose record (lf_set_lens_poses): the row's interface is posed -- the POSE instantiations of
+// k_march_asph take pose_event there (lf_pose.h), on the row's record of the pose table.  The bit comes with LF_EV_ASPH (the
+// interface has an aspheric record) or with LF_EV_BICONIC (a biconic record, or a sphere or plane written as one).  (32 is
+// lf_path_table.h's LF_EV_SENSOR.)
+enum { LF_EV_POSE = 64 };
 // the conic constants and even coefficients of the prescription's interfaces (host; lf_set_lens_aspheres): coef[m * n_surfaces + k]
 // multiplies r^(4 + 2 m) on interface k.  n = interfaces whose record is not all zero (0: a lens of spheres).
 struct LfAspheres {
@@ -224,6 +229,14 @@ struct LfBiconics {
   float rx[LF_MAX_SURFACES] = {};
   float kx[LF_MAX_SURFACES] = {};
   float ky[LF_MAX_SURFACES] = {};
+};
+// the pose records of the prescription's interfaces (host; lf_set_lens_poses): on[k] != 0: interface k is decentred by
+// t[3 k ..] mm and tilted by a[3 k ..] degrees (lf_pose.h).  A record of zeros is a record.  n = the records (0: none).
+struct LfPoses {
+  int n = 0;
+  int on[LF_MAX_SURFACES] = {};
+  float t[3 * LF_MAX_SURFACES] = {};
+  float a[3 * LF_MAX_SURFACES] = {};
 };
 // A program row as the device walks it: the interface once, the index ratios of the up to three
 // wavelengths that march it together (lf_march.hip, k_march<K>); one 64-byte scalar load.
@@ -602,6 +615,7 @@ struct lf_ctx {
   LfCoatings coat;                                        // lf_set_lens_coatings / lf_set_lens_coating_stacks (cleared by lf_set_lens)
   LfAspheres asph;                                        // lf_set_lens_aspheres (cleared by lf_set_lens, kept by lf_focus_lens)
   LfBiconics bic;                                         // lf_set_lens_biconics (cleared by lf_set_lens, kept by lf_focus_lens)
+  LfPoses pose;                                           // lf_set_lens_poses (likewise)
   bool asph_force = false;                                // lf_test_knob("asph_force"): k_march_asph on a lens of spheres, zero records
   int mask_filter = LF_MASK_NEAREST;                      // lf_set_mask_filter (a setting of the context: nothing clears it)
   std::vector<float> mask_host;                           // the STARBURST slot's texels (occupancy / open radius follow the filter)
@@ -860,7 +874,11 @@ lf_status lfk_cull_prepare(lf_ctx* ctx, int spp);
 // the batched single event; one explicit ray per lane along the sequence of pair (i, j)
 // (a lens with a biconic record, lf_set_lens_biconics, takes the same route through the kernel's BIC instantiations)
 inline bool lf_march_biconic(const lf_ctx* ctx) { return ctx->bic.n > 0; }
-inline bool lf_march_aspheric(const lf_ctx* ctx) { return ctx->asph.n > 0 || ctx->asph_force || lf_march_biconic(ctx); }
+// (and so does a lens with a pose record, lf_set_lens_poses, through the POSE instantiations)
+inline bool lf_march_posed(const lf_ctx* ctx) { return ctx->pose.n > 0; }
+inline bool lf_march_aspheric(const lf_ctx* ctx) {
+  return ctx->asph.n > 0 || ctx->asph_force || lf_march_biconic(ctx) || lf_march_posed(ctx);
+}
 // is there a record on glass interface k, and of which kind: 0, LF_EV_BICONIC or LF_EV_ASPH.  ONE predicate for the rows of
 // lf_march_path_rays (build_path_table) and of the lens camera's primary table (lf_upload_primary_table), so that
 // lf_generate_lens_rays and the scene kernel agree on which rows are recorded.
@@ -878,6 +896,8 @@ lf_status lfk_asphere_events(lf_ctx* ctx, const float* consts16, int reflect, in
                              float* d_out, int* d_fates);
 lf_status lfk_biconic_events(lf_ctx* ctx, const float* consts16, int reflect, size_t n, const float* d_rays, float* d_out,
                              int* d_fates);
+lf_status lfk_pose_events(lf_ctx* ctx, const float* consts16, const float* pose16, int reflect, int asph, size_t n,
+                          const float* d_rays, float* d_out, int* d_fates);
 lf_status lfk_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, int n, const float* d_xy, const float* d_uv, float* d_out);
 // lf_march_sensor.hip: the sensor ghosts -- the frame's launch behind (add) or instead of the ordinary march, one explicit ray
 // per lane along the sensor path of interface i, and what lf_destroy frees

@@ -181,6 +181,10 @@ lf_status lf_lenscam_prepare(lf_ctx* ctx) {
   // (the default setting, LF_LENSCAM_SURFACES_SPHERICAL, refuses a lens with records as it always has; under
   // LF_LENSCAM_SURFACES_ALL the scene kernel marches them: lf_set_lens_camera_surfaces)
   const bool spherical_only = ctx->lenscam_surfaces == LF_LENSCAM_SURFACES_SPHERICAL;
+  if (ctx->pose.n > 0)
+    return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lens camera: the lens has posed interfaces (lf_set_lens_poses) -- the scene term's primary "
+                                            "path marches none under either setting of lf_set_lens_camera_surfaces; "
+                                            "lf_generate_lens_rays marches them");
   if (spherical_only && ctx->asph.n > 0)
     return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lens camera: the lens has aspheric interfaces (lf_set_lens_aspheres) -- the scene term's primary "
                                             "path knows spherical interfaces only; lf_generate_lens_rays marches them");

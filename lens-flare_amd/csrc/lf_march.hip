@@ -46,6 +46,7 @@
 #include "lf_march_events.h"
 #include "lf_march_common.h"
 #include "lf_asphere.h"
+#include "lf_pose.h"
 
 namespace {
 
@@ -1190,11 +1191,29 @@ static void pack_program(lf_ctx* ctx, const std::vector<LfEventRow>& rows, const
   const size_t asph_off = (prog_bytes + 63) & ~(size_t)63;
   ctx->prog_asph_off = aspheric ? asph_off : 0;
   if (aspheric) prog_bytes = asph_off + (size_t)n_recs * sizeof(lfm::LfAsphRec);
+  // ... and, only for a lens with a pose record (lf_set_lens_poses), behind the aspheric records: one LfPoseRec per program
+  // record at pose_off + 64 * record (lf_pose_table_offset: the kernel finds it from the aspheric table and prog_recs).  A
+  // posed interface without an aspheric record takes the biconic route: its slot of the aspheric table holds its biconic
+  // record, or {1/R, 0, 0} (a sphere; a plane: zeros).
+  const LfPoses& Po = ctx->pose;
+  auto pose_row = [&](int k) { return Po.n > 0 && Po.on[surf_of(k)] != 0 && !(row_at(0, first_row[(size_t)k]).flags & LF_EV_STOP); };
+  const size_t pose_off = asph_off + lfm::lf_pose_table_offset(n_recs);
+  if (Po.n > 0) prog_bytes = pose_off + (size_t)n_recs * sizeof(lfm::LfPoseRec);
   out.assign(prog_bytes, 0);
+  if (Po.n > 0)
+    for (int k = 0; k < n_recs; k++) {
+      const int surf = surf_of(k);
+      const lfm::LfPoseRec rec = pose_row(k) ? lfm::lf_pose_make(Po.t[3 * surf], Po.t[3 * surf + 1], Po.t[3 * surf + 2], Po.a[3 * surf],
+                                                                 Po.a[3 * surf + 1], Po.a[3 * surf + 2])
+                                             : lfm::lf_pose_make(0, 0, 0, 0, 0, 0);
+      std::memcpy(out.data() + pose_off + (size_t)k * sizeof(rec), &rec, sizeof(rec));
+    }
   if (aspheric)
     for (int k = 0; k < n_recs; k++) {
       lfm::LfAsphRec rec{};
-      if (bic_row(k)) {
+      if (pose_row(k) && !bic_row(k) && !(A.n > 0 && asph_row(k))) {
+        rec.kappa = row_at(0, first_row[(size_t)k]).curv;
+      } else if (bic_row(k)) {
         const int surf = surf_of(k);
         rec.kappa = B.rx[surf] == 0.0f ? 0.0f : 1.0f / B.rx[surf];
         rec.a[0] = B.kx[surf];
@@ -1220,6 +1239,8 @@ static void pack_program(lf_ctx* ctx, const std::vector<LfEventRow>& rows, const
       seq[e] = id * (int)sizeof(LfProgRow) | ((r.flags & (LF_EV_REFLECT | LF_EV_STOP | LF_EV_FLAT)) << 16);
       if (aspheric && bic_row(id)) seq[e] |= LF_EV_BICONIC << 16;
       else if (aspheric && asph_row(id)) seq[e] |= LF_EV_ASPH << 16;
+      if (pose_row(id))   // (a posed row says which event runs in the surface's frame; asph_force's bit does not apply to it)
+        seq[e] = (seq[e] & ~((LF_EV_ASPH | LF_EV_BICONIC) << 16)) | (LF_EV_POSE | (A.n > 0 && !bic_row(id) && asph_row(id) ? LF_EV_ASPH : LF_EV_BICONIC)) << 16;
     }
   }
   LfProgHdr* hdrs = reinterpret_cast<LfProgHdr*>(out.data());

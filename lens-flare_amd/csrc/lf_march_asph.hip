@@ -9,7 +9,10 @@
 //   k_march_asph<VAR, true> the same kernel for a lens with a BICONIC record (lf_set_lens_biconics; lf_biconic.h): one more
 //                          wave-uniform branch, on LF_EV_BICONIC, to biconic_event.  BIC = false is the code it was.
 //   k_asphere_events       lf_asphere_events: one event for n rays, the device twin of lf_asphere_event
+//   k_march_asph<VAR, true, true> the same kernel for a lens with a POSE record (lf_set_lens_poses; lf_pose.h): one more
+//                          wave-uniform branch, on LF_EV_POSE, to pose_event.  POSE = false is the code it was.
 //   k_biconic_events       lf_biconic_events: the device twin of lf_biconic_event
+//   k_pose_events          lf_pose_events: the device twin of lf_pose_event
 //   k_march_path_rays      lf_march_path_rays: one explicit ray per lane along the sequence of pair (i, j), with its weight
 // The sample starts are sample_start's (lf_march_events.h): the path tree's rays for the same inputs, bit for bit.
 #include <hip/hip_runtime.h>
@@ -24,6 +27,7 @@
 #include "lf_march_common.h"
 #include "lf_asphere.h"
 #include "lf_biconic.h"
+#include "lf_pose.h"
 #include "lf_path_table.h"
 
 using namespace lfm;
@@ -44,6 +48,22 @@ __device__ __forceinline__ LfAsphRec load_asph(const LfAsphRec* __restrict__ bas
   return r;
 }
 
+// a record of the pose table: TWO 32-byte scalar loads (the offset is wave-uniform)
+__device__ __forceinline__ LfPoseRec load_pose(const LfPoseRec* __restrict__ base, unsigned off) {
+  typedef const char __attribute__((address_space(4))) * cptr;
+  const lf_i8 v = *(const lf_i8 __attribute__((address_space(4)))*)((cptr)(base) + off);
+  const lf_i8 w = *(const lf_i8 __attribute__((address_space(4)))*)((cptr)(base) + off + 32u);
+  LfPoseRec r;
+#pragma unroll
+  for (int m = 0; m < 8; m++) r.r[m] = __int_as_float(v[m]);
+  r.r[8] = __int_as_float(w[0]);
+#pragma unroll
+  for (int m = 0; m < 3; m++) r.t[m] = __int_as_float(w[1 + m]);
+#pragma unroll
+  for (int m = 0; m < 4; m++) r.spare[m] = 0.0f;
+  return r;
+}
+
 struct AsphTally {
   unsigned long long n_rays = 0, events = 0, n_clip = 0, n_vign = 0, n_tir = 0, n_scene = 0, n_rm_lane = 0, n_rm_rows = 0;
   unsigned n_light = 0;   // per lane
@@ -51,11 +71,12 @@ struct AsphTally {
 
 // One row of a path for wavelength slot j of its group, W as surface_event's: the stop, an aspheric row, or the spherical
 // event.  *stop: the row was the stop (its dead lanes count as clipped).
-template <bool W, int VAR, bool BIC = false>
+template <bool W, int VAR, bool BIC = false, bool POSE = false>
 __device__ __forceinline__ lanemask asph_row(Ray& r, unsigned cur, int j, const LfProgRow* __restrict__ recs,
                                              const LfWeightRow* __restrict__ wrecs, const LfWeightRow* __restrict__ wrec_table,
                                              const LfAsphRec* __restrict__ asph_table, const float* __restrict__ mask,
-                                             float inv_stop_h, int mw, int mh, lanemask& geom_ok, bool& stop) {
+                                             float inv_stop_h, int mw, int mh, lanemask& geom_ok, bool& stop,
+                                             const LfPoseRec* __restrict__ pose_table = nullptr) {
   const unsigned off = cur & 0xffffu, kind = cur >> 16;
   const LfProgRow wr = load_prec(recs, off);
   stop = (kind & LF_EV_STOP) != 0u;
@@ -74,6 +95,12 @@ __device__ __forceinline__ lanemask asph_row(Ray& r, unsigned cur, int j, const 
     if (VAR & kVarCoat) coat = load_wrec_dword(wrecs, off + (unsigned)offsetof(LfWeightRow, coat));
   }
   const float delta = j == 0 ? wr.delta[0] : j == 1 ? wr.delta[1] : wr.delta[2];
+  if (POSE && (kind & LF_EV_POSE)) {   // wave-uniform: a pose record at the program record's offset of the table behind the aspheric one
+    const LfAsphRec rec = load_asph(asph_table, off >> 1);
+    const LfPoseRec pose = load_pose(pose_table, off);
+    return pose_event<W>(r, wr.dzv, wr.curv, (kind & LF_EV_ASPH) != 0u, rec, pose, delta, wr.h2, (kind & LF_EV_REFLECT) != 0, wr.sgn,
+                         geom_ok, fs, fo, fi, CoatSel<VAR>{wrec_table, coat, j});
+  }
   if (BIC && (kind & LF_EV_BICONIC)) {   // wave-uniform: a biconic record in the aspheric record's slot
     const LfAsphRec rec = load_asph(asph_table, off >> 1);
     return biconic_event<W>(r, wr.dzv, wr.curv, LfBicRec{rec.kappa, rec.a[0], rec.a[1], {}}, delta, wr.h2,
@@ -92,7 +119,7 @@ __device__ __forceinline__ lanemask asph_row(Ray& r, unsigned cur, int j, const 
 
 // path q of one sensor sample per lane, every wavelength on its own: geometry, tallies, the lights' pre-test, the weighted
 // march of the lit lanes, the lit epilogue into the tile's LDS sums
-template <int VAR, bool BIC = false>
+template <int VAR, bool BIC = false, bool POSE = false>
 __device__ __forceinline__ void march_asph_path(const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs,
                                                 const int* __restrict__ seq_table, const LfProgRow* __restrict__ rec_table,
                                                 const LfWeightRow* __restrict__ wrec_table,
@@ -101,6 +128,8 @@ __device__ __forceinline__ void march_asph_path(const LfLensDev* __restrict__ le
                                                 unsigned long long* __restrict__ s_acc, const float* __restrict__ s_chan,
                                                 AsphTally& T) {
   const int n_lambda = lens->n_lambda, prog_recs = pairs->prog_recs;
+  // (the pose table lies behind the aspheric one: lf_pose_table_offset)
+  const LfPoseRec* const pose_table = POSE ? (const LfPoseRec*)((const char*)asph_table + lf_pose_table_offset(prog_recs)) : nullptr;
   const int n_ev = pairs->ev_cnt[q];
   typedef const int __attribute__((address_space(4))) * sptr;
   const sptr seq = (sptr)(seq_table + pairs->ev_off[q]);
@@ -118,8 +147,8 @@ __device__ __forceinline__ void march_asph_path(const LfLensDev* __restrict__ le
     for (int e = 0; e < n_ev && nlive != 0u; e++) {
       lanemask gv;
       bool stop;
-      const lanemask ok = asph_row<false, VAR, BIC>(r[0], (unsigned)seq[e], j, recs, wrecs, wrec_table, asph_table, mask, a.inv_stop_h,
-                                               a.mw, a.mh, gv, stop);
+      const lanemask ok = asph_row<false, VAR, BIC, POSE>(r[0], (unsigned)seq[e], j, recs, wrecs, wrec_table, asph_table, mask,
+                                                          a.inv_stop_h, a.mw, a.mh, gv, stop, pose_table);
       const lanemask died = alive[0] & ~ok;
       if (died != 0ull) {
         if (stop) T.n_clip += (unsigned)__popcll(died);
@@ -144,14 +173,14 @@ __device__ __forceinline__ void march_asph_path(const LfLensDev* __restrict__ le
     for (int e = 0; e < n_ev; e++) {
       lanemask gv;
       bool stop;
-      (void)asph_row<true, VAR, BIC>(rw, (unsigned)seq[e], j, recs, wrecs, wrec_table, asph_table, mask, a.inv_stop_h, a.mw, a.mh, gv,
-                                stop);
+      (void)asph_row<true, VAR, BIC, POSE>(rw, (unsigned)seq[e], j, recs, wrecs, wrec_table, asph_table, mask, a.inv_stop_h, a.mw, a.mh,
+                                           gv, stop, pose_table);
     }
     lights_epilogue<VAR>(lens, s_chan, rw, ((lit[0] >> lane) & 1ull) != 0ull, l, &s_acc[lane * 3], T.n_light);
   }
 }
 
-template <int VAR, bool BIC = false>
+template <int VAR, bool BIC = false, bool POSE = false>
 __global__ __launch_bounds__(64 * kAsphWgWaves) void k_march_asph(
     const LfLensDev* __restrict__ lens, const LfPairsDev* __restrict__ pairs, const int* __restrict__ seq_table,
     const LfProgRow* __restrict__ rec_table, const LfWeightRow* __restrict__ wrec_table,
@@ -201,7 +230,7 @@ __global__ __launch_bounds__(64 * kAsphWgWaves) void k_march_asph(
       const int s = sg + k * sgroups;       // wave-uniform
       const StartRay s0 = sample_start(spec, x, y, s);
       for (int q = 0; q < n_paths; q++)
-        march_asph_path<VAR, BIC>(lens, pairs, seq_table, rec_table, wrec_table, asph_table, mask, a, K, q, active_mask, s0, lane, s_acc,
+        march_asph_path<VAR, BIC, POSE>(lens, pairs, seq_table, rec_table, wrec_table, asph_table, mask, a, K, q, active_mask, s0, lane, s_acc,
                              s_chan, T);
     }
 
@@ -266,8 +295,38 @@ __global__ __launch_bounds__(256) void k_biconic_events(AsphEventArgs c, int ref
   fates[i] = h.fate;
 }
 
+// ---- lf_pose_events: the host's lf_pose_event, n times; the sixteen constants of lf_asphere_events (asph) or of
+// lf_biconic_events, and the pose {R row-major, t, 0 ...} ------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_pose_events(AsphEventArgs c, AsphEventArgs pose, int reflect, int asph, int n,
+                                                     const float* __restrict__ rays, float* __restrict__ out,
+                                                     int* __restrict__ fates) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  LfAsphRec ka;
+  ka.kappa = c.k[8];
+#pragma unroll
+  for (int m = 0; m < 6; m++) ka.a[m] = c.k[9 + m];
+  ka.spare = 0.0f;
+  const LfBicRec kb{c.k[8], c.k[9], c.k[10], {}};
+  LfPoseRec p;
+#pragma unroll
+  for (int m = 0; m < 9; m++) p.r[m] = pose.k[m];
+#pragma unroll
+  for (int m = 0; m < 3; m++) p.t[m] = pose.k[9 + m];
+#pragma unroll
+  for (int m = 0; m < 4; m++) p.spare[m] = 0.0f;
+  const float* ri = rays + 6 * (size_t)i;
+  float px = ri[0], py = ri[1], hz = ri[2], dx = ri[3], dy = ri[4], dz = ri[5], r2;
+  const AsphHit h = lf_pose_event(px, py, hz, r2, dx, dy, dz, c.k[4], c.k[0], asph != 0, ka, kb, p, c.k[1], c.k[2], reflect != 0, c.k[3]);
+  float* o = out + 8 * (size_t)i;
+  o[0] = px; o[1] = py; o[2] = hz; o[3] = dx; o[4] = dy; o[5] = dz; o[6] = h.sq; o[7] = h.ct;
+  fates[i] = h.fate;
+}
+
 // ---- lf_march_path_rays: the sequence of pair (i, j) for ONE wavelength, one row per event (lf_path_table.h; host: build_path_table) ----
-template <bool FILT, bool COAT, bool BIC = false>
+// (POSE: the rows' pose records lie behind the table and its stack records, at kPathPoseOffset, one per row)
+constexpr size_t kPathPoseOffset = (sizeof(LfPathDev) + kPathStackBytes + 63) & ~(size_t)63;
+template <bool FILT, bool COAT, bool BIC = false, bool POSE = false>
 __global__ __launch_bounds__(256) void k_march_path_rays(const LfLensDev* __restrict__ lens, const LfPathDev* __restrict__ P,
                                                          const float* __restrict__ mask, int mw, int mh, int n,
                                                          const float* __restrict__ sensor_xy, const float* __restrict__ pupil_uv,
@@ -288,6 +347,11 @@ __global__ __launch_bounds__(256) void k_march_path_rays(const LfLensDev* __rest
     const bool reflect = (w.kind & LF_EV_REFLECT) != 0;
     if (w.kind & LF_EV_STOP) {
       ok = stop_event<true, FILT>(r, w.dzv, w.h2, P->inv_stop_h, mask, mw, mh);
+    } else if (POSE && (w.kind & LF_EV_POSE)) {   // wave-uniform
+      const LfPoseRec pose = load_pose((const LfPoseRec*)((const char*)P + kPathPoseOffset), (unsigned)e * (unsigned)sizeof(LfPoseRec));
+      const bool asph = (w.kind & LF_EV_ASPH) != 0;
+      if (COAT) ok = pose_event<true>(r, w.dzv, w.curv, asph, w.asph, pose, w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo, w.fi, PathCoat{&w});
+      else ok = pose_event<true>(r, w.dzv, w.curv, asph, w.asph, pose, w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo, w.fi);
     } else if (BIC && (w.kind & LF_EV_BICONIC)) {
       const LfBicRec rec{w.asph.kappa, w.asph.a[0], w.asph.a[1], {}};
       if (COAT) ok = biconic_event<true>(r, w.dzv, w.curv, rec, w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo, w.fi, PathCoat{&w});
@@ -317,7 +381,8 @@ __global__ __launch_bounds__(256) void k_march_path_rays(const LfLensDev* __rest
 // host: the rows of pair (i, j) at wavelength l -- the order of lf_build_march_tables, the constants of pack_program
 lf_status build_path_table(lf_ctx* ctx, int l, int i, int j, std::vector<unsigned char>& buf) {
   const LfLensDev& L = ctx->lens;
-  buf.assign(sizeof(LfPathDev) + kPathStackBytes, 0);
+  const LfPoses& Po = ctx->pose;
+  buf.assign(Po.n > 0 ? kPathPoseOffset + (size_t)kPathRowsMax * sizeof(LfPoseRec) : sizeof(LfPathDev) + kPathStackBytes, 0);
   LfPathDev& P = *reinterpret_cast<LfPathDev*>(buf.data());
   size_t next_stack = sizeof(LfPathDev);
   P.n = 0;
@@ -328,7 +393,19 @@ lf_status build_path_table(lf_ctx* ctx, int l, int i, int j, std::vector<unsigne
   auto put = [&](int k, int from, bool reflect, bool fwd) {
     if (P.n >= kPathRowsMax) { st = LF_ERR_STATE; return; }
     const size_t row_off = (size_t)((const unsigned char*)&P.row[P.n++] - buf.data());
-    if (lf_path_row_fill(ctx, l, k, from, reflect, fwd, buf.data(), row_off, &next_stack, buf.size()) != LF_OK) st = LF_ERR_STATE;
+    if (lf_path_row_fill(ctx, l, k, from, reflect, fwd, buf.data(), row_off, &next_stack, sizeof(LfPathDev) + kPathStackBytes) != LF_OK)
+      st = LF_ERR_STATE;
+    if (Po.n > 0 && Po.on[k] && L.surf[k].is_stop == 0.0f) {   // a posed row: its record, and which event runs in its frame
+      LfPathRow& w = P.row[P.n - 1];
+      w.kind |= LF_EV_POSE;
+      if (!(w.kind & LF_EV_BICONIC) && !(w.kind & LF_EV_ASPH && ctx->asph.n > 0)) {   // a sphere or a plane: as a biconic
+        w.kind = (w.kind & ~LF_EV_ASPH) | LF_EV_BICONIC;
+        w.asph = LfAsphRec{};
+        w.asph.kappa = L.surf[k].curv;
+      }
+      const LfPoseRec rec = lf_pose_make(Po.t[3 * k], Po.t[3 * k + 1], Po.t[3 * k + 2], Po.a[3 * k], Po.a[3 * k + 1], Po.a[3 * k + 2]);
+      std::memcpy(buf.data() + kPathPoseOffset + (size_t)(P.n - 1) * sizeof(rec), &rec, sizeof(rec));
+    }
   };
   if (i < 0) {
     for (int k = L.n_surf - 1; k >= 0; k--) put(k, k + 1, false, false);
@@ -366,6 +443,17 @@ lf_status lfk_biconic_events(lf_ctx* ctx, const float* consts16, int reflect, si
   return LF_OK;
 }
 
+lf_status lfk_pose_events(lf_ctx* ctx, const float* consts16, const float* pose16, int reflect, int asph, size_t n,
+                          const float* d_rays, float* d_out, int* d_fates) {
+  AsphEventArgs c, p;
+  std::memcpy(c.k, consts16, sizeof(c.k));
+  std::memcpy(p.k, pose16, sizeof(p.k));
+  hipLaunchKernelGGL(k_pose_events, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, c, p, reflect, asph, (int)n,
+                     d_rays, d_out, d_fates);
+  LF_HIP(ctx, hipGetLastError());
+  return LF_OK;
+}
+
 lf_status lfk_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, int n, const float* d_xy, const float* d_uv, float* d_out) {
   const LfApertureDev& m = ctx->ap[LF_APERTURE_STARBURST];
   ctx->lens.pitch = ctx->sensor_w_mm / (float)std::max(1, ctx->W);
@@ -378,10 +466,16 @@ lf_status lfk_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, int n, cons
   if (e == hipSuccess) e = hipMemcpyAsync(ctx->lens_dev, &ctx->lens, sizeof(LfLensDev), hipMemcpyHostToDevice, ctx->stream);
   if (e == hipSuccess) {
     const bool filt = ctx->mask_filter == LF_MASK_BILINEAR, coat = ctx->coat.n > 0;
-#define LF_LAUNCH_PATH(FF, CC, BB)                                                                                      \
-  hipLaunchKernelGGL((k_march_path_rays<FF, CC, BB>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,    \
+#define LF_LAUNCH_PATH(FF, CC, BB) LF_LAUNCH_PATH2(FF, CC, BB, false)
+#define LF_LAUNCH_PATH2(FF, CC, BB, PP)                                                                                 \
+  hipLaunchKernelGGL((k_march_path_rays<FF, CC, BB, PP>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,    \
                      ctx->lens_dev, (const LfPathDev*)d_tab, m.texels, m.w, m.h, n, d_xy, d_uv, d_out)
-    if (lf_march_biconic(ctx)) {   // (a lens with a biconic record: the instantiations that know the branch)
+    if (lf_march_posed(ctx)) {   // (a lens with a pose record: the instantiations that know both branches)
+      if (filt && coat) LF_LAUNCH_PATH2(true, true, true, true);
+      else if (filt) LF_LAUNCH_PATH2(true, false, true, true);
+      else if (coat) LF_LAUNCH_PATH2(false, true, true, true);
+      else LF_LAUNCH_PATH2(false, false, true, true);
+    } else if (lf_march_biconic(ctx)) {   // (a lens with a biconic record: the instantiations that know the branch)
       if (filt && coat) LF_LAUNCH_PATH(true, true, true);
       else if (filt) LF_LAUNCH_PATH(true, false, true);
       else if (coat) LF_LAUNCH_PATH(false, true, true);
@@ -391,6 +485,7 @@ lf_status lfk_march_path_rays(lf_ctx* ctx, int lambda, int i, int j, int n, cons
     else if (coat) LF_LAUNCH_PATH(false, true, false);
     else LF_LAUNCH_PATH(false, false, false);
 #undef LF_LAUNCH_PATH
+#undef LF_LAUNCH_PATH2
     e = hipGetLastError();
   }
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);   // (the table is this call's own)
@@ -408,11 +503,12 @@ lf_status lfk_march_asph(lf_ctx* ctx, const MarchArgs& a, size_t blocks) {
   const int var = kGen | (ctx->ghost_occlusion ? kVarOccl : 0) | (ctx->mask_filter == LF_MASK_BILINEAR ? kVarFilt : 0) |
                   (ctx->coat.n > 0 ? (kVarCoat | kVarStack) : 0);
   const bool bic = lf_march_biconic(ctx);   // (a biconic record: the same kernel with the branch that knows it)
+  const bool posed = lf_march_posed(ctx);   // (a pose record: ... with both branches)
   hipEvent_t ev = lf_timing_begin(ctx, LFK_MARCH);
 #define LF_LAUNCH_ASPH(VV)                                                                                               \
-  if (bic) LF_LAUNCH_ASPH2(VV, true); else LF_LAUNCH_ASPH2(VV, false)
-#define LF_LAUNCH_ASPH2(VV, BB)                                                                                          \
-  hipLaunchKernelGGL((k_march_asph<VV, BB>), dim3((unsigned)blocks), dim3(64 * kAsphWgWaves), 0, ctx->stream, ctx->lens_dev,  \
+  if (posed) LF_LAUNCH_ASPH2(VV, true, true); else if (bic) LF_LAUNCH_ASPH2(VV, true, false); else LF_LAUNCH_ASPH2(VV, false, false)
+#define LF_LAUNCH_ASPH2(VV, BB, PP)                                                                                      \
+  hipLaunchKernelGGL((k_march_asph<VV, BB, PP>), dim3((unsigned)blocks), dim3(64 * kAsphWgWaves), 0, ctx->stream, ctx->lens_dev,  \
                      ctx->pairs_dev, (const int*)(ctx->prog_dev + ctx->prog_seq_off),                                    \
                      (const LfProgRow*)(ctx->prog_dev + ctx->prog_rec_off),                                              \
                      (const LfWeightRow*)(ctx->prog_dev + ctx->prog_wrec_off),                                           \
