@@ -668,8 +668,8 @@ lf_status lf_biconic_events(lf_ctx* ctx, float curvature_x, float curvature_y, f
  * plane as a biconic), and is carried back -- the clear aperture is the glass's own, a ray that meets the surface from
  * behind is vignetted.  No cull table is built (LF_CULL_POSED); lights, films, stacks, occlusion, bands and deals work as on
  * any lens; lf_march_path_rays and lf_generate_lens_rays follow the records.  Refused with LF_ERR_UNSUPPORTED: sensor ghosts
- * under LF_SENSOR_GHOSTS_ADD / _ONLY (at lf_trace_ghosts) with lf_march_sensor_path_rays, and the lens camera's scene image under either setting of
- * lf_set_lens_camera_surfaces.  Everything paraxial -- pupils, focus, efl, the hand-over of a flare to a light -- stays the
+ * under LF_SENSOR_GHOSTS_ADD / _ONLY (at lf_trace_ghosts) with lf_march_sensor_path_rays, and the lens camera's scene image under every setting of
+ * lf_set_lens_camera_surfaces but LF_LENSCAM_SURFACES_POSED.  Everything paraxial -- pupils, focus, efl, the hand-over of a flare to a light -- stays the
  * centred lens's. */
 lf_status lf_set_lens_poses(lf_ctx* ctx, int n_surfaces, const int* on, const float* decentre, const float* tilt_deg);
 /* what is installed (any pointer may be NULL): on n_surfaces, decentre and tilt_deg 3 n_surfaces, n_posed = the records */
@@ -1281,12 +1281,19 @@ lf_status lf_set_lens_camera_aim(lf_ctx* ctx, float margin);
  *                                            the scene image such a lens forms: an anamorphic lens's squeeze and oval bokeh, where
  *                                            its ghosts belong.  A lens without records launches the kernels it always launched
  *                                            and renders the same frame bit for bit.
+ *   LF_LENSCAM_SURFACES_POSED                everything LF_LENSCAM_SURFACES_ALL accepts, plus pose records (lf_set_lens_poses):
+ *                                            the scene kernel marches a posed row with lf_march_path_rays' posed event, in the
+ *                                            frame of the surface -- the image shifts, the field tilts, the bokeh goes lopsided.
+ *                                            A lens without pose records launches what it launches under ALL, bit for bit.
+ *                                            Under the two settings above a posed lens stays LF_ERR_UNSUPPORTED.
+ * The value reads as bits -- 1: aspheric / biconic records, 2: poses -- and a posed face always runs in a recorded event's
+ * frame, so 2 alone is no setting (LF_ERR_INVALID).
  * Focus (lf_focus_lens), the entrance pupil (where the camera position sits in the lens) and the exit-pupil aim
  * (lf_set_lens_camera_aim) keep meaning the y meridian's paraxial quantities: for an anamorphic lens a convention about
  * where the camera sits, not an approximation of the image, which real rays form.  The exposure calibration follows the
  * records (it goes through lf_generate_lens_rays).  The per-lane test kernel (lf_test_knob("scene_compact", 0)) has no
  * instantiation for records: LF_ERR_UNSUPPORTED.  Any other value: LF_ERR_INVALID.  A change re-derives table and calibration. */
-typedef enum { LF_LENSCAM_SURFACES_SPHERICAL = 0, LF_LENSCAM_SURFACES_ALL = 1 } lf_lenscam_surfaces;
+typedef enum { LF_LENSCAM_SURFACES_SPHERICAL = 0, LF_LENSCAM_SURFACES_ALL = 1, LF_LENSCAM_SURFACES_POSED = 3 } lf_lenscam_surfaces;
 lf_status lf_set_lens_camera_surfaces(lf_ctx* ctx, int which);
 lf_status lf_get_lens_camera_surfaces(lf_ctx* ctx, int* which);
 /* The lens camera's samples, as the device draws them: out[(i * ns_aa + s) * 4 ..] = {X, Y, pa, pb} -- the sensor point in mm

@@ -551,8 +551,9 @@ def light_lobe_factors(kind, vec, angular_radius, rays):
 # with a point light installed is refused) or at the light
 OCCLUSION_REACH_SKY, OCCLUSION_REACH_LIGHT = 0, 1
 # which interfaces the lens camera's primary path may meet (lf_set_lens_camera_surfaces): spheres, flats and the stop (the default: a
-# lens with aspheric or biconic records is refused, as it always was), or every kind the geometric lens knows
-LENSCAM_SURFACES_SPHERICAL, LENSCAM_SURFACES_ALL = 0, 1
+# lens with aspheric or biconic records is refused, as it always was), every recorded kind, or those and posed interfaces
+# (lf_set_lens_poses).  Bits: 1 records, 2 poses; 2 alone is no setting
+LENSCAM_SURFACES_SPHERICAL, LENSCAM_SURFACES_ALL, LENSCAM_SURFACES_POSED = 0, 1, 3
 
 
 def ghost_shadow_reach(kind, vec, rays, world_per_mm):
@@ -1815,9 +1816,11 @@ class LensFlare:
 
     def set_lens_camera_surfaces(self, which=LENSCAM_SURFACES_SPHERICAL):
         """LENSCAM_SURFACES_ALL: render_scene_term and lens_camera() accept a lens with aspheric and / or biconic records (the
-        scene kernel marches them); LENSCAM_SURFACES_SPHERICAL (the default) refuses such a lens as before."""
+        scene kernel marches them); LENSCAM_SURFACES_POSED: those, and a lens with pose records (set_lens_poses);
+        LENSCAM_SURFACES_SPHERICAL (the default) refuses such lenses as before."""
         if isinstance(which, bool) or not isinstance(which, (int, np.integer)):
-            raise ValueError("set_lens_camera_surfaces: LENSCAM_SURFACES_SPHERICAL (0) or LENSCAM_SURFACES_ALL (1)")
+            raise ValueError("set_lens_camera_surfaces: LENSCAM_SURFACES_SPHERICAL (0), LENSCAM_SURFACES_ALL (1) or "
+                             "LENSCAM_SURFACES_POSED (3)")
         self._ck(self.lib.lf_set_lens_camera_surfaces(self.ctx, int(which)))
 
     def lens_camera_surfaces(self):

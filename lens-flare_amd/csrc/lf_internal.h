@@ -453,10 +453,17 @@ constexpr size_t kPrimaryStackBytes = (size_t)LF_MAX_SURFACES * LF_MAX_LAMBDA * 
 // and a 32-byte slot in LfAsphRec's layout (lf_asphere.h; a biconic record {1/Rx, kx, ky} sits in the same slot, as it does in
 // the march's table).  Built and uploaded by lf_upload_primary_table only for a lens that has records; read by
 // primary_path_general (lf_primary_general.h) under LF_LENSCAM_SURFACES_ALL.
-struct alignas(32) LfPrimarySurfDev {
+// Under LF_LENSCAM_SURFACES_POSED a posed row's kind word also carries LF_EV_POSE (with LF_EV_ASPH or LF_EV_BICONIC: which
+// event runs in the surface's frame, as in lf_march_path_rays' rows) and `pose` holds the row's LfPoseRec (lf_pose.h: R
+// row-major, t, four spare words), 64 bytes per row BEHIND the records, whose offsets do not move.  Row e is interface
+// n - 1 - e: the pose of interface k lies in row n - 1 - k.  Uploaded only for a lens with pose records.
+struct alignas(64) LfPrimarySurfDev {
   int kind[LF_MAX_SURFACES];
   alignas(32) float rec[LF_MAX_SURFACES][8];
+  alignas(64) float pose[LF_MAX_SURFACES][16];
 };
+static_assert(offsetof(LfPrimarySurfDev, rec) == 64 && offsetof(LfPrimarySurfDev, pose) == 64 + 32 * LF_MAX_SURFACES,
+              "the SURF = 1, 2 kernels read kind and rec at these offsets");
 // what k_scene_term's lens mode needs beside the table (kernel argument, by value)
 struct LfLensCamArgs {
   int mode;              // 1 = one reference wavelength carries R, G and B; 2 = one ray per wavelength

@@ -23,6 +23,7 @@
 
 #include "lf_internal.h"
 #include "lf_march_events.h"
+#include "lf_pose.h"
 
 // host: one row per interface in the order the primary path meets them, constants as pack_program
 // derives them for a ray travelling -z (n_in = the medium behind the interface, n_out = in front)
@@ -78,7 +79,11 @@ lf_status lf_upload_primary_table(lf_ctx* ctx) {
   LF_HIP(ctx, hipMemcpy(ctx->primary_dev, buf.data(), buf.size(), hipMemcpyHostToDevice));
   // the records of a lens that has any, row by row (LfPrimarySurfDev): which rows carry one is lf_march_path_rays's own
   // predicate, so that lf_generate_lens_rays and the scene kernel march the same surfaces.  A lens of spheres uploads nothing.
-  if (ctx->asph.n > 0 || ctx->bic.n > 0) {
+  // A posed row (lf_set_lens_poses) is what build_path_table makes of one: LF_EV_POSE with the event that runs in its frame --
+  // its aspheric record, its biconic record, or a sphere / plane written as the biconic {1/R, 0, 0} -- and the row's
+  // LfPoseRec behind the records.  Row e is interface k = n - 1 - e: the pose of interface k goes to row e.
+  const LfPoses& Po = ctx->pose;
+  if (ctx->asph.n > 0 || ctx->bic.n > 0 || Po.n > 0) {
     std::vector<unsigned char> sbuf(sizeof(LfPrimarySurfDev), 0);
     LfPrimarySurfDev& S = *reinterpret_cast<LfPrimarySurfDev*>(sbuf.data());
     const LfAspheres& A = ctx->asph;
@@ -96,9 +101,26 @@ lf_status lf_upload_primary_table(lf_ctx* ctx) {
         S.rec[e][0] = A.kappa[k];
         for (int m = 0; m < LF_MAX_ASPH_COEF; m++) S.rec[e][1 + m] = A.coef[(size_t)m * L.n_surf + k];
       }
+      if (Po.n > 0 && Po.on[k]) {
+        if (kind == LF_EV_ASPH && A.n > 0) {
+          S.kind[e] = LF_EV_POSE | LF_EV_ASPH;
+        } else {
+          S.kind[e] = LF_EV_POSE | LF_EV_BICONIC;
+          if (kind != LF_EV_BICONIC) {   // a sphere or a plane: as a biconic
+            for (int m = 0; m < 8; m++) S.rec[e][m] = 0.0f;
+            S.rec[e][0] = L.surf[k].curv;
+          }
+        }
+        const lfm::LfPoseRec rec = lfm::lf_pose_make(Po.t[3 * k], Po.t[3 * k + 1], Po.t[3 * k + 2], Po.a[3 * k], Po.a[3 * k + 1],
+                                                     Po.a[3 * k + 2]);
+        static_assert(sizeof(rec) == sizeof(S.pose[0]), "one pose record per primary row");
+        std::memcpy(S.pose[e], &rec, sizeof(rec));
+      }
     }
     if (!ctx->primary_surf_dev) LF_HIP(ctx, hipMalloc((void**)&ctx->primary_surf_dev, sbuf.size()));
-    LF_HIP(ctx, hipMemcpy(ctx->primary_surf_dev, sbuf.data(), sbuf.size(), hipMemcpyHostToDevice));
+    // (a lens without pose records uploads what it always uploaded: kinds and records)
+    LF_HIP(ctx, hipMemcpy(ctx->primary_surf_dev, sbuf.data(), Po.n > 0 ? sbuf.size() : offsetof(LfPrimarySurfDev, pose),
+                          hipMemcpyHostToDevice));
   }
   return LF_OK;
 }
@@ -179,11 +201,12 @@ static lf_status calibrate_exposure(lf_ctx* ctx, double* exposure) {
 
 lf_status lf_lenscam_prepare(lf_ctx* ctx) {
   // (the default setting, LF_LENSCAM_SURFACES_SPHERICAL, refuses a lens with records as it always has; under
-  // LF_LENSCAM_SURFACES_ALL the scene kernel marches them: lf_set_lens_camera_surfaces)
-  const bool spherical_only = ctx->lenscam_surfaces == LF_LENSCAM_SURFACES_SPHERICAL;
-  if (ctx->pose.n > 0)
+  // LF_LENSCAM_SURFACES_ALL the scene kernel marches aspheric and biconic records, under LF_LENSCAM_SURFACES_POSED pose
+  // records too: lf_set_lens_camera_surfaces.  The value is two bits -- 1: records, 2: poses)
+  const bool spherical_only = (ctx->lenscam_surfaces & 1) == 0;
+  if (ctx->pose.n > 0 && (ctx->lenscam_surfaces & 2) == 0)
     return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lens camera: the lens has posed interfaces (lf_set_lens_poses) -- the scene term's primary "
-                                            "path marches none under either setting of lf_set_lens_camera_surfaces; "
+                                            "path marches them under LF_LENSCAM_SURFACES_POSED of lf_set_lens_camera_surfaces alone; "
                                             "lf_generate_lens_rays marches them");
   if (spherical_only && ctx->asph.n > 0)
     return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lens camera: the lens has aspheric interfaces (lf_set_lens_aspheres) -- the scene term's primary "
@@ -256,8 +279,10 @@ extern "C" {
 
 lf_status lf_set_lens_camera_surfaces(lf_ctx* ctx, int which) {
   if (!ctx) return LF_ERR_INVALID;
-  if (which != LF_LENSCAM_SURFACES_SPHERICAL && which != LF_LENSCAM_SURFACES_ALL)
-    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_camera_surfaces: LF_LENSCAM_SURFACES_SPHERICAL (0) or LF_LENSCAM_SURFACES_ALL (1)");
+  // (bit 0: aspheric / biconic records, bit 1: poses -- a posed face runs in a recorded event's frame, so 2 alone is no setting)
+  if (which != LF_LENSCAM_SURFACES_SPHERICAL && which != LF_LENSCAM_SURFACES_ALL && which != LF_LENSCAM_SURFACES_POSED)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_lens_camera_surfaces: LF_LENSCAM_SURFACES_SPHERICAL (0), LF_LENSCAM_SURFACES_ALL (1) or "
+                                        "LF_LENSCAM_SURFACES_POSED (3)");
   if (which != ctx->lenscam_surfaces) ctx->lenscam_dirty = true;
   ctx->lenscam_surfaces = which;
   return LF_OK;

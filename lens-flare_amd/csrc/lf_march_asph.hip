@@ -48,21 +48,7 @@ __device__ __forceinline__ LfAsphRec load_asph(const LfAsphRec* __restrict__ bas
   return r;
 }
 
-// a record of the pose table: TWO 32-byte scalar loads (the offset is wave-uniform)
-__device__ __forceinline__ LfPoseRec load_pose(const LfPoseRec* __restrict__ base, unsigned off) {
-  typedef const char __attribute__((address_space(4))) * cptr;
-  const lf_i8 v = *(const lf_i8 __attribute__((address_space(4)))*)((cptr)(base) + off);
-  const lf_i8 w = *(const lf_i8 __attribute__((address_space(4)))*)((cptr)(base) + off + 32u);
-  LfPoseRec r;
-#pragma unroll
-  for (int m = 0; m < 8; m++) r.r[m] = __int_as_float(v[m]);
-  r.r[8] = __int_as_float(w[0]);
-#pragma unroll
-  for (int m = 0; m < 3; m++) r.t[m] = __int_as_float(w[1 + m]);
-#pragma unroll
-  for (int m = 0; m < 4; m++) r.spare[m] = 0.0f;
-  return r;
-}
+// (a record of the pose table: load_pose, lf_pose.h)
 
 struct AsphTally {
   unsigned long long n_rays = 0, events = 0, n_clip = 0, n_vign = 0, n_tir = 0, n_scene = 0, n_rm_lane = 0, n_rm_rows = 0;

@@ -4,7 +4,7 @@
 // nominal vertex on the axis, t = (dx, dy, dz) in mm, the angles right-handed and in degrees, the turn about the surface's
 // own z first (it rotates a cylinder's axis).  Each interface on its own: a record is no cumulative coordinate break.
 // R and t are formed on the host in double and narrowed to float (lf_pose_make).  ONE definition of the event for the host
-// (lf_pose_event) and the kernels (lf_march_asph.hip), in lf_asphere.h's conventions: every multiply-add an explicit fmaf,
+// (lf_pose_event) and the kernels (lf_march_asph.hip; lf_primary_general.h for lf_scene.hip), in lf_asphere.h's conventions: every multiply-add an explicit fmaf,
 // every root and division the IEEE one, so that both sides agree bit for bit.  Nothing here is part of the ABI.
 #pragma once
 
@@ -18,7 +18,8 @@
 namespace lfm {
 
 // The record of a posed (interface, direction of travel): R row-major and t, in a side table of its own -- 64 bytes at the
-// program record's own offset, two aligned wave-uniform loads (load_pose, lf_march_asph.hip).
+// program record's own offset (one per primary row in the lens camera's LfPrimarySurfDev), two aligned wave-uniform loads
+// (load_pose, below).
 struct alignas(64) LfPoseRec {
   float r[9];
   float t[3];
@@ -91,6 +92,23 @@ __host__ __device__ inline AsphHit lf_pose_event(float& px, float& py, float& hz
 }
 
 #if defined(__HIPCC__)
+// a record of a pose table: TWO 32-byte scalar loads (the offset is wave-uniform).  One helper for the march's tables
+// (lf_march_asph.hip) and the lens camera's primary rows (lf_primary_general.h).
+__device__ __forceinline__ LfPoseRec load_pose(const LfPoseRec* __restrict__ base, unsigned off) {
+  typedef const char __attribute__((address_space(4))) * cptr;
+  const lf_i8 v = *(const lf_i8 __attribute__((address_space(4)))*)((cptr)(base) + off);
+  const lf_i8 w = *(const lf_i8 __attribute__((address_space(4)))*)((cptr)(base) + off + 32u);
+  LfPoseRec r;
+#pragma unroll
+  for (int m = 0; m < 8; m++) r.r[m] = __int_as_float(v[m]);
+  r.r[8] = __int_as_float(w[0]);
+#pragma unroll
+  for (int m = 0; m < 3; m++) r.t[m] = __int_as_float(w[1 + m]);
+#pragma unroll
+  for (int m = 0; m < 4; m++) r.spare[m] = 0.0f;
+  return r;
+}
+
 // The event of a marching wave: biconic_event's interface, liveness masks and weight on a posed interface; `asph` is
 // wave-uniform (a kind bit of the row).
 template <bool W, class CT = NoCoat>

@@ -2,13 +2,16 @@
 // lf_set_lens_biconics), for the lens camera of the scene term under LF_LENSCAM_SURFACES_ALL (lf_set_lens_camera_surfaces;
 // DESIGN.md section 4, "the scene through recorded interfaces").  primary_path (lf_march_events.h) and LfPrimaryDev know
 // spheres only and stay as they are; the records travel in a side table of their own (LfPrimarySurfDev, lf_internal.h: one
-// kind word and one 32-byte record slot per primary row).  Device code only; nothing here is part of the ABI.
+// kind word and one 32-byte record slot per primary row).  Under LF_LENSCAM_SURFACES_POSED a row may be posed too
+// (lf_set_lens_poses): its kind word carries LF_EV_POSE and its LfPoseRec lies behind the records (SURF = 3).  Device code only;
+// nothing here is part of the ABI.
 #pragma once
 
 #include "lf_internal.h"
 #include "lf_march_events.h"
 #include "lf_asphere.h"
 #include "lf_biconic.h"
+#include "lf_pose.h"
 
 namespace lfm {
 
@@ -33,6 +36,12 @@ template <int SURF, class CT>
 __device__ __forceinline__ lanemask primary_row_general(const LfPrimaryRow& w, const LfPrimarySurfDev* __restrict__ S, int e,
                                                         int lambda, Ray& r, lanemask& geom_ok, const CT& coat) {
   const int kind = load_primary_surf_kind(S, e);
+  if (SURF >= 3 && (kind & LF_EV_POSE)) {      // wave-uniform: a posed row -- its record in the slot, R and t behind the records (SGPRs)
+    const LfAsphRec rec = load_primary_surf_rec(S, e);
+    const LfPoseRec pose = load_pose((const LfPoseRec*)&S->pose[0][0], (unsigned)e * (unsigned)sizeof(LfPoseRec));
+    return pose_event<true>(r, w.dzv, w.curv, (kind & LF_EV_ASPH) != 0, rec, pose, w.delta[lambda], w.h2, false, -1.0f, geom_ok,
+                            w.fs[lambda], w.fo[lambda], w.fi[lambda], coat);
+  }
   if (SURF >= 2 && (kind & LF_EV_BICONIC)) {   // wave-uniform: a biconic record {1/Rx, kx, ky} in the row's slot
     const LfAsphRec rec = load_primary_surf_rec(S, e);
     return biconic_event<true>(r, w.dzv, w.curv, LfBicRec{rec.kappa, rec.a[0], rec.a[1], {}}, w.delta[lambda], w.h2, false,
@@ -48,7 +57,8 @@ __device__ __forceinline__ lanemask primary_row_general(const LfPrimaryRow& w, c
 }
 
 // primary_path with the rows' records.  SURF = 0: spheres, primary_path itself; 1: aspheric records; 2: aspheric and
-// biconic records (a lens may carry both kinds on different interfaces, as k_march_asph<VAR, true> allows).  VAR holds
+// biconic records (a lens may carry both kinds on different interfaces, as k_march_asph<VAR, true> allows); 3: pose records
+// too (pose_event<true> in the frame of the row's aspheric or biconic event, as k_march_path_rays<.., true, true>).  VAR holds
 // kVarCoat (the lens camera's kernels always do).  The Newton step counts are the events' fixed, wave-uniform six and three.
 template <int VAR, int SURF>
 __device__ __forceinline__ bool primary_path_general(const LfPrimaryDev* __restrict__ P, const LfPrimarySurfDev* __restrict__ S,

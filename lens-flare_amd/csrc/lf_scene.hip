@@ -474,11 +474,25 @@ constexpr int kLensStridedMaxPrims = 1024;
 #ifndef LF_SCENE_LENS_SURF_SOFT_WAVES
 #define LF_SCENE_LENS_SURF_SOFT_WAVES 1
 #endif
-// SURF (lf_set_lens_camera_surfaces, LF_LENSCAM_SURFACES_ALL): what the primary path's rows may be -- 0 spheres (the kernel it
-// was: primary_path itself, `surf` unread), 1 aspheric records too, 2 aspheric and biconic records (primary_path_general,
-// lf_primary_general.h; the records in `surf`).  Launched by what the lens holds: a lens of spheres never sees 1 or 2.
+// The SURF = 3 instantiations (posed interfaces, LF_LENSCAM_SURFACES_POSED) have bounds of their own, so that a change of
+// them leaves SURF = 1, 2 alone (profiles/lenscam_poses_resources.txt).
+#ifndef LF_SCENE_LENS_POSE_WAVES
+#define LF_SCENE_LENS_POSE_WAVES 2
+#endif
+#ifndef LF_SCENE_LENS_POSE_SOFT_WAVES
+#define LF_SCENE_LENS_POSE_SOFT_WAVES 1
+#endif
+// SURF (lf_set_lens_camera_surfaces, LF_LENSCAM_SURFACES_ALL / _POSED): what the primary path's rows may be -- 0 spheres (the
+// kernel it was: primary_path itself, `surf` unread), 1 aspheric records too, 2 aspheric and biconic records, 3 pose records too
+// (primary_path_general, lf_primary_general.h; the records in `surf`).  Launched by what the lens holds: a lens of spheres
+// never sees 1, 2 or 3, a lens without pose records never 3.
+constexpr int scene_lens_waves(bool soft, int surf) {
+  return surf == 0 ? LF_SCENE_LENS_WAVES
+       : surf == 3 ? (soft ? LF_SCENE_LENS_POSE_SOFT_WAVES : LF_SCENE_LENS_POSE_WAVES)
+                   : (soft ? LF_SCENE_LENS_SURF_SOFT_WAVES : LF_SCENE_LENS_SURF_WAVES);
+}
 template <bool SOFT, bool FILT = false, bool STACK = false, int SURF = 0>   // FILT, STACK: as scene_pixel's
-__global__ __launch_bounds__(256, SURF == 0 ? LF_SCENE_LENS_WAVES : SOFT ? LF_SCENE_LENS_SURF_SOFT_WAVES : LF_SCENE_LENS_SURF_WAVES) void k_scene_lens(
+__global__ __launch_bounds__(256, scene_lens_waves(SOFT, SURF)) void k_scene_lens(
                                                        LfSceneDev sc, LfEnvDev ev, LfCamera cam, ScenePixelArgs a,
                                                        int y0, int y1, LfDeal deal, int mxs, LfLensCamArgs lc,
                                                        const LfPrimaryDev* __restrict__ prim,
@@ -1181,17 +1195,18 @@ lf_status lf_render_scene_term(lf_ctx* ctx) {
   LfLensCamArgs lc;
   lf_fill_lenscam_args(ctx, &lc);
   // (lf_set_lens_camera_surfaces(LF_LENSCAM_SURFACES_ALL) let a lens with records through lf_lenscam_prepare: the compacted
-  // kernel's SURF instantiations march them -- 2 knows both kinds, a lens may carry both; the per-lane A/B kernel has none)
-  const int lens_surf = !lens ? 0 : ctx->bic.n > 0 ? 2 : ctx->asph.n > 0 ? 1 : 0;
+  // kernel's SURF instantiations march them -- 2 knows both kinds, a lens may carry both; 3, under LF_LENSCAM_SURFACES_POSED,
+  // knows pose records too (lf_set_lens_poses); the per-lane A/B kernel has none)
+  const int lens_surf = !lens ? 0 : ctx->pose.n > 0 ? 3 : ctx->bic.n > 0 ? 2 : ctx->asph.n > 0 ? 1 : 0;
   if (lens_surf != 0 && ctx->scene_compact == 0)
-    return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lens camera: a lens with aspheric / biconic records is marched by the compacted scene "
+    return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lens camera: a lens with aspheric / biconic / pose records is marched by the compacted scene "
                                             "kernel alone (lf_test_knob(\"scene_compact\", 0) selects the per-lane kernel)");
   if (lens_surf != 0 && !ctx->primary_surf_dev)
     return lf_fail(ctx, LF_ERR_STATE, "lens camera: the primary rows' records were not uploaded");
   hipEvent_t ev = lf_timing_begin(ctx, LFK_SCENE);
 #define LF_LAUNCH_SCENE_LENS(SOFT)  do { if (filt && stacks) LF_LAUNCH_SCENE_LENS1(SOFT, true, true); else if (stacks) LF_LAUNCH_SCENE_LENS1(SOFT, false, true); \
                                          else if (filt) LF_LAUNCH_SCENE_LENS1(SOFT, true, false); else LF_LAUNCH_SCENE_LENS1(SOFT, false, false); } while (0)
-#define LF_LAUNCH_SCENE_LENS1(SOFT, FILT, STACK)  do { if (lens_surf == 2) LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK, 2); else if (lens_surf == 1) LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK, 1); \
+#define LF_LAUNCH_SCENE_LENS1(SOFT, FILT, STACK)  do { if (lens_surf == 3) LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK, 3); else if (lens_surf == 2) LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK, 2); else if (lens_surf == 1) LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK, 1); \
                                                        else LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK, 0); } while (0)
 #define LF_LAUNCH_SCENE_LENS2(SOFT, FILT, STACK, SURF)                                                     \
   hipLaunchKernelGGL((k_scene_lens<SOFT, FILT, STACK, SURF>), dim3((unsigned)((lens_tiles_x + 3) / 4), (unsigned)(((ctx->y1 + 7) >> 3) - (ctx->y0 >> 3))), \
