@@ -582,9 +582,27 @@ enum { LF_SENSOR_GHOSTS_OFF = 0, LF_SENSOR_GHOSTS_ADD = 1, LF_SENSOR_GHOSTS_ONLY
 lf_status lf_set_sensor_ghosts(lf_ctx* ctx, int mode, const int* interfaces, int n);
 lf_status lf_get_sensor_ghosts(lf_ctx* ctx, int* mode, int* interfaces, int cap, int* n);
 /* lf_march_path_rays' twin for the sensor path of interface i: the same eight floats per ray, the weight with
- * reflectance[lambda]; follows films, stacks, aspheric and biconic records and the mask filter; aims at the default disc. */
+ * reflectance[lambda]; follows films, stacks, aspheric and biconic records and the mask filter; aims at the default disc.
+ * A lens with pose records: LF_ERR_UNSUPPORTED under LF_SENSOR_SURFACES_CENTRED, marched under LF_SENSOR_SURFACES_POSED
+ * (lf_set_sensor_ghost_surfaces, below). */
 lf_status lf_march_sensor_path_rays(lf_ctx* ctx, int lambda, int i, size_t n, const float* sensor_xy_mm, const float* pupil_uv,
                                     float* out);
+/* Which interfaces a sensor path may meet, a setting of the context (nothing clears it: not lf_set_lens, not lf_focus_lens):
+ *   LF_SENSOR_SURFACES_CENTRED   the default: every interface on the axis.  A lens with pose records (lf_set_lens_poses) is
+ *                                refused with LF_ERR_UNSUPPORTED by lf_trace_ghosts under LF_SENSOR_GHOSTS_ADD / _ONLY and by
+ *                                lf_march_sensor_path_rays.
+ *   LF_SENSOR_SURFACES_POSED     both march such a lens: every crossing of a posed interface -- three for one behind the
+ *                                path's mirror: towards the scene, towards the sensor, towards the scene -- is
+ *                                lf_march_path_rays' posed event (lf_pose_event) with the row's own direction of travel; a
+ *                                ray that meets the face from behind is lost there.  The stop and the sensor carry no pose.
+ *                                On a lens without pose records the setting changes nothing: the same kernels, the same bits.
+ * Any other value: LF_ERR_INVALID, the previous one stays.  The sensor paths keep aiming at the default disc, and that disc
+ * is the CENTRED rear element's clear aperture at its nominal vertex plane, also when that element is decentred -- the
+ * convention of the ordinary march of a posed lens and of the lens camera: it says where the samples aim, the event itself
+ * is not approximated. */
+enum { LF_SENSOR_SURFACES_CENTRED = 0, LF_SENSOR_SURFACES_POSED = 1 };
+lf_status lf_set_sensor_ghost_surfaces(lf_ctx* ctx, int which);
+lf_status lf_get_sensor_ghost_surfaces(lf_ctx* ctx, int* which);
 /* host only: the events of the sensor path of interface i in marching order, out[e] = interface | reflect << 8 | forward << 9
  * with n_surfaces standing for the sensor's mirror; *n_events = 3 n_surfaces - 2 i.  LF_ERR_INVALID: i the stop or out of range,
  * cap too small. */
@@ -596,7 +614,8 @@ lf_status lf_sensor_mirror_event(const float ray_in[6], float dzv, float half_wi
                                  int* inside);
 /* Since the last lf_reset_counters: {sensor-path rays started, rays that reached the sensor's mirror, of those lost off the
  * rectangle there, lit (ray, light) contributions}.  lf_get_counters, lf_get_executed_events and lf_get_march_stats keep
- * describing the ordinary paths alone, under ADD too.  lf_timing_get's slot of the launch: "march_sensor". */
+ * describing the ordinary paths alone, under ADD too.  lf_timing_get's slot of the launch: "march_sensor"; "sensor_table"
+ * counts the uploads of the sensor paths' table (one when its rows or pose records changed, none for an unchanged frame). */
 lf_status lf_get_sensor_ghost_stats(lf_ctx* ctx, uint64_t out[4]);
 /* BICONIC INTERFACES: cylinders, toroids, the anamorphic flare (no reference counterpart).  Interface k of the installed
  * lens becomes
@@ -667,8 +686,9 @@ lf_status lf_biconic_events(lf_ctx* ctx, float curvature_x, float curvature_y, f
  * ray is carried into the surface's frame, meets the interface through the aspheric or the biconic event (a sphere or a
  * plane as a biconic), and is carried back -- the clear aperture is the glass's own, a ray that meets the surface from
  * behind is vignetted.  No cull table is built (LF_CULL_POSED); lights, films, stacks, occlusion, bands and deals work as on
- * any lens; lf_march_path_rays and lf_generate_lens_rays follow the records.  Refused with LF_ERR_UNSUPPORTED: sensor ghosts
- * under LF_SENSOR_GHOSTS_ADD / _ONLY (at lf_trace_ghosts) with lf_march_sensor_path_rays, and the lens camera's scene image under every setting of
+ * any lens; lf_march_path_rays and lf_generate_lens_rays follow the records.  Refused with LF_ERR_UNSUPPORTED under the
+ * default settings: sensor ghosts under LF_SENSOR_GHOSTS_ADD / _ONLY (at lf_trace_ghosts) with lf_march_sensor_path_rays
+ * (lf_set_sensor_ghost_surfaces(LF_SENSOR_SURFACES_POSED) lifts both), and the lens camera's scene image under every setting of
  * lf_set_lens_camera_surfaces but LF_LENSCAM_SURFACES_POSED.  Everything paraxial -- pupils, focus, efl, the hand-over of a flare to a light -- stays the
  * centred lens's. */
 lf_status lf_set_lens_poses(lf_ctx* ctx, int n_surfaces, const int* on, const float* decentre, const float* tilt_deg);

@@ -55,6 +55,7 @@ ABI_SYMBOLS = [
     "lf_set_lens_poses", "lf_get_lens_poses", "lf_pose_event", "lf_pose_events",
     "lf_set_sensor_reflectance", "lf_get_sensor_reflectance", "lf_set_sensor_ghosts", "lf_get_sensor_ghosts",
     "lf_march_sensor_path_rays", "lf_sensor_path_sequence", "lf_sensor_mirror_event", "lf_get_sensor_ghost_stats",
+    "lf_set_sensor_ghost_surfaces", "lf_get_sensor_ghost_surfaces",
     "lf_set_mask_filter", "lf_get_mask_filter", "lf_mask_lookup",
     "lf_set_pupil_target", "lf_get_pupil_target", "lf_aim_at_exit_pupil", "lf_paraxial_exit_pupil", "lf_set_ghost_accumulate",
     "lf_set_lens_camera", "lf_get_lens_camera", "lf_set_lens_camera_aim", "lf_set_lens_camera_surfaces", "lf_get_lens_camera_surfaces",
@@ -312,6 +313,7 @@ ASPH_ALIVE, ASPH_MISSED, ASPH_APERTURE, ASPH_TIR = 0, 1, 2, 3   # the fates of l
 CULL_ANAMORPHIC = 10     # LF_CULL_ANAMORPHIC
 CULL_POSED = 11          # LF_CULL_POSED
 SENSOR_GHOSTS_OFF, SENSOR_GHOSTS_ADD, SENSOR_GHOSTS_ONLY = 0, 1, 2   # the modes of lf_set_sensor_ghosts
+SENSOR_SURFACES_CENTRED, SENSOR_SURFACES_POSED = 0, 1                # lf_set_sensor_ghost_surfaces: may a sensor path meet posed interfaces
 
 
 def sensor_path_sequence(n_surfaces, stop_index, i):
@@ -1201,6 +1203,17 @@ class LensFlare:
         sel = np.zeros(16, np.int32)
         self._ck(self.lib.lf_get_sensor_ghosts(self.ctx, C.byref(mode), _fp(sel, C.c_int), len(sel), C.byref(n)))
         return mode.value, [int(v) for v in sel[:n.value]]
+
+    def set_sensor_ghost_surfaces(self, which=SENSOR_SURFACES_POSED):
+        """Which interfaces a sensor path may meet: SENSOR_SURFACES_CENTRED (the default: a lens with pose records is refused)
+        or SENSOR_SURFACES_POSED (trace_ghosts under SENSOR_GHOSTS_ADD / _ONLY and march_sensor_path_rays march it).  A
+        setting of the context: set_lens and focus_lens keep it; a lens without pose records renders the same bits under both."""
+        self._ck(self.lib.lf_set_sensor_ghost_surfaces(self.ctx, int(which)))
+
+    def sensor_ghost_surfaces(self):
+        which = C.c_int()
+        self._ck(self.lib.lf_get_sensor_ghost_surfaces(self.ctx, C.byref(which)))
+        return which.value
 
     def march_sensor_path_rays(self, lam, i, sensor_xy_mm, pupil_uv):
         """march_path_rays along the sensor path of interface i: n x 8, the weight with the sensor's reflectance."""

@@ -78,7 +78,7 @@ namespace {
 
 const char* kKernelNames[LFK_COUNT] = {"march", "flare_layer", "ghost_raster", "dft",
                                        "frame_setup", "tonemap", "exchange", "scene_term", "cull_prepass", "cull_audit",
-                                       "cull_cache_build", "flare_visibility", "march_sensor"};
+                                       "cull_cache_build", "flare_visibility", "march_sensor", "sensor_table"};
 
 // the reference's hard-coded prescription (pathtracer.cpp:541-556); literals narrowed to float
 // where the reference narrows them
@@ -1646,9 +1646,10 @@ lf_status lf_trace_ghosts(lf_ctx* ctx, int spp, uint64_t key) {
   const int sensor_mode = ctx->sensor.mode;
   if (sensor_mode != LF_SENSOR_GHOSTS_OFF && ctx->sensor.n_refl == 0)
     return lf_fail(ctx, LF_ERR_STATE, "lf_trace_ghosts: sensor ghosts are on and the sensor has no reflectance (lf_set_sensor_reflectance)");
-  if (sensor_mode != LF_SENSOR_GHOSTS_OFF && ctx->pose.n > 0)
+  if (sensor_mode != LF_SENSOR_GHOSTS_OFF && ctx->pose.n > 0 && ctx->sensor.surfaces != LF_SENSOR_SURFACES_POSED)
     return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lf_trace_ghosts: sensor ghosts (lf_set_sensor_ghosts: LF_SENSOR_GHOSTS_ADD / LF_SENSOR_GHOSTS_ONLY) "
-                                            "are not marched through a lens with posed interfaces (lf_set_lens_poses)");
+                                            "are not marched through a lens with posed interfaces (lf_set_lens_poses) under "
+                                            "LF_SENSOR_SURFACES_CENTRED; lf_set_sensor_ghost_surfaces(LF_SENSOR_SURFACES_POSED) marches them");
   LF_HIP(ctx, hipSetDevice(ctx->device));
   lf_status st = LF_OK;
   if (sensor_mode != LF_SENSOR_GHOSTS_ONLY) st = lfk_march(ctx, spp, key);
@@ -2676,6 +2677,20 @@ lf_status lf_get_sensor_ghosts(lf_ctx* ctx, int* mode, int* interfaces, int cap,
   return LF_OK;
 }
 
+lf_status lf_set_sensor_ghost_surfaces(lf_ctx* ctx, int which) {
+  if (!ctx) return LF_ERR_INVALID;
+  if (which != LF_SENSOR_SURFACES_CENTRED && which != LF_SENSOR_SURFACES_POSED)
+    return lf_fail(ctx, LF_ERR_INVALID, "lf_set_sensor_ghost_surfaces: LF_SENSOR_SURFACES_CENTRED (0) or LF_SENSOR_SURFACES_POSED (1)");
+  ctx->sensor.surfaces = which;   // (the table's dirty test is by content: nothing to mark)
+  return LF_OK;
+}
+
+lf_status lf_get_sensor_ghost_surfaces(lf_ctx* ctx, int* which) {
+  if (!ctx || !which) return LF_ERR_INVALID;
+  *which = ctx->sensor.surfaces;
+  return LF_OK;
+}
+
 lf_status lf_sensor_path_sequence(int n_surfaces, int stop_index, int i, int* out, int cap, int* n_events) {
   if (n_surfaces < 1 || n_surfaces > LF_MAX_SURFACES || stop_index < -1 || stop_index >= n_surfaces || !out || !n_events)
     return LF_ERR_INVALID;
@@ -2709,9 +2724,10 @@ lf_status lf_march_sensor_path_rays(lf_ctx* ctx, int lambda, int i, size_t n, co
     return lf_fail(ctx, LF_ERR_STATE, "aperture mask (LF_APERTURE_STARBURST slot) not set");
   if (ctx->sensor.n_refl == 0)
     return lf_fail(ctx, LF_ERR_STATE, "lf_march_sensor_path_rays: the sensor has no reflectance (lf_set_sensor_reflectance)");
-  if (ctx->pose.n > 0)   // (as lf_trace_ghosts refuses the frame: the sensor paths know no pose record)
+  if (ctx->pose.n > 0 && ctx->sensor.surfaces != LF_SENSOR_SURFACES_POSED)   // (as lf_trace_ghosts refuses the frame)
     return lf_fail(ctx, LF_ERR_UNSUPPORTED, "lf_march_sensor_path_rays: sensor paths are not marched through a lens with posed "
-                                            "interfaces (lf_set_lens_poses)");
+                                            "interfaces (lf_set_lens_poses) under LF_SENSOR_SURFACES_CENTRED; "
+                                            "lf_set_sensor_ghost_surfaces(LF_SENSOR_SURFACES_POSED) marches them");
   if (lambda < 0 || lambda >= ctx->lens.n_lambda || n > 0x7fffffffull / 8)
     return lf_fail(ctx, LF_ERR_INVALID, "lf_march_sensor_path_rays: wavelength index / count out of range");
   if (i < 0 || i >= ctx->lens.n_surf || i == ctx->lens.stop)

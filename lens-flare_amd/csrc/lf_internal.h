@@ -492,12 +492,14 @@ constexpr int kSceneCounters = 4;
 // the paths' own table: one row list per (sensor path, wavelength), resident on the device.  Its dirty test is by content:
 // a launch forms the rows on the host (a few hundred, microseconds) and uploads them only where they differ from
 // table_host, what the device holds -- so a change of the lens, its focus, films, stacks, aspheric or biconic records, the
-// reflectance or the selection is caught without every setter having to know the table.
+// reflectance, the pose records or the selection is caught without every setter having to know the table.  An upload counts
+// as one "sensor_table" of lf_timing_get.
 constexpr int kSensorStats = 4;   // rays started, that reached the mirror, lost off the rectangle there, lit (ray, light) pairs
 struct LfSensorGhosts {
   int n_refl = 0;
   float refl[LF_MAX_LAMBDA] = {};
   int mode = LF_SENSOR_GHOSTS_OFF;
+  int surfaces = LF_SENSOR_SURFACES_CENTRED;   // lf_set_sensor_ghost_surfaces (a setting of the context: nothing clears it)
   int n_sel = -1;
   int sel[LF_MAX_SURFACES] = {};
   unsigned char* table_dev = nullptr;
@@ -508,7 +510,8 @@ struct LfSensorGhosts {
 
 // ---- timing ---------------------------------------------------------------------------------
 enum LfKernelId { LFK_MARCH = 0, LFK_FLARE_LAYER, LFK_GHOST_RASTER, LFK_DFT, LFK_FRAME_SETUP,
-                  LFK_TONEMAP, LFK_EXCHANGE, LFK_SCENE, LFK_CULL, LFK_CULL_AUDIT, LFK_CULL_CACHE_BUILD, LFK_FLARE_VIS, LFK_MARCH_SENSOR, LFK_COUNT };
+                  LFK_TONEMAP, LFK_EXCHANGE, LFK_SCENE, LFK_CULL, LFK_CULL_AUDIT, LFK_CULL_CACHE_BUILD, LFK_FLARE_VIS, LFK_MARCH_SENSOR,
+                  LFK_SENSOR_TABLE, LFK_COUNT };
 
 struct LfTimedLaunch { int kernel; hipEvent_t start, stop; };
 

@@ -7,10 +7,15 @@
 //                                  paths' OWN table -- one self-contained row list per (path, wavelength) (lf_path_table.h), read
 //                                  through the scalar cache -- geometry first, the weighted march again only for the lanes the
 //                                  lights' pre-test admits, lit rays through lights_epilogue.  SURF: 0 spheres only, 1 + aspheric
-//                                  rows, 2 + biconic rows.  Adds to the ghost buffer on the ordinary launch's fixed-point grid.
+//                                  rows, 2 + biconic rows, 3 + posed rows (lf_set_sensor_ghost_surfaces(LF_SENSOR_SURFACES_POSED)
+//                                  on a lens with pose records: one more wave-uniform branch, on LF_EV_POSE, to pose_event --
+//                                  lf_pose.h; SURF <= 2 is the code it was).  Adds to the ghost buffer on the ordinary launch's
+//                                  fixed-point grid.
 //   k_march_sensor_path_rays       lf_march_sensor_path_rays: k_march_path_rays with the sensor row
 // Both always aim at the DEFAULT disc, the rear element's clear aperture: the first mirror of a sensor path lies behind the
-// stop or has the stop's image clipped by what follows (the comment on lf_set_pupil_target).
+// stop or has the stop's image clipped by what follows (the comment on lf_set_pupil_target).  For a posed lens the disc is the
+// CENTRED rear element's clear aperture at its nominal vertex plane, also when that element is decentred -- the convention of
+// the ordinary posed march and of the lens camera: it says where the samples aim and approximates nothing of the event.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -23,6 +28,7 @@
 #include "lf_march_common.h"
 #include "lf_asphere.h"
 #include "lf_biconic.h"
+#include "lf_pose.h"
 #include "lf_path_table.h"
 #include "lf_sensor_event.h"
 
@@ -32,7 +38,10 @@ namespace {
 
 constexpr int kSensorWgWaves = 8;
 
-// The table: a header, one entry per (path, wavelength), the rows (128-byte aligned), the stack records behind them.
+// The table: a header, one entry per (path, wavelength), the rows (128-byte aligned), the stack records behind them and --
+// only where SURF = 3 reads it -- ONE LfPoseRec per posed interface behind those, from a 64-byte boundary on (a pose depends
+// neither on the wavelength nor on the direction of travel).  A posed row carries LF_EV_POSE with LF_EV_ASPH or LF_EV_BICONIC
+// (a sphere or a plane as the biconic {1/R, 0, 0}), and in its spare dword the record's byte offset from the table's start.
 struct alignas(32) LfSensorTabHdr {
   int n_paths, n_lambda;
   int pad[6];
@@ -52,6 +61,7 @@ struct SRow {
   int kind;
   float cn22, rn2, delta, fs, fo, fi;
   int coated;
+  unsigned pose;   // (a posed row's: the byte offset of its pose record)
 };
 __device__ __forceinline__ SRow load_srow(sc_ptr tab, unsigned off) {
   const lf_i16 v = *(lf_const_prow_ptr)(tab + off);
@@ -60,6 +70,7 @@ __device__ __forceinline__ SRow load_srow(sc_ptr tab, unsigned off) {
   r.sc = __int_as_float(v[4]); r.h2 = __int_as_float(v[5]); r.sgn = __int_as_float(v[6]); r.kind = v[7];
   r.cn22 = __int_as_float(v[8]); r.rn2 = __int_as_float(v[9]); r.delta = __int_as_float(v[10]);
   r.fs = __int_as_float(v[11]); r.fo = __int_as_float(v[12]); r.fi = __int_as_float(v[13]); r.coated = v[14];
+  r.pose = (unsigned)v[15];
   return r;
 }
 // a row's aspheric / biconic record: its last 32 bytes, one scalar load
@@ -117,6 +128,12 @@ __device__ __forceinline__ lanemask sensor_row(Ray& r, sc_ptr tab, unsigned off,
   const bool reflect = (w.kind & LF_EV_REFLECT) != 0;
   if (VAR & kVarCoat) {
     const SensorCoat coat{tab + off, w.coated};
+    if (SURF >= 3 && (w.kind & LF_EV_POSE)) {   // wave-uniform: the row's pose record, through the scalar cache
+      const LfAsphRec rec = load_srow_rec(tab, off);
+      const LfPoseRec pose = load_pose((const LfPoseRec*)(const char*)tab, w.pose);
+      return pose_event<W>(r, w.dzv, w.curv, (w.kind & LF_EV_ASPH) != 0, rec, pose, w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo,
+                           w.fi, coat);
+    }
     if (SURF >= 2 && (w.kind & LF_EV_BICONIC)) {
       const LfAsphRec rec = load_srow_rec(tab, off);
       return biconic_event<W>(r, w.dzv, w.curv, LfBicRec{rec.kappa, rec.a[0], rec.a[1], {}}, w.delta, w.h2, reflect, w.sgn, geom_ok,
@@ -126,6 +143,11 @@ __device__ __forceinline__ lanemask sensor_row(Ray& r, sc_ptr tab, unsigned off,
       return asphere_event<W>(r, w.dzv, w.curv, load_srow_rec(tab, off), w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo, w.fi, coat);
     return surface_event<W>(r, w.dzv, w.curv, w.ch, w.c2, w.sc, w.cn22, w.rn2, w.delta, w.h2, reflect, (w.kind & LF_EV_FLAT) != 0,
                             w.sgn, geom_ok, w.fs, w.fo, w.fi, coat);
+  }
+  if (SURF >= 3 && (w.kind & LF_EV_POSE)) {
+    const LfAsphRec rec = load_srow_rec(tab, off);
+    const LfPoseRec pose = load_pose((const LfPoseRec*)(const char*)tab, w.pose);
+    return pose_event<W>(r, w.dzv, w.curv, (w.kind & LF_EV_ASPH) != 0, rec, pose, w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo, w.fi);
   }
   if (SURF >= 2 && (w.kind & LF_EV_BICONIC)) {
     const LfAsphRec rec = load_srow_rec(tab, off);
@@ -307,6 +329,11 @@ __global__ __launch_bounds__(256) void k_march_sensor_path_rays(const LfLensDev*
       ok = stop_event<true, FILT>(r, w.dzv, w.h2, P->inv_stop_h, mask, mw, mh);
     } else if (w.kind & LF_EV_SENSOR) {
       ok = sensor_event<true>(r, w.dzv, sa.xmax, sa.ymax, w.fs);
+    } else if (SURF >= 3 && (w.kind & LF_EV_POSE)) {   // wave-uniform
+      const LfPoseRec pose = load_pose((const LfPoseRec*)P, (unsigned)w.pad);
+      const bool asph = (w.kind & LF_EV_ASPH) != 0;
+      if (COAT) ok = pose_event<true>(r, w.dzv, w.curv, asph, w.asph, pose, w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo, w.fi, PathCoat{&w});
+      else ok = pose_event<true>(r, w.dzv, w.curv, asph, w.asph, pose, w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo, w.fi);
     } else if (SURF >= 2 && (w.kind & LF_EV_BICONIC)) {
       const LfBicRec rec{w.asph.kappa, w.asph.a[0], w.asph.a[1], {}};
       if (COAT) ok = biconic_event<true>(r, w.dzv, w.curv, rec, w.delta, w.h2, reflect, w.sgn, geom_ok, w.fs, w.fo, w.fi, PathCoat{&w});
@@ -333,15 +360,46 @@ __global__ __launch_bounds__(256) void k_march_sensor_path_rays(const LfLensDev*
   }
 }
 
-// host: the rows of the sensor path of interface i at wavelength l, from base + first_row on (lf_sensor_path_sequence's order)
+// host: the pose block of a table -- ONE record per posed interface, in the interfaces' order; interface k's is the
+// pose_slot(k)-th.  The block starts at a 64-byte boundary (load_pose's two aligned 32-byte loads).
+int pose_slot(const lf_ctx* ctx, int k) {
+  int m = 0;
+  for (int j = 0; j < k; j++) m += ctx->pose.on[j] != 0 ? 1 : 0;
+  return m;
+}
+void pose_block_fill(const lf_ctx* ctx, unsigned char* block) {
+  const LfPoses& Po = ctx->pose;
+  for (int k = 0; k < ctx->lens.n_surf; k++) {
+    if (!Po.on[k]) continue;
+    const LfPoseRec rec = lf_pose_make(Po.t[3 * k], Po.t[3 * k + 1], Po.t[3 * k + 2], Po.a[3 * k], Po.a[3 * k + 1], Po.a[3 * k + 2]);
+    std::memcpy(block + (size_t)pose_slot(ctx, k) * sizeof(rec), &rec, sizeof(rec));
+  }
+}
+
+// host: the rows of the sensor path of interface i at wavelength l, from base + first_row on (lf_sensor_path_sequence's order).
+// pose_off != 0 (SURF = 3): the byte offset of the table's pose block; every crossing of a posed interface then becomes a
+// posed row (build_path_table's fields, written HERE and not in lf_path_row_fill: lf_march_path_rays' rows stay what they
+// are) that points at the interface's one record.  The stop's rows and the sensor's never carry the bit.
 lf_status sensor_path_rows(const lf_ctx* ctx, int l, int i, unsigned char* base, size_t first_row, size_t* next_stack, size_t cap,
-                           int* n_rows) {
+                           size_t pose_off, int* n_rows) {
   const LfLensDev& L = ctx->lens;
+  const LfPoses& Po = ctx->pose;
   const int n = L.n_surf;
   int cnt = 0;
   lf_status st = LF_OK;
   auto put = [&](int k, int from, bool reflect, bool fwd) {
-    if (st == LF_OK) st = lf_path_row_fill(ctx, l, k, from, reflect, fwd, base, first_row + (size_t)cnt * sizeof(LfPathRow), next_stack, cap);
+    const size_t row_off = first_row + (size_t)cnt * sizeof(LfPathRow);
+    if (st == LF_OK) st = lf_path_row_fill(ctx, l, k, from, reflect, fwd, base, row_off, next_stack, cap);
+    if (st == LF_OK && pose_off != 0 && Po.on[k] && L.surf[k].is_stop == 0.0f) {
+      LfPathRow& w = *reinterpret_cast<LfPathRow*>(base + row_off);
+      w.kind |= LF_EV_POSE;
+      if (!(w.kind & LF_EV_BICONIC) && !(w.kind & LF_EV_ASPH && ctx->asph.n > 0)) {   // a sphere or a plane: as a biconic
+        w.kind = (w.kind & ~LF_EV_ASPH) | LF_EV_BICONIC;
+        w.asph = LfAsphRec{};
+        w.asph.kappa = L.surf[k].curv;
+      }
+      w.pad = (int)(pose_off + (size_t)pose_slot(ctx, k) * sizeof(LfPoseRec));
+    }
     cnt++;
   };
   for (int k = n - 1; k > i; k--) put(k, k + 1, false, false);
@@ -370,7 +428,28 @@ void default_disc(const lf_ctx* ctx, LfLensDev& L) {
 }
 
 // SURF of the kernels: what kinds of row the table can hold (lf_surface_record_kind)
-int surf_kind(const lf_ctx* ctx) { return lf_march_biconic(ctx) ? 2 : lf_march_aspheric(ctx) ? 1 : 0; }
+// (3: posed rows -- only for a lens with a pose record under LF_SENSOR_SURFACES_POSED; the entry points refuse such a lens
+// under LF_SENSOR_SURFACES_CENTRED, and a lens without records launches what it launched whatever the setting)
+int surf_kind(const lf_ctx* ctx) {
+  if (lf_march_posed(ctx) && ctx->sensor.surfaces == LF_SENSOR_SURFACES_POSED) return 3;
+  return lf_march_biconic(ctx) ? 2 : lf_march_aspheric(ctx) ? 1 : 0;
+}
+
+// host: the stack records' bytes of the whole selection, exactly: the pose block's offset goes into the rows while they are
+// written, before the last stack record is.  The sensor path of interface i crosses interface k three times where k > i, twice
+// where k == i and once in front of it (lf_sensor_path_sequence); lf_path_row_fill appends one record per crossing of a
+// stacked interface.
+size_t sensor_stack_bytes(const lf_ctx* ctx, const int* sel, int n_sel) {
+  const LfCoatings& C = ctx->coat;
+  if (C.n_stacked <= 0) return 0;
+  size_t bytes = 0;
+  for (int q = 0; q < n_sel; q++)
+    for (int k = 0; k < ctx->lens.n_surf; k++) {
+      if (C.n_layers[k] < 2 || ctx->lens.surf[k].is_stop != 0.0f) continue;
+      bytes += (size_t)(k > sel[q] ? 3 : k == sel[q] ? 2 : 1) * sizeof(float) * kStackDwords(C.n_layers[k]);
+    }
+  return bytes * (size_t)ctx->lens.n_lambda;
+}
 
 // host: the whole table of the selection; uploads it where the device's copy differs
 lf_status sensor_table_upload(lf_ctx* ctx, const int* sel, int n_sel) {
@@ -384,17 +463,27 @@ lf_status sensor_table_upload(lf_ctx* ctx, const int* sel, int n_sel) {
   LfSensorTabHdr& H = *reinterpret_cast<LfSensorTabHdr*>(buf.data());
   H.n_paths = n_sel; H.n_lambda = nl;
   size_t next_row = hdr, next_stack = rows_end;
+  // (SURF = 3 alone reads a pose block: it lies behind the last stack record, from the next 64-byte boundary on)
+  const bool posed = surf_kind(ctx) == 3;
+  const size_t stack_end = rows_end + sensor_stack_bytes(ctx, sel, n_sel);
+  const size_t pose_off = posed ? (stack_end + 63) & ~(size_t)63 : 0;
   for (int q = 0; q < n_sel; q++)
     for (int l = 0; l < nl; l++) {
       LfSensorPathHdr& ph = reinterpret_cast<LfSensorPathHdr*>(buf.data() + sizeof(LfSensorTabHdr))[q * nl + l];
       int cnt = 0;
-      if (3 * n - 2 * sel[q] > kPathRowsMax || sensor_path_rows(ctx, l, sel[q], buf.data(), next_row, &next_stack, buf.size(), &cnt) != LF_OK)
+      if (3 * n - 2 * sel[q] > kPathRowsMax ||
+          sensor_path_rows(ctx, l, sel[q], buf.data(), next_row, &next_stack, buf.size(), pose_off, &cnt) != LF_OK)
         return lf_fail(ctx, LF_ERR_STATE, "sensor ghosts: a path's rows exceed their table");
       ph.off = (int)next_row; ph.n_ev = cnt; ph.iface = sel[q];
       ph.skip = ctx->sensor.refl[l] == 0.0f ? 1 : 0;
       next_row += (size_t)cnt * sizeof(LfPathRow);
     }
   buf.resize(next_stack);
+  if (posed) {   // (after the resize, which cuts the table at its last stack record: the block is part of the allocation)
+    if (next_stack != stack_end) return lf_fail(ctx, LF_ERR_STATE, "sensor ghosts: the stack records are not where the pose block expects them");
+    buf.resize(pose_off + (size_t)ctx->pose.n * sizeof(LfPoseRec), 0);
+    pose_block_fill(ctx, buf.data() + pose_off);
+  }
   LfSensorGhosts& S = ctx->sensor;
   if (S.table_dev && buf == S.table_host) return LF_OK;
   // (the stream is non-blocking: a kernel still walking the previous table must be done before it changes -- build_event_table)
@@ -406,7 +495,9 @@ lf_status sensor_table_upload(lf_ctx* ctx, const int* sel, int n_sel) {
     S.table_cap = buf.size();
   }
   S.table_host.clear();
+  hipEvent_t ev = lf_timing_begin(ctx, LFK_SENSOR_TABLE);   // ("sensor_table": one per upload)
   LF_HIP(ctx, hipMemcpy(S.table_dev, buf.data(), buf.size(), hipMemcpyHostToDevice));
+  lf_timing_end(ctx, LFK_SENSOR_TABLE, ev);
   S.table_host.swap(buf);
   return LF_OK;
 }
@@ -512,7 +603,10 @@ lf_status lfk_march_sensor(lf_ctx* ctx, int spp, uint64_t key, bool add) {
   const int surf = surf_kind(ctx);
   hipEvent_t ev = lf_timing_begin(ctx, LFK_MARCH_SENSOR);
 #define LF_LAUNCH_SENSOR(VV)                                                                                             \
-  do { if (surf == 2) LF_LAUNCH_SENSOR2(VV, 2); else if (surf == 1) LF_LAUNCH_SENSOR2(VV, 1); else LF_LAUNCH_SENSOR2(VV, 0); } while (0)
+  do {                                                                                                                   \
+    if (surf == 3) LF_LAUNCH_SENSOR2(VV, 3); else if (surf == 2) LF_LAUNCH_SENSOR2(VV, 2);                               \
+    else if (surf == 1) LF_LAUNCH_SENSOR2(VV, 1); else LF_LAUNCH_SENSOR2(VV, 0);                                         \
+  } while (0)
 #define LF_LAUNCH_SENSOR2(VV, SS)                                                                                        \
   hipLaunchKernelGGL((k_march_sensor<VV, SS>), dim3((unsigned)blocks), dim3(64 * kSensorWgWaves), 0, ctx->stream, ctx->lens_dev, \
                      (const unsigned char*)S.table_dev, m.texels, a, sa, ctx->ghost, ctx->accum, S.stats_dev)
@@ -543,14 +637,18 @@ lf_status lfk_march_sensor_path_rays(lf_ctx* ctx, int lambda, int i, int n, cons
   ctx->lens.pitch = ctx->sensor_w_mm / (float)std::max(1, ctx->W);
   const LfLensDev& L = ctx->lens;
   if (3 * L.n_surf - 2 * i > kPathRowsMax) return lf_fail(ctx, LF_ERR_STATE, "lf_march_sensor_path_rays: the path's rows exceed their table");
-  std::vector<unsigned char> buf(sizeof(LfPathDev) + kPathStackBytes, 0);
+  // (SURF = 3: the pose block behind the table and its stack records, from a 64-byte boundary on -- one record per posed interface)
+  const bool posed = surf_kind(ctx) == 3;
+  const size_t pose_off = posed ? (sizeof(LfPathDev) + kPathStackBytes + 63) & ~(size_t)63 : 0;
+  std::vector<unsigned char> buf(posed ? pose_off + (size_t)ctx->pose.n * sizeof(LfPoseRec) : sizeof(LfPathDev) + kPathStackBytes, 0);
   LfPathDev& P = *reinterpret_cast<LfPathDev*>(buf.data());
   P.inv_stop_h = 1.0f / L.stop_h;
   P.front_zv = L.surf[0].zv;
   P.n_start = L.n_start[lambda];
   size_t next_stack = sizeof(LfPathDev);
-  if (sensor_path_rows(ctx, lambda, i, buf.data(), offsetof(LfPathDev, row), &next_stack, buf.size(), &P.n) != LF_OK)
+  if (sensor_path_rows(ctx, lambda, i, buf.data(), offsetof(LfPathDev, row), &next_stack, sizeof(LfPathDev) + kPathStackBytes, pose_off, &P.n) != LF_OK)
     return lf_fail(ctx, LF_ERR_STATE, "lf_march_sensor_path_rays: the path's rows exceed their table");
+  if (posed) pose_block_fill(ctx, buf.data() + pose_off);
   LfLensDev up = ctx->lens;
   default_disc(ctx, up);
   SensorArgs sa;
@@ -567,7 +665,10 @@ lf_status lfk_march_sensor_path_rays(lf_ctx* ctx, int lambda, int i, int n, cons
   hipLaunchKernelGGL((k_march_sensor_path_rays<FF, CC, SS>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream,    \
                      ctx->lens_dev, (const LfPathDev*)d_tab, m.texels, m.w, m.h, sa, n, d_xy, d_uv, d_out)
 #define LF_LAUNCH_SPATH2(FF, CC)                                                                                              \
-  do { if (surf == 2) LF_LAUNCH_SPATH(FF, CC, 2); else if (surf == 1) LF_LAUNCH_SPATH(FF, CC, 1); else LF_LAUNCH_SPATH(FF, CC, 0); } while (0)
+  do {                                                                                                                        \
+    if (surf == 3) LF_LAUNCH_SPATH(FF, CC, 3); else if (surf == 2) LF_LAUNCH_SPATH(FF, CC, 2);                                \
+    else if (surf == 1) LF_LAUNCH_SPATH(FF, CC, 1); else LF_LAUNCH_SPATH(FF, CC, 0);                                          \
+  } while (0)
     if (filt && coat) LF_LAUNCH_SPATH2(true, true);
     else if (filt) LF_LAUNCH_SPATH2(true, false);
     else if (coat) LF_LAUNCH_SPATH2(false, true);
